@@ -1,11 +1,21 @@
 """Headline benchmark: rendered views/sec of the LDI splat+warp hot path.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3]
+                  [--dump-outputs DIR] [--full]
 
 A "step" is one `forward_splat(compose_layers=True, compute_trg_disp=False,
 trg_downsampling=0.5)` (reference ldi.py:71-182: projection + soft z-buffer
 weights + 4-corner splat + normalise/compose) over one batch of synthetic LDI
 tensors that are already resident in HBM.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the line (headline
+figure, `ms_per_step`, the `roofline` of the same timed launches).  `--full`
+adds what takes runs of its own: `extra` (backward, both outputs, the Python
+call surface, the other workloads, the training step), `roofline.traffic` (two
+rocprofv3 --pmc passes), `cpu_baseline` and, N > 1, `extra.weak`.
+`--dump-outputs DIR` writes the last timed step's rendering (rank 0) as
+DIR/img.npy and DIR/wts.npy (float32); the inputs are seeded, so two builds
+can be compared output for output.
 
 Workloads (BASELINE.json `configs`):
   cfg3  KITTI, 4-layer, 256x768, batch 32 -- the configuration north_star's
@@ -21,7 +31,7 @@ batch is split B/N over the ranks (SURVEY.md 8e / BASELINE config 3: 32 views
 that split, the one north_star's ">= 6x from 1 to 8 GPUs" is about.  The same
 run then also times the weak-scaling case (every rank renders the whole batch:
 the per-GPU minibatch of a data-parallel training run) and reports it under
-`extra.weak`; `--scaling weak` makes that the headline instead.  `--shard-of N`
+`extra.weak` (with --full); `--scaling weak` makes that the headline instead.  `--shard-of N`
 times one rank's shard of an N-rank split on a single GPU.  `python bench.py --gpus N` from a bare
 shell re-launches itself under torch.distributed.run (one rank per GPU).
 
@@ -614,6 +624,7 @@ def timed_region(r, steps, warmup, launch_mode, dist, dev):
     for _ in range(max(warmup, 1)):
       r.launch()
     stream.synchronize()
+    turn0 = r.turn  # the input set the timed steps start on (graph: captured)
     graph = None
     if launch_mode == 'graph':
       try:
@@ -643,6 +654,10 @@ def timed_region(r, steps, warmup, launch_mode, dist, dev):
       stream.synchronize()
     ev0 = torch.cuda.Event(enable_timing=True)
     ev1 = torch.cuda.Event(enable_timing=True)
+    # (eager: the settle loop ran a time-dependent number of steps; the timed
+    # steps walk the same input sets as a captured graph would, so the last
+    # step's inputs do not depend on the clock)
+    r.turn = turn0
     if dist is not None:
       dist.barrier()
     torch.cuda.synchronize()
@@ -662,6 +677,22 @@ def timed_region(r, steps, warmup, launch_mode, dist, dev):
   return elapsed, ev_ms, launch_mode
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(r, out_dir):
+  """What the timed path handed its caller in the last timed step: the composed
+  rendering `img` (1 x B x Ht x Wt x 3) and its weights `wts` (1 x B x Ht x Wt
+  x 1), float32, as out_dir/img.npy and out_dir/wts.npy.  Every workload fits
+  in DUMP_MAX_BYTES; past it only the first views of the batch are written."""
+  os.makedirs(out_dir, exist_ok=True)
+  per_view = (r.img[0, 0].numel() + r.wts[0, 0].numel()) * 4
+  views = max(1, min(r.img.shape[1], DUMP_MAX_BYTES // per_view))
+  for name, t in (('img', r.img), ('wts', r.wts)):
+    np.save(os.path.join(out_dir, name + '.npy'),
+            t[:, :views].float().cpu().numpy())
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--gpus', type=int, default=1)
@@ -673,15 +704,26 @@ def main():
   ap.add_argument('--launch', default='graph', choices=['graph', 'eager'])
   ap.add_argument('--band-rows', type=int, default=0)
   ap.add_argument('--threads', type=int, default=0)
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='after the headline also measure what takes runs of its '
+                  'own: extra (backward, both outputs, Python call surface, other '
+                  'workloads, training step), roofline.traffic, cpu_baseline and, '
+                  'N > 1, extra.weak; a plain run times the headline only')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write the last timed step\'s outputs (rank 0) as '
+                  'DIR/img.npy and DIR/wts.npy, float32')
+  ap.add_argument('--no-cpu-baseline', action='store_true',
+                  help='with --full: skip cpu_baseline')
   ap.add_argument('--no-extra', action='store_true',
-                  help='skip the extras (backward, other workloads, traffic)')
+                  help='with --full: skip the extras (backward, other workloads, '
+                  'training step)')
   ap.add_argument('--train-step-budget', type=float, default=45.0,
-                  help='seconds of wall time for extra.train_step (the full '
-                  'training step as samples/s and fraction of the MFMA peak); 0: skip')
+                  help='with --full: seconds of wall time for extra.train_step '
+                  '(the full training step as samples/s and fraction of the MFMA '
+                  'peak); 0: skip')
   ap.add_argument('--traffic', default='measure', choices=['measure', 'off'],
-                  help='roofline.traffic: two rocprofv3 --pmc passes of this '
-                  'script (N=1 only), or null')
+                  help='with --full: roofline.traffic from two rocprofv3 --pmc '
+                  'passes of this script (N=1 only), or null')
   ap.add_argument('--inner-traffic', action='store_true',
                   help=argparse.SUPPRESS)
   ap.add_argument('--selftest-backend', default=None, choices=['gloo'],
@@ -693,7 +735,8 @@ def main():
                   'LSI_HIP_LIB=hooks (build.py --hooks)')
   ap.add_argument('--scaling', default='strong', choices=['weak', 'strong'],
                   help='N > 1: strong = the workload\'s batch is split B/N over '
-                  'the ranks (default; the weak figure is added under extra.weak), '
+                  'the ranks (default; with --full the weak figure is added under '
+                  'extra.weak), '
                   'weak = every rank renders the whole batch (per-GPU work fixed)')
   ap.add_argument('--shard-of', type=int, default=1,
                   help='N=1 only: time the per-rank shard of an N-rank run (what '
@@ -802,15 +845,17 @@ def main():
   r.desc.reserved = args.debug_flags
   elapsed, ev_ms, launch_mode = timed_region(r, args.steps, args.warmup,
                                              args.launch, dist, dev)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(r, args.dump_outputs)
   ev_ms_rank = ev_ms
   elapsed, ev_ms = reduce_max([elapsed, ev_ms], dist, dev)
   # per-rank average launch time: slowest and fastest rank (N > 1: which GPU
   # holds the job back)
   ev_min = -reduce_max([-ev_ms_rank], dist, dev)[0]
   # N > 1, batch split over the ranks: the weak-scaling figure of the same run
-  # (every rank renders the workload's whole batch) goes under extra.weak
+  # (every rank renders the workload's whole batch) goes under extra.weak (--full)
   weak = None
-  if world > 1 and scaling == 'strong' and args.shard_of == 1:
+  if args.full and world > 1 and scaling == 'strong' and args.shard_of == 1:
     del r
     torch.cuda.empty_cache()
     rw = build_renderer(args.workload, batch, 1000 + rank, dev, args)
@@ -872,7 +917,7 @@ def main():
     }
     if weak is not None:
       out['extra'] = {'weak': weak}
-    if world == 1 and not args.no_extra:
+    if args.full and world == 1 and not args.no_extra:
       extra = {}
       bwd_us = time_backward(r)
       balg = backward_bytes(nl, b_local, h, w)
@@ -938,9 +983,9 @@ def main():
         except Exception as e:  # pylint: disable=broad-except
           extra['train_step'] = {'error': '%s: %s' % (type(e).__name__, e)}
       out['extra'] = extra
-    if world == 1 and args.traffic == 'measure':
+    if args.full and world == 1 and args.traffic == 'measure':
       out['roofline']['traffic'] = measure_traffic(args)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
       out['cpu_baseline'] = cpu_baseline(nl, b_local, h, w, cams, max_disp, bg)
     print(json.dumps(out))
   if dist is not None:

@@ -92,8 +92,8 @@ def test_two_ranks_split_the_batch_and_add_the_weak_figure(built_lib):
   env = {k: v for k, v in os.environ.items()
          if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
   env['LSI_BENCH_SHARE_GPU'] = '1'
-  out = _torchrun(2, ['--gpus', '2', '--steps', '5', '--warmup', '2', '--no-cpu-baseline',
-                      '--no-extra', '--traffic', 'off'], env)
+  out = _torchrun(2, ['--gpus', '2', '--steps', '5', '--warmup', '2', '--full',
+                      '--no-cpu-baseline', '--no-extra', '--traffic', 'off'], env)
   assert out.returncode == 0, out.stderr[-3000:]
   rec = _one_json_line(out)
   assert rec['n_gpus'] == 2 and rec['scaling'] == 'strong'
@@ -101,3 +101,39 @@ def test_two_ranks_split_the_batch_and_add_the_weak_figure(built_lib):
   assert rec['value'] > 0 and abs(rec['value'] - 32 * 5 / (rec['ms_per_step'] * 5e-3)) < 1e-6 * rec['value']
   weak = rec['extra']['weak']
   assert weak['scaling'] == 'weak' and weak['views_per_gpu'] == 32 and weak['value'] > 0
+
+
+def test_plain_run_is_lean_and_dumps_the_last_steps_rendering(built_lib, ref_cpu, tmp_path):
+  """A plain run (no --full) prints the headline line alone -- no `extra`, no
+  `cpu_baseline`, no measured traffic -- and `--dump-outputs` writes what the
+  last timed step rendered: the C oracle on that step's inputs (the seeded input
+  sets, walked round-robin from the first warm-up step on) gives the same views."""
+  if not torch.cuda.is_available():
+    pytest.fail('gpu test selected but no ROCm device is visible')
+  import numpy as np
+  sys.path.insert(0, ROOT)
+  import bench
+  env = {k: v for k, v in os.environ.items()
+         if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+  steps, warmup = 4, 3
+  out = subprocess.run(
+      [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps),
+       '--warmup', str(warmup), '--workload', 'cfg2', '--dump-outputs', str(tmp_path)],
+      env=env, capture_output=True, text=True, timeout=600)
+  assert out.returncode == 0, out.stderr[-2000:]
+  rec = _one_json_line(out)
+  assert rec['steps'] == steps and rec['ms_per_step'] > 0
+  assert 'extra' not in rec and 'cpu_baseline' not in rec
+  assert rec['roofline']['traffic'] is None
+  img = np.load(os.path.join(str(tmp_path), 'img.npy'))
+  wts = np.load(os.path.join(str(tmp_path), 'wts.npy'))
+  nl, h, w, b, _, cams, max_disp, bg = bench.WORKLOADS['cfg2']
+  assert img.dtype == np.float32 and img.shape == (1, b, h // 2, w // 2, 3)
+  assert wts.dtype == np.float32 and wts.shape == (1, b, h // 2, w // 2, 1)
+  last = (warmup + steps - 1) % bench.rotation_sets(nl, b, h, w)
+  tex, disp, mat = bench.make_inputs(nl, b, h, w, cams, max_disp, 1000 + 7919 * last,
+                                     torch.device('cuda:0'))
+  want = ref_cpu.forward_splat(tex.cpu().numpy(), None, disp.cpu().numpy(), mat.numpy(),
+                               0.5, bg, max_disp, bench.ZBUF_SCALE, True, want_disp=False)
+  np.testing.assert_allclose(img, want['img'], rtol=0, atol=2e-5)
+  np.testing.assert_allclose(wts, want['wts'], rtol=1e-4)

@@ -30,7 +30,7 @@ for rep in range(reps):
     want_traffic = '--traffic' in extra
     if want_traffic:
       extra.remove('--traffic')
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline',
            '--no-extra'] + ([] if (want_traffic and rep == 0) else ['--traffic', 'off']) + extra
     try:
       out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)

@@ -11,12 +11,12 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-r04}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-timeout 900 python $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 900 python $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 for wl in cfg2 cfg5; do
   timeout 300 python $R/bench.py --workload $wl --no-cpu-baseline --no-extra --traffic off > $OUT/bench_$wl.json 2>> $OUT/bench_default.err
 done
 # (cfg4: with the FETCH / WRITE traffic passes of the any-pose path)
-timeout 600 python $R/bench.py --workload cfg4 --no-cpu-baseline --no-extra > $OUT/bench_cfg4.json 2>> $OUT/bench_default.err
+timeout 600 python $R/bench.py --workload cfg4 --full --no-cpu-baseline --no-extra > $OUT/bench_cfg4.json 2>> $OUT/bench_default.err
 for n in 2 4 8; do
   timeout 300 python $R/bench.py --shard-of $n --no-cpu-baseline --no-extra --traffic off > $OUT/bench_cfg3_shard_of_$n.json 2>> $OUT/bench_default.err
 done

@@ -61,6 +61,10 @@ extern "C" {
                              /* 4 outputs writes).  One 16-byte load then      */
                              /* fetches a pixel's colour and disparity.  The   */
                              /* entry points verify it (LSI_EINVAL if not).    */
+#define LSI_GRAD_M 64u       /* backward only: the gradient w.r.t. the B x 4 x 4 */
+                             /* matrices M as well (lsi_splat_bwd_m,           */
+                             /* lsi_splat_bwd_both_m; the entries without _m   */
+                             /* refuse it with LSI_EINVAL)                     */
 
 /* LsiSplatDesc.path: which kernel family renders the splat.                  */
 #define LSI_PATH_AUTO 0      /* library decides from the descriptor          */
@@ -216,7 +220,10 @@ int lsi_splat_fwd(const LsiSplatDesc* desc, const float* tex, const float* disp,
  * stride), the streamed kernel
  * (csrc/lsi_splat_bwd_stream.hip) derives that canvas in LDS and leaves the
  * workspace untouched; other descriptors take a pre-pass + one thread per
- * source pixel.
+ * source pixel.  With LSI_GRAD_M in desc->flags the workspace also holds one
+ * 16-float partial of the matrix gradient per workgroup (lsi_splat_bwd_m).
+ * The entries without _m refuse LSI_GRAD_M (LSI_EINVAL) and otherwise are
+ * lsi_splat_bwd_m / lsi_splat_bwd_both_m with g_M = NULL.
  */
 size_t lsi_splat_bwd_workspace_bytes(const LsiSplatDesc* desc);
 
@@ -225,6 +232,31 @@ int lsi_splat_bwd(const LsiSplatDesc* desc, const float* tex, const float* disp,
                   const float* out_wts, const float* g_img, const float* g_wts,
                   float* g_tex, float* g_disp_in, float* g_mask,
                   void* workspace, size_t workspace_bytes, lsi_stream_t stream);
+
+/*
+ * lsi_splat_bwd plus the gradient w.r.t. M, the B x 4 x 4 src->trg matrices
+ * (projection.py:71-86 -> ldi.py:134-140: q = M p for p = (x+.5, y+.5, 1, d),
+ * u = q0/n' * s, v = q1/n' * s, dd = q3/n', n' = divide_safe(q2)), what TF
+ * autodiff of the reference gives k_s, k_t, rot and t through
+ * tf.matrix_inverse / tf.matmul:
+ *   g_M[b][j][k] = sum over l, y, x of dL/dq_j * p_k   (dL/dq_2 = dL/dn')
+ * with the same zero-gradient conventions as the rest of the backward (floor,
+ * clip, the 1e-3 corner clamp, dropped non-finite pixels: 0).  Requested by
+ * LSI_GRAD_M in desc->flags: then g_M (B x 4 x 4 fp32, contiguous,
+ * overwritten) must not be NULL (LSI_ENULL); without the flag it must be NULL
+ * (LSI_EINVAL) and the call is lsi_splat_bwd's, launch for launch.  Each
+ * workgroup of the backward kernel sums its pixels' shares in registers and
+ * across its waves, and writes one 16-float partial to the workspace; one more
+ * kernel adds the partials of each batch element in a fixed order (no float
+ * atomics: g_M is bitwise reproducible whatever LSI_DETERMINISTIC says).  The
+ * other outputs are bitwise those of the call without the flag.
+ */
+int lsi_splat_bwd_m(const LsiSplatDesc* desc, const float* tex,
+                    const float* disp, const float* mask, const float* M,
+                    const float* out_img, const float* out_wts,
+                    const float* g_img, const float* g_wts, float* g_tex,
+                    float* g_disp_in, float* g_mask, float* g_M, void* workspace,
+                    size_t workspace_bytes, lsi_stream_t stream);
 
 /*
  * forward_splat's two variants of one source view in ONE sweep: the reference's
@@ -256,6 +288,20 @@ int lsi_splat_bwd_both(const LsiSplatDesc* desc, const float* tex,
                        const float* g_img_c, const float* g_wts_c, float* g_tex,
                        float* g_disp_in, float* g_mask, void* workspace,
                        size_t workspace_bytes, lsi_stream_t stream);
+
+/*
+ * lsi_splat_bwd_both plus the gradient w.r.t. M (both outputs' share), as
+ * lsi_splat_bwd_m: LSI_GRAD_M in desc->flags, g_M B x 4 x 4, overwritten.
+ */
+int lsi_splat_bwd_both_m(const LsiSplatDesc* desc, const float* tex,
+                         const float* disp, const float* mask, const float* M,
+                         const float* out_img, const float* out_wts,
+                         const float* out_img_c, const float* out_wts_c,
+                         const float* g_img, const float* g_wts,
+                         const float* g_img_c, const float* g_wts_c,
+                         float* g_tex, float* g_disp_in, float* g_mask,
+                         float* g_M, void* workspace, size_t workspace_bytes,
+                         lsi_stream_t stream);
 
 /*
  * Parity/debug view of the projection stage: for every source pixel the four

@@ -154,6 +154,50 @@ __device__ __forceinline__ void store_stream_f1(float* p, float x) {
   __builtin_nontemporal_store(x, p);
 }
 
+// The camera gradient of the backward kernels (LSI_GRAD_M): dL/dM[j][k] =
+// sum over source pixels of dL/dq_j * p_k, p = (x + .5, y + .5, 1, d).  One
+// pixel's share added to a lane's 16 register accumulators (acc[4 j + k]).
+__device__ __forceinline__ void grad_m_add(float (&acc)[16], float gq0, float gq1,
+                                           float gn, float gq3, float px, float py,
+                                           float d) {
+  const float gq[4] = {gq0, gq1, gn, gq3};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    acc[4 * j + 0] = __fmaf_rn(gq[j], px, acc[4 * j + 0]);
+    acc[4 * j + 1] = __fmaf_rn(gq[j], py, acc[4 * j + 1]);
+    acc[4 * j + 2] = acc[4 * j + 2] + gq[j];
+    acc[4 * j + 3] = __fmaf_rn(gq[j], d, acc[4 * j + 3]);
+  }
+}
+
+// The workgroup's sum of the lanes' 16 accumulators, in a fixed order (a
+// butterfly over the wave's lanes, then the NW waves one after the other
+// through `red`, NW * 16 floats of LDS): threads 0 .. 15 write out[0 .. 15].
+// Every thread of the workgroup must call it.
+template <int NW>
+__device__ __forceinline__ void grad_m_block_sum(float (&acc)[16], float* red,
+                                                 float* out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    float v = acc[k];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_xor(v, o, 64);
+    acc[k] = v;
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) red[wave * 16 + k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    float v = red[threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v = v + red[w * 16 + threadIdx.x];
+    out[threadIdx.x] = v;
+  }
+}
+
 // fp32 atomic add that lowers to global_atomic_add_f32 / ds_add_f32 (no CAS
 // loop); the translation unit is built with -munsafe-fp-atomics.
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) {

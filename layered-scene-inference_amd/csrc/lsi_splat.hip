@@ -386,12 +386,15 @@ __global__ __launch_bounds__(256) void splat_bwd_pre_kernel(
 // (0,0,0,1) -- every rectified pair.  Then u = q0 * s exactly (x / 1 == x), so
 // the corner cells are the forward's bit for bit, and the projection and its
 // gradient need no division at all.
+// GRAD_M (LSI_GRAD_M): the pixel's dL/dM share is added to `acc` as well
+// (grad_m_add); the other outputs are the same bit for bit.
 struct BwdPx { float gt0, gt1, gt2, gm, gd; };
 
-template <bool SIMPLE_M>
+template <bool SIMPLE_M, bool GRAD_M>
 __device__ __forceinline__ BwdPx splat_bwd_core(
     const LsiSplatDesc& d, const float* __restrict__ m, int y, int x, float dv,
-    float mk, float t0, float t1, float t2, const float4* __restrict__ Gb) {
+    float mk, float t0, float t1, float t2, const float4* __restrict__ Gb,
+    float (&acc)[16]) {
   const float s = d.trg_downsampling;
   const float inv_md = div_rn(1.0f, d.max_disp);
   Proj p;
@@ -461,11 +464,21 @@ __device__ __forceinline__ BwdPx splat_bwd_core(
   float gd;
   if (SIMPLE_M) {  // n' == 1, M[2][3] == 0, M[3][3] == 1
     gd = (gX * s) * m[3] + (gY * s) * m[7] + gD;
+    if (GRAD_M) {
+      // (dL/dn' = -(dL/dq . q) / n'^2 with n' = 1; the indicator of
+      // divide_safe has no gradient)
+      const float gq0 = gX * s, gq1 = gY * s;
+      const float gn = -(gq0 * p.q0 + gq1 * p.q1 + gD * p.q3);
+      if (p.ok)
+        grad_m_add(acc, gq0, gq1, gn, gD, (float)x + 0.5f, (float)y + 0.5f, dv);
+    }
   } else {
     const float inv_n = 1.0f / p.nden;
     const float gq0 = gX * s * inv_n, gq1 = gY * s * inv_n, gq3 = gD * inv_n;
     const float gn = -(gq0 * p.q0 + gq1 * p.q1 + gq3 * p.q3) * inv_n;
     gd = gq0 * m[3] + gq1 * m[7] + gn * m[11] + gq3 * m[15];
+    if (GRAD_M && p.ok)
+      grad_m_add(acc, gq0, gq1, gn, gq3, (float)x + 0.5f, (float)y + 0.5f, dv);
   }
   if (!p.ok) gd = 0.0f;
   r.gd = gd;
@@ -482,11 +495,11 @@ constexpr int BWD_ROWS = 8;
 
 struct BwdIn { float dv, mk, t0, t1, t2; };
 
-template <bool SIMPLE_M>
+template <bool SIMPLE_M, bool GRAD_M>
 __device__ __forceinline__ void splat_bwd_rows(
     const SplatArgs& a, const float* __restrict__ m, int b, int l, int y0, int x,
     const float4* __restrict__ G, float* __restrict__ g_tex,
-    float* __restrict__ g_disp, float* __restrict__ g_mask) {
+    float* __restrict__ g_disp, float* __restrict__ g_mask, float (&acc)[16]) {
   const LsiSplatDesc& d = a.d;
   const bool has_mask = d.flags & LSI_HAS_MASK;
   const float* dbase = a.disp + l * d.disp_sl + b * d.disp_sb + x * d.disp_sx;
@@ -517,8 +530,8 @@ __device__ __forceinline__ void splat_bwd_rows(
     const int y = y0 + r;
     const BwdIn nxt = load(y + 1);
     if (y < d.H) {
-      const BwdPx g = splat_bwd_core<SIMPLE_M>(d, m, y, x, cur.dv, cur.mk, cur.t0,
-                                               cur.t1, cur.t2, Gb);
+      const BwdPx g = splat_bwd_core<SIMPLE_M, GRAD_M>(d, m, y, x, cur.dv, cur.mk,
+                                                       cur.t0, cur.t1, cur.t2, Gb, acc);
       const size_t o = obase + (size_t)y * d.W;
       // one 12-byte store per lane: a wave writes 768 contiguous bytes
       *reinterpret_cast<float3*>(g_tex + 3 * o) = make_float3(g.gt0, g.gt1, g.gt2);
@@ -529,10 +542,14 @@ __device__ __forceinline__ void splat_bwd_rows(
   }
 }
 
+// GRAD_M: every workgroup also writes its 16-float share of dL/dM to
+// gm_part[16 * (flat workgroup index)] (b-major: blockIdx.z = b * L + l), which
+// grad_m_fold_kernel sums per batch element.
+template <bool GRAD_M>
 __global__ __launch_bounds__(256) void splat_bwd_kernel(
     SplatArgs a, float inv_l, const float4* __restrict__ G,
     float* __restrict__ g_tex, float* __restrict__ g_disp,
-    float* __restrict__ g_mask) {
+    float* __restrict__ g_mask, float* __restrict__ gm_part) {
   const LsiSplatDesc& d = a.d;
   const int y0 = blockIdx.y * BWD_ROWS;
   // blockIdx.z = b * L + l: the layers of a batch element run back to back and
@@ -542,25 +559,61 @@ __global__ __launch_bounds__(256) void splat_bwd_kernel(
   if (l < 0) { --b; l += d.L; }
   if (l >= d.L) { ++b; l -= d.L; }
   const int x = blockIdx.x * 256 + threadIdx.x;
-  if (x >= d.W) return;
-  const float* __restrict__ m = a.M + 16 * b;
-  const bool simple_m = m[8] == 0.0f && m[9] == 0.0f && m[10] == 1.0f &&
-                        m[11] == 0.0f && m[12] == 0.0f && m[13] == 0.0f &&
-                        m[14] == 0.0f && m[15] == 1.0f;
-  if (simple_m)
-    splat_bwd_rows<true>(a, m, b, l, y0, x, G, g_tex, g_disp, g_mask);
-  else
-    splat_bwd_rows<false>(a, m, b, l, y0, x, G, g_tex, g_disp, g_mask);
+  // (GRAD_M: the lanes past the right edge stay for the workgroup's sum)
+  if (!GRAD_M && x >= d.W) return;
+  float acc[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
+  if (x < d.W) {
+    const float* __restrict__ m = a.M + 16 * b;
+    const bool simple_m = m[8] == 0.0f && m[9] == 0.0f && m[10] == 1.0f &&
+                          m[11] == 0.0f && m[12] == 0.0f && m[13] == 0.0f &&
+                          m[14] == 0.0f && m[15] == 1.0f;
+    if (simple_m)
+      splat_bwd_rows<true, GRAD_M>(a, m, b, l, y0, x, G, g_tex, g_disp, g_mask, acc);
+    else
+      splat_bwd_rows<false, GRAD_M>(a, m, b, l, y0, x, G, g_tex, g_disp, g_mask, acc);
+  }
+  if (GRAD_M) {
+    __shared__ float red[4 * 16];
+    const size_t wg = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x +
+                      blockIdx.x;
+    grad_m_block_sum<4>(acc, red, gm_part + 16 * wg);
+  }
 }
 
 static void launch_bwd(const SplatArgs& a, const float4* G, float* g_tex,
-                       float* g_disp, float* g_mask, hipStream_t stream) {
+                       float* g_disp, float* g_mask, float* gm_part,
+                       hipStream_t stream) {
   const LsiSplatDesc* d = &a.d;
-  hipLaunchKernelGGL(splat_bwd_kernel,
-                     dim3((d->W + 255) / 256, (d->H + BWD_ROWS - 1) / BWD_ROWS,
-                          d->L * d->B),
-                     dim3(256), 0, stream, a, 1.0f / (float)d->L, G, g_tex, g_disp,
-                     g_mask);
+  const dim3 grid((d->W + 255) / 256, (d->H + BWD_ROWS - 1) / BWD_ROWS, d->L * d->B);
+  if (gm_part)
+    hipLaunchKernelGGL(splat_bwd_kernel<true>, grid, dim3(256), 0, stream, a,
+                       1.0f / (float)d->L, G, g_tex, g_disp, g_mask, gm_part);
+  else
+    hipLaunchKernelGGL(splat_bwd_kernel<false>, grid, dim3(256), 0, stream, a,
+                       1.0f / (float)d->L, G, g_tex, g_disp, g_mask, nullptr);
+}
+
+// dL/dM of batch element blockIdx.x: the sum of its `nper` workgroup partials
+// (16 floats each, contiguous per batch element), in a fixed order -- no
+// atomics, the same bits from run to run.  Thread (j, e) sums entry e of the
+// partials j, j + 16, ...; then thread e sums the 16 in order.
+__global__ __launch_bounds__(256) void grad_m_fold_kernel(
+    const float* __restrict__ part, int nper, float* __restrict__ g_M) {
+  __shared__ float red[16 * 16];
+  const int e = threadIdx.x & 15, j = threadIdx.x >> 4;
+  const float* p = part + (size_t)blockIdx.x * nper * 16;
+  float v = 0.0f;
+  for (int n = j; n < nper; n += 16) v = v + p[(size_t)n * 16 + e];
+  red[j * 16 + e] = v;
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    float t = red[e];
+#pragma unroll
+    for (int k = 1; k < 16; ++k) t = t + red[k * 16 + e];
+    g_M[16 * blockIdx.x + e] = t;
+  }
 }
 
 // Pre-pass of lsi_splat_bwd_both: layer l's canvas receives the gradient of
@@ -818,23 +871,83 @@ int lsi_project_indices(const LsiSplatDesc* d, const float* disp,
   return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
 }
 
+}  // extern "C"
+
+namespace {
+
+// LSI_GRAD_M workspace: the gradient canvas, then (256-byte aligned) one
+// 16-float partial per workgroup of whichever backward kernel runs -- the
+// gather kernel's (W / 256) x (H / BWD_ROWS) x L x B or the streamed one's at
+// most H x L x B bands (a band is >= 1 source row).
+size_t grad_m_part_offset(const LsiSplatDesc* d) {
+  const int nl = (d->flags & LSI_COMPOSE) ? 1 : d->L;
+  const size_t canvas = (size_t)nl * d->B * d->Ht * d->Wt * sizeof(float4);
+  return (canvas + 255) & ~(size_t)255;
+}
+
+size_t grad_m_gather_parts(const LsiSplatDesc* d) {
+  return (size_t)((d->W + 255) / 256) * ((d->H + BWD_ROWS - 1) / BWD_ROWS) * d->L *
+         d->B;
+}
+
+size_t grad_m_part_count(const LsiSplatDesc* d) {
+  const size_t gather = grad_m_gather_parts(d);
+  const size_t stream = (size_t)d->H * d->L * d->B;
+  return gather > stream ? gather : stream;
+}
+
+int grad_m_fold(const LsiSplatDesc* d, const float* part, int nper, float* g_M,
+                hipStream_t stream) {
+  if (hipGetLastError() != hipSuccess) return LSI_ELAUNCH;
+  hipLaunchKernelGGL(grad_m_fold_kernel, dim3(d->B), dim3(256), 0, stream, part,
+                     nper, g_M);
+  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+}
+
+// The LSI_GRAD_M / g_M agreement of the _m entries (before any device call).
+int grad_m_args(const LsiSplatDesc* d, const float* g_M) {
+  if (d->flags & LSI_GRAD_M) return g_M ? LSI_OK : LSI_ENULL;
+  return g_M ? LSI_EINVAL : LSI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 size_t lsi_splat_bwd_workspace_bytes(const LsiSplatDesc* d) {
   if (check_desc(d) != LSI_OK) return 0;
   const int nl = (d->flags & LSI_COMPOSE) ? 1 : d->L;
+  if (d->flags & LSI_GRAD_M)
+    return grad_m_part_offset(d) + grad_m_part_count(d) * 16 * sizeof(float);
   return (size_t)nl * d->B * d->Ht * d->Wt * sizeof(float4);
 }
 
 int lsi_splat_bwd(const LsiSplatDesc* d, const float* tex, const float* disp,
-                     const float* mask, const float* M, const float* out_img,
-                     const float* out_wts, const float* g_img,
-                     const float* g_wts, float* g_tex, float* g_disp_in,
-                     float* g_mask, void* workspace, size_t workspace_bytes,
-                     lsi_stream_t stream_) {
+                  const float* mask, const float* M, const float* out_img,
+                  const float* out_wts, const float* g_img, const float* g_wts,
+                  float* g_tex, float* g_disp_in, float* g_mask, void* workspace,
+                  size_t workspace_bytes, lsi_stream_t stream_) {
+  if (d && (d->flags & LSI_GRAD_M)) return LSI_EINVAL;  // (lsi_splat_bwd_m)
+  return lsi_splat_bwd_m(d, tex, disp, mask, M, out_img, out_wts, g_img, g_wts,
+                         g_tex, g_disp_in, g_mask, nullptr, workspace,
+                         workspace_bytes, stream_);
+}
+
+int lsi_splat_bwd_m(const LsiSplatDesc* d, const float* tex, const float* disp,
+                    const float* mask, const float* M, const float* out_img,
+                    const float* out_wts, const float* g_img, const float* g_wts,
+                    float* g_tex, float* g_disp_in, float* g_mask, float* g_M,
+                    void* workspace, size_t workspace_bytes,
+                    lsi_stream_t stream_) {
   int rc = check_desc(d);
   if (rc != LSI_OK) return rc;
   if (!tex || !disp || !M || !out_img || !out_wts || !g_img || !g_tex ||
       !g_disp_in || !workspace)
     return LSI_ENULL;
+  rc = grad_m_args(d, g_M);
+  if (rc != LSI_OK) return rc;
+  float* const gm_part =
+      g_M ? (float*)((char*)workspace + grad_m_part_offset(d)) : nullptr;
   if ((d->flags & LSI_HAS_MASK) && !mask) return LSI_ENULL;
   if (!packed_ok(d, tex, disp)) return LSI_EINVAL;
   if (workspace_bytes < lsi_splat_bwd_workspace_bytes(d)) return LSI_EWORKSPACE;
@@ -843,8 +956,11 @@ int lsi_splat_bwd(const LsiSplatDesc* d, const float* tex, const float* disp,
   // stores, the band's gradient-canvas rows built in LDS; no pre-pass)
   if (lsi_bwd_stream_applies(d, tex, disp, mask, g_tex, g_disp_in, g_mask)) {
     const LsiBwdCanvas ci = {out_img, out_wts, g_img, g_wts};
-    return lsi_bwd_stream_launch(d, tex, disp, mask, M, &ci, nullptr, g_tex,
-                                 g_disp_in, g_mask, stream);
+    int nper = 0;
+    rc = lsi_bwd_stream_launch(d, tex, disp, mask, M, &ci, nullptr, g_tex,
+                               g_disp_in, g_mask, gm_part, &nper, stream);
+    if (rc != LSI_OK || !g_M) return rc;
+    return grad_m_fold(d, gm_part, nper, g_M, stream);
   }
   const int nl = (d->flags & LSI_COMPOSE) ? 1 : d->L;
   const size_t n = (size_t)nl * d->B * d->Ht * d->Wt;
@@ -860,7 +976,8 @@ int lsi_splat_bwd(const LsiSplatDesc* d, const float* tex, const float* disp,
   a.out_img_c = a.out_wts_c = nullptr;
   if ((long)d->B * d->L > 65535 || d->H > 65535) return LSI_EINVAL;  // grid.y / z
   launch_bwd(a, (const float4*)workspace, g_tex, g_disp_in,
-             (d->flags & LSI_HAS_MASK) ? g_mask : nullptr, stream);
+             (d->flags & LSI_HAS_MASK) ? g_mask : nullptr, gm_part, stream);
+  if (g_M) return grad_m_fold(d, gm_part, (int)(grad_m_gather_parts(d) / d->B), g_M, stream);
   return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
 }
 
@@ -907,10 +1024,30 @@ int lsi_splat_bwd_both(const LsiSplatDesc* d, const float* tex,
                        const float* g_img_c, const float* g_wts_c, float* g_tex,
                        float* g_disp_in, float* g_mask, void* workspace,
                        size_t workspace_bytes, lsi_stream_t stream_) {
+  if (d && (d->flags & LSI_GRAD_M)) return LSI_EINVAL;  // (lsi_splat_bwd_both_m)
+  return lsi_splat_bwd_both_m(d, tex, disp, mask, M, out_img, out_wts, out_img_c,
+                              out_wts_c, g_img, g_wts, g_img_c, g_wts_c, g_tex,
+                              g_disp_in, g_mask, nullptr, workspace,
+                              workspace_bytes, stream_);
+}
+
+int lsi_splat_bwd_both_m(const LsiSplatDesc* d, const float* tex,
+                         const float* disp, const float* mask, const float* M,
+                         const float* out_img, const float* out_wts,
+                         const float* out_img_c, const float* out_wts_c,
+                         const float* g_img, const float* g_wts,
+                         const float* g_img_c, const float* g_wts_c,
+                         float* g_tex, float* g_disp_in, float* g_mask,
+                         float* g_M, void* workspace, size_t workspace_bytes,
+                         lsi_stream_t stream_) {
   int rc = check_desc(d);
   if (rc != LSI_OK) return rc;
   if (d->flags & LSI_COMPOSE) return LSI_EINVAL;
   if (!tex || !disp || !M || !g_tex || !g_disp_in || !workspace) return LSI_ENULL;
+  rc = grad_m_args(d, g_M);
+  if (rc != LSI_OK) return rc;
+  float* const gm_part =
+      g_M ? (float*)((char*)workspace + grad_m_part_offset(d)) : nullptr;
   if (!packed_ok(d, tex, disp)) return LSI_EINVAL;
   if (g_img && (!out_img || !out_wts)) return LSI_ENULL;
   if (g_img_c && (!out_img_c || !out_wts_c)) return LSI_ENULL;
@@ -920,8 +1057,11 @@ int lsi_splat_bwd_both(const LsiSplatDesc* d, const float* tex,
   if (lsi_bwd_stream_applies(d, tex, disp, mask, g_tex, g_disp_in, g_mask)) {
     const LsiBwdCanvas ci = {out_img, out_wts, g_img, g_wts};
     const LsiBwdCanvas cc = {out_img_c, out_wts_c, g_img_c, g_wts_c};
-    return lsi_bwd_stream_launch(d, tex, disp, mask, M, &ci, &cc, g_tex, g_disp_in,
-                                 g_mask, stream);
+    int nper = 0;
+    rc = lsi_bwd_stream_launch(d, tex, disp, mask, M, &ci, &cc, g_tex, g_disp_in,
+                               g_mask, gm_part, &nper, stream);
+    if (rc != LSI_OK || !g_M) return rc;
+    return grad_m_fold(d, gm_part, nper, g_M, stream);
   }
   const size_t n1 = (size_t)d->B * d->Ht * d->Wt;
   hipLaunchKernelGGL(splat_bwd_pre_both_kernel,
@@ -937,7 +1077,8 @@ int lsi_splat_bwd_both(const LsiSplatDesc* d, const float* tex,
   a.out_img_c = a.out_wts_c = nullptr;
   if ((long)d->B * d->L > 65535 || d->H > 65535) return LSI_EINVAL;  // grid.y / z
   launch_bwd(a, (const float4*)workspace, g_tex, g_disp_in,
-             (d->flags & LSI_HAS_MASK) ? g_mask : nullptr, stream);
+             (d->flags & LSI_HAS_MASK) ? g_mask : nullptr, gm_part, stream);
+  if (g_M) return grad_m_fold(d, gm_part, (int)(grad_m_gather_parts(d) / d->B), g_M, stream);
   return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
 }
 

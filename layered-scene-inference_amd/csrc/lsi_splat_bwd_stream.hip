@@ -23,6 +23,11 @@
 //   while this one computes.  Items go round-robin over the waves.
 // * Row-uniform terms (the y axis of the footprint: cells, weights, border
 //   masks) are computed once per item from scalars.
+// * GRAD_M (LSI_GRAD_M): the gradient w.r.t. the whole 4 x 4 matrix as well,
+//   rows 2 and 3, M[1][0] and M[1][3] included (the precondition fixes their
+//   values, not their gradients): each lane adds its pixels' dL/dq (x) p to 16
+//   registers, and the workgroup writes their sum as one partial
+//   (grad_m_block_sum) -- BSArgs.gm_part[16 * (band + nbands * (layer + NZ b))].
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -82,6 +87,7 @@ struct BSArgs {
   int remap;    // see the kernel: the layers of a band as neighbours on one XCD
   int RS;       // source rows per band
   int GR;       // canvas rows the LDS tile holds (0: always gather from global)
+  float* gm_part;  // GRAD_M: the workgroups' dL/dM partials
 };
 
 struct BSIn { float4 d4, t0, t1, t2, mk; };
@@ -159,12 +165,13 @@ typedef const __attribute__((address_space(3))) bs_f4v bs_lds_f4;
 
 // The wave's items, two register sets of loads in flight.  IN_LDS: the band's
 // canvas rows glo .. are in the LDS tile `gt`; else gathered from Gb.
-template <bool IN_LDS, bool PACK, bool MASK>
+template <bool IN_LDS, bool PACK, bool MASK, bool GRAD_M>
 __device__ __forceinline__ void bs_run(const BSArgs& a, const float (&m)[8],
                                        BSIn (&set)[2], const float4* gt,
                                        size_t obi, size_t obc, int b,
                                        int l_lo, int NL, int ys, int nitem,
-                                       int glo, int wave, int lane) {
+                                       int glo, int wave, int lane,
+                                       float (&acc)[16]) {
   const int Wt = a.Wt, nseg = a.nseg;
   const int half = (Wt + 1) >> 1;
   const float s = a.s;
@@ -206,7 +213,8 @@ __device__ __forceinline__ void bs_run(const BSArgs& a, const float (&m)[8],
     const int y = ys + p.r, sg = p.sg, l = p.l;
     // ---- row-uniform: the y axis of the footprint ---------------------------
     const float py = (float)y + 0.5f;
-    const float Y = mrow(m, 1, 0.5f, py, 0.0f) * s - 0.5f;
+    const float q1 = mrow(m, 1, 0.5f, py, 0.0f);  // (M[1][0] = M[1][3] = 0)
+    const float Y = q1 * s - 0.5f;
     const Axis ay = splat_axis(Y, ymax);
     const bool yok = finite_f(Y);
     const int r0 = yok ? (int)ay.c0s : glo, r1 = yok ? (int)ay.c1s : glo;
@@ -284,6 +292,15 @@ __device__ __forceinline__ void bs_run(const BSArgs& a, const float (&m)[8],
       // (M[1][3] == 0: the row coordinate does not move with the disparity)
       const float gd = (gX * s) * m[3] + gD;
       od[i] = ok ? gd : 0.0f;
+      // (lanes past the end of the row hold copies of its last pixels)
+      if (GRAD_M && ok && sg * BS_SEG + 4 * lane < a.W) {
+        // n' = 1: dL/dq = (gX s, gY s, dL/dn', gD), dL/dn' = -(dL/dq . q)
+        const float gY = -ay.v0 * (k0 * ax.w0 + k1 * ax.w1) +
+                         ay.v1 * (k2 * ax.w0 + k3 * ax.w1);
+        const float gq0 = gX * s, gq1 = gY * s;
+        const float gn = -(gq0 * q0 + gq1 * q1 + gD * d);
+        grad_m_add(acc, gq0, gq1, gn, gD, px, py, d);
+      }
       // (the gathers of the next pixels stay behind this pixel's arithmetic:
       // 16 of them in flight at once cost more registers than they hide)
       if (((i + 1) & ((1 << LSI_BS_FENCE) - 1)) == 0 && i < 3) asm volatile("" ::: "memory");
@@ -321,7 +338,7 @@ __device__ __forceinline__ void bs_run(const BSArgs& a, const float (&m)[8],
   }
 }
 
-template <bool PACK, bool MASK>
+template <bool PACK, bool MASK, bool GRAD_M>
 __global__ __launch_bounds__(BS_T, LSI_BS_WPE) void splat_bwd_stream_kernel(BSArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float4* const gt = reinterpret_cast<float4*>(smem);  // [GR][Wt]
@@ -428,11 +445,23 @@ __global__ __launch_bounds__(BS_T, LSI_BS_WPE) void splat_bwd_stream_kernel(BSAr
     }
   }
   __syncthreads();
-  if (nitem <= 0) return;
-  if (in_lds)
-    bs_run<true, PACK, MASK>(a, m, set, gt, obi, obc, b, l_lo, NL, ys, nitem, glo, wave, lane);
-  else
-    bs_run<false, PACK, MASK>(a, m, set, gt, obi, obc, b, l_lo, NL, ys, nitem, glo, wave, lane);
+  float acc[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
+  if (!GRAD_M && nitem <= 0) return;
+  if (nitem > 0) {
+    if (in_lds)
+      bs_run<true, PACK, MASK, GRAD_M>(a, m, set, gt, obi, obc, b, l_lo, NL, ys, nitem,
+                                       glo, wave, lane, acc);
+    else
+      bs_run<false, PACK, MASK, GRAD_M>(a, m, set, gt, obi, obc, b, l_lo, NL, ys, nitem,
+                                        glo, wave, lane, acc);
+  }
+  if (GRAD_M) {
+    __shared__ float red[BS_NW * 16];
+    const size_t wg = ((size_t)b * gridDim.z + bz) * gridDim.x + bx;
+    grad_m_block_sum<BS_NW>(acc, red, a.gm_part + 16 * wg);
+  }
 }
 
 bool aligned16b(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -476,8 +505,9 @@ int lsi_bwd_stream_launch(const LsiSplatDesc* d, const float* tex,
                           const float* disp, const float* mask, const float* M,
                           const LsiBwdCanvas* ci, const LsiBwdCanvas* cc,
                           float* g_tex, float* g_disp, float* g_mask,
-                          hipStream_t stream) {
+                          float* gm_part, int* gm_nper, hipStream_t stream) {
   BSArgs a;
+  a.gm_part = gm_part;
   a.tex = tex; a.disp = disp; a.M = M; a.g_tex = g_tex; a.g_disp = g_disp;
   {
     // Plain stores: a lane's four 16-byte stores are a third of the 48 bytes it
@@ -528,10 +558,17 @@ int lsi_bwd_stream_launch(const LsiSplatDesc* d, const float* tex,
   a.GR = rows_for(rs);
   size_t lds = bytes_for(rs);
   if (lds > cap) { a.GR = 0; lds = 0; }
-  const void* fn = (d->flags & LSI_PACKED_RGBD)
-                       ? (const void*)splat_bwd_stream_kernel<true, false>
-                       : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true>
-                                   : (const void*)splat_bwd_stream_kernel<false, false>);
+  const void* fn;
+  if (gm_part)
+    fn = (d->flags & LSI_PACKED_RGBD)
+             ? (const void*)splat_bwd_stream_kernel<true, false, true>
+             : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, true>
+                         : (const void*)splat_bwd_stream_kernel<false, false, true>);
+  else
+    fn = (d->flags & LSI_PACKED_RGBD)
+             ? (const void*)splat_bwd_stream_kernel<true, false, false>
+             : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, false>
+                         : (const void*)splat_bwd_stream_kernel<false, false, false>);
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)(lds > 0 ? lds : 16)) != hipSuccess) {
     // a device that does not grant the LDS asked for: corners from the arrays
@@ -542,6 +579,7 @@ int lsi_bwd_stream_launch(const LsiSplatDesc* d, const float* tex,
       return LSI_ELAUNCH;
   }
   const dim3 grid((d->H + rs - 1) / rs, d->B, a.compose ? 1 : d->L);
+  if (gm_nper) *gm_nper = (int)(grid.x * grid.z);
   {
     static const char* rm = getenv("LSI_BWD_REMAP");
     const long nwg = (long)grid.x * grid.y * grid.z;

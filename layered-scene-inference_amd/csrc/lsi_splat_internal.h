@@ -59,11 +59,13 @@ bool lsi_bwd_stream_applies(const LsiSplatDesc* d, const float* tex,
                             const float* disp, const float* mask,
                             const float* g_tex, const float* g_disp,
                             const float* g_mask);
+// gm_part != NULL (LSI_GRAD_M): every workgroup also writes its 16-float share
+// of dL/dM there, `*gm_nper` of them per batch element (b-major).
 int lsi_bwd_stream_launch(const LsiSplatDesc* d, const float* tex,
                           const float* disp, const float* mask, const float* M,
                           const LsiBwdCanvas* ci, const LsiBwdCanvas* cc,
                           float* g_tex, float* g_disp, float* g_mask,
-                          hipStream_t stream);
+                          float* gm_part, int* gm_nper, hipStream_t stream);
 
 // LSI_PATH_TILE launcher and workspace need (lsi_splat_tile.hip).
 size_t lsi_tile_workspace_bytes(const LsiSplatDesc* d);

@@ -20,6 +20,7 @@ LSI_OK = 0
 LSI_COMPOSE, LSI_WANT_DISP, LSI_HAS_MASK, LSI_WS_KEEP = 1, 2, 4, 8
 LSI_DETERMINISTIC = 16
 LSI_PACKED_RGBD = 32
+LSI_GRAD_M = 64
 LSI_PATH_AUTO, LSI_PATH_ATOMIC, LSI_PATH_ROWBAND, LSI_PATH_STREAM = 0, 1, 2, 3
 LSI_PATH_TILE = 4
 PATH_NAMES = {1: 'atomic', 2: 'rowband', 3: 'stream', 4: 'tile'}
@@ -96,8 +97,10 @@ SIGNATURES = {
     'lsi_splat_fwd': (ctypes.c_int, [_DP] + [_VP] * 8 + [_SZ, _VP]),
     'lsi_splat_bwd_workspace_bytes': (_SZ, [_DP]),
     'lsi_splat_bwd': (ctypes.c_int, [_DP] + [_VP] * 12 + [_SZ, _VP]),
+    'lsi_splat_bwd_m': (ctypes.c_int, [_DP] + [_VP] * 13 + [_SZ, _VP]),
     'lsi_splat_fwd_both': (ctypes.c_int, [_DP] + [_VP] * 9 + [_SZ, _VP]),
     'lsi_splat_bwd_both': (ctypes.c_int, [_DP] + [_VP] * 16 + [_SZ, _VP]),
+    'lsi_splat_bwd_both_m': (ctypes.c_int, [_DP] + [_VP] * 17 + [_SZ, _VP]),
     'lsi_project_indices': (ctypes.c_int, [_DP] + [_VP] * 6),
     'lsi_splat_generic': (ctypes.c_int, [_I32] * 6 + [_VP] * 4),
     'lsi_splat_generic_bwd': (ctypes.c_int, [_I32] * 6 + [_VP] * 6),

@@ -115,7 +115,10 @@ def _device_matrices(src2trg_mat, mat_host, dev):
   directions of a stereo pair, an evaluation loop) then issues no copy at all;
   a pageable host-to-device copy would wait for the kernels queued before it
   and serialise the host with the GPU.  New content goes through pinned memory,
-  asynchronously."""
+  asynchronously.  A matrix autograd is to differentiate (grad mode on, it
+  requires grad) is moved by a differentiable op and never cached."""
+  if torch.is_grad_enabled() and src2trg_mat.requires_grad:
+    return src2trg_mat.to(dev, torch.float32)
   if src2trg_mat.is_cuda or dev.type != 'cuda':
     # (a CPU `dev`: the call is about to fail in require_device -- no CPU path)
     return src2trg_mat.detach().to(dev, torch.float32)
@@ -213,8 +216,17 @@ class _NoLock(object):
 _NOLOCK = _NoLock()
 
 
+def _grad_m_desc(desc):
+  """A copy of the forward's descriptor that asks the backward for dL/dM too
+  (LSI_GRAD_M: lsi_splat_bwd_m / lsi_splat_bwd_both_m)."""
+  d = _C.LsiSplatDesc.from_buffer_copy(desc)
+  d.flags |= _C.LSI_GRAD_M
+  return d
+
+
 class _ForwardSplat(torch.autograd.Function):
-  """lsi_splat_fwd / lsi_splat_bwd (include/lsi_hip.h)."""
+  """lsi_splat_fwd / lsi_splat_bwd (include/lsi_hip.h); lsi_splat_bwd_m when
+  the matrices need their gradient."""
 
   @staticmethod
   def forward(ctx, tex, mask, disp, mat, mat_host, cfg):
@@ -289,6 +301,18 @@ class _ForwardSplat(torch.autograd.Function):
     g_mask = (torch.empty((nl, b, h, w, 1), dtype=torch.float32, device=dev)
               if mask is not None else None)
     lib = _C.lib()
+    if ctx.needs_input_grad[3]:
+      desc = _grad_m_desc(desc)
+      g_m = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
+      ws_bytes = int(lib.lsi_splat_bwd_workspace_bytes(ctypes.byref(desc)))
+      ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+      rc = lib.lsi_splat_bwd_m(ctypes.byref(desc), _C.ptr(tex), _C.ptr(disp),
+                               _C.ptr(mask), _C.ptr(mat), _C.ptr(img), _C.ptr(wts),
+                               _C.ptr(g_img), _C.ptr(g_wts), _C.ptr(g_tex),
+                               _C.ptr(g_disp), _C.ptr(g_mask), _C.ptr(g_m),
+                               _C.ptr(ws), ws_bytes, _C.stream_ptr(dev))
+      _C.check(rc, 'lsi_splat_bwd_m')
+      return g_tex, g_mask, g_disp, g_m, None, None
     ws_bytes = int(lib.lsi_splat_bwd_workspace_bytes(ctypes.byref(desc)))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     rc = lib.lsi_splat_bwd(ctypes.byref(desc), _C.ptr(tex), _C.ptr(disp),
@@ -301,8 +325,9 @@ class _ForwardSplat(torch.autograd.Function):
 
 
 class _ForwardSplatBoth(torch.autograd.Function):
-  """lsi_splat_fwd_both / lsi_splat_bwd_both: the per-layer and the composed
-  rendering of one LDI from one sweep over its pixels."""
+  """lsi_splat_fwd_both / lsi_splat_bwd_both (_m when the matrices need their
+  gradient): the per-layer and the composed rendering of one LDI from one
+  sweep over its pixels."""
 
   @staticmethod
   def forward(ctx, tex, mask, disp, mat, mat_host, cfg):
@@ -372,6 +397,19 @@ class _ForwardSplatBoth(torch.autograd.Function):
     g_mask = (torch.empty((nl, b, h, w, 1), dtype=torch.float32, device=dev)
               if mask is not None else None)
     lib = _C.lib()
+    if ctx.needs_input_grad[3]:
+      desc = _grad_m_desc(desc)
+      g_m = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
+      ws_bytes = int(lib.lsi_splat_bwd_workspace_bytes(ctypes.byref(desc)))
+      ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+      rc = lib.lsi_splat_bwd_both_m(
+          ctypes.byref(desc), _C.ptr(tex), _C.ptr(disp), _C.ptr(mask),
+          _C.ptr(mat), _C.ptr(img), _C.ptr(wts), _C.ptr(img_c), _C.ptr(wts_c),
+          _C.ptr(g_img), _C.ptr(g_wts), _C.ptr(g_img_c), _C.ptr(g_wts_c),
+          _C.ptr(g_tex), _C.ptr(g_disp), _C.ptr(g_mask), _C.ptr(g_m), _C.ptr(ws),
+          ws_bytes, _C.stream_ptr(dev))
+      _C.check(rc, 'lsi_splat_bwd_both_m')
+      return g_tex, g_mask, g_disp, g_m, None, None
     ws_bytes = int(lib.lsi_splat_bwd_workspace_bytes(ctypes.byref(desc)))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     rc = lib.lsi_splat_bwd_both(
@@ -394,6 +432,7 @@ def forward_splat_both(ldi_src, src2trg_mat, trg_downsampling=1,
   (lsi_splat_fwd_both), and one gather pass in the backward.
 
   Returns (img [L,B,Ht,Wt,3], wts [L,...,1], img_c [1,B,Ht,Wt,3], wts_c).
+  A `src2trg_mat` that requires grad gets its gradient (lsi_splat_bwd_both_m).
   """
   tex, mask, disp = ldi_src
   if mat_host is None and path not in ('atomic', 'tile'):
@@ -422,6 +461,8 @@ def forward_splat_matrix(ldi_src, src2trg_mat, compose_layers=True,
   folded / noisy disparity fields, a tie or 0.5 % slower on smooth ones.
   `deterministic` (LSI_DETERMINISTIC) asks for bitwise run-to-run reproducible
   sums on the stream path (fixed merge order; a little slower).
+  A `src2trg_mat` that requires grad gets its gradient (lsi_splat_bwd_m:
+  reduced in the backward kernels, bitwise reproducible).
   """
   tex, mask, disp = ldi_src
   if mat_host is None and path not in ('atomic', 'tile'):
@@ -582,26 +623,53 @@ def forward_splat(ldi_src,
         disparities are one elementwise pass, and D + f = (q3 + f n) / n is
         folded into row 3 of the projection matrix (not index-critical: only
         the z-buffer weight and the disparity output see it).
+  Camera tensors and focal_disps that require grad get their gradients (as
+  TF autodiff gives the reference's): the matrix is then built by
+  differentiable torch ops (the same bits as the host fast path) and its
+  gradient comes from the backward kernels (lsi_splat_bwd_m).  Coordinates
+  that require grad take the generic route, differentiable throughout.
   Returns:
     trg_img nl x B x Ht x Wt x 3, trg_wts nl x B x Ht x Wt x 1 (un-normalised)
     [, trg_disp nl x B x Ht x Wt x 1]; nl = 1 if compose_layers else L.
   """
-  mat_host = projection.forward_projection_matrix(
-      _host_copy(k_s), _host_copy(k_t), _host_copy(rot), _host_copy(t))
-  if not _is_pixel_grid(pixel_coords_src, ldi_src[2]):
+  cams = (k_s, k_t, rot, t)
+  grad_on = torch.is_grad_enabled()
+  learnt = [x for x in cams if x.requires_grad] if grad_on else []
+  grad_cam = bool(learnt) or (grad_on and focal_disps is not None and
+                              focal_disps.requires_grad)
+  if grad_cam:
+    # differentiable, where the cameras are (the same bits as the host path);
+    # the host copy only chooses the kernels
+    cdev = learnt[0].device if learnt else k_s.device
+    mat = projection.forward_projection_matrix(
+        *[x.to(cdev, torch.float32) for x in cams])
+    mat_host = mat.detach().to('cpu', torch.float32)
+  else:
+    mat_host = projection.forward_projection_matrix(
+        _host_copy(k_s), _host_copy(k_t), _host_copy(rot), _host_copy(t))
+    mat = mat_host
+  if ((grad_on and pixel_coords_src is not None and pixel_coords_src.requires_grad)
+      or not _is_pixel_grid(pixel_coords_src, ldi_src[2])):
     return _forward_splat_coords(
-        ldi_src, pixel_coords_src, mat_host, focal_disps, compose_layers, compute_trg_disp,
+        ldi_src, pixel_coords_src, mat, focal_disps, compose_layers, compute_trg_disp,
         trg_downsampling, bg_layer_disp, max_disp, zbuf_scale)
   if focal_disps is not None:
     tex, masks, disps = ldi_src
-    f = focal_disps.detach().to(torch.float32).reshape(-1)
+    f = focal_disps.to(torch.float32).reshape(-1)
     if f.numel() != disps.shape[1]:
       raise ValueError('focal_disps: one value per batch element (B x 1 x 1 x 1)')
     ldi_src = [tex, masks, disps - f.to(disps.device).view(1, -1, 1, 1, 1)]
-    mat_host = mat_host.clone()
-    mat_host[:, 3, :] += f.to('cpu').view(-1, 1) * mat_host[:, 2, :]
+    if grad_cam:
+      fm = f.to(mat.device).view(-1, 1)
+      mat = torch.cat([mat[:, :3, :], (mat[:, 3, :] + fm * mat[:, 2, :])[:, None]],
+                      dim=1)
+      mat_host = mat.detach().to('cpu', torch.float32)
+    else:
+      mat_host = mat_host.clone()
+      mat_host[:, 3, :] += f.detach().to('cpu').view(-1, 1) * mat_host[:, 2, :]
+      mat = mat_host
   return forward_splat_matrix(
-      ldi_src, mat_host, compose_layers=compose_layers,
+      ldi_src, mat, compose_layers=compose_layers,
       compute_trg_disp=compute_trg_disp, trg_downsampling=trg_downsampling,
       bg_layer_disp=bg_layer_disp, max_disp=max_disp, zbuf_scale=zbuf_scale,
       mat_host=mat_host)

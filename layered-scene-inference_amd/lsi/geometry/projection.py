@@ -35,10 +35,14 @@ def _host_matrices(k_s, k_t, rot, t, inverse):
   """lsi_projection_matrices (csrc/lsi_host.hip): the whole batch in one call,
   for B x 3 x 3 / B x 3 x 1 fp32 cameras on the host -- the same values as the
   torch ops below, without a dozen small-tensor dispatches.  None when the
-  arguments are not of that form."""
+  arguments are not of that form, or when autograd is to differentiate the
+  result (grad mode on and a camera requires grad): the torch ops below give
+  the same bits and carry the gradient to the cameras."""
   args = (k_s, k_t, rot, t)
   if not all(isinstance(x, torch.Tensor) and x.device.type == 'cpu' and
              x.dtype == torch.float32 and x.dim() == 3 for x in args):
+    return None
+  if torch.is_grad_enabled() and any(x.requires_grad for x in args):
     return None
   b = k_s.shape[0]
   if (tuple(k_s.shape) != (b, 3, 3) or tuple(k_t.shape) != (b, 3, 3) or

@@ -1,7 +1,9 @@
 """Times lsi_splat_bwd and lsi_splat_fwd_both / lsi_splat_bwd_both on a bench
 workload (HIP events; microseconds per call).  LSI_BWD_STREAM=0 selects the
 one-thread-per-pixel gather kernel, LSI_HIP_LIB=<name> an experiment build.
-  python tools/time_bwd.py [--workload cfg3] [--shard-of N]"""
+--grad-m also times lsi_splat_bwd_m (the same call with the gradient w.r.t.
+the matrices, LSI_GRAD_M), interleaved with the plain call.
+  python tools/time_bwd.py [--workload cfg3] [--shard-of N] [--grad-m]"""
 import argparse, json, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,6 +19,7 @@ ap.add_argument('--tex-layout', default='nhwc')
 ap.add_argument('--path', default='auto')
 ap.add_argument('--band-rows', type=int, default=0)
 ap.add_argument('--threads', type=int, default=0)
+ap.add_argument('--grad-m', action='store_true')
 args = ap.parse_args()
 dev = torch.device('cuda', 0)
 torch.cuda.set_device(0)
@@ -25,7 +28,51 @@ r = bench.build_renderer(args.workload, b_local, 1000, dev, args)
 r.launch()
 torch.cuda.synchronize()
 nl, h, w = bench.WORKLOADS[args.workload][:3]
-bwd = min(bench.time_backward(r) for _ in range(3))
+
+
+def time_backward_m(r, iters=20):
+  """bench.time_backward with LSI_GRAD_M: lsi_splat_bwd_m (+ its fold kernel)."""
+  import ctypes
+  from lsi import _C
+  lib = _C.lib()
+  nl, b = r.tex.shape[:2]
+  d = _C.LsiSplatDesc.from_buffer_copy(r.desc)
+  d.flags |= _C.LSI_GRAD_M
+  g_img = torch.rand_like(r.img)
+  g_tex = torch.empty(r.tex.shape[:4] + (3,), device=dev)
+  g_disp = torch.empty(r.tex.shape[:4] + (1,), device=dev)
+  g_m = torch.empty((b, 4, 4), device=dev)
+  ws_bytes = int(lib.lsi_splat_bwd_workspace_bytes(ctypes.byref(d)))
+  ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+  turn = [0]
+
+  def launch():
+    tex, disp = r.sets[turn[0]]
+    turn[0] = (turn[0] + 1) % len(r.sets)
+    _C.check(lib.lsi_splat_bwd_m(ctypes.byref(d), _C.ptr(tex), _C.ptr(disp), None,
+                                 _C.ptr(r.mat), _C.ptr(r.img), _C.ptr(r.wts),
+                                 _C.ptr(g_img), None, _C.ptr(g_tex), _C.ptr(g_disp),
+                                 None, _C.ptr(g_m), _C.ptr(ws), ws_bytes,
+                                 _C.stream_ptr(dev)), 'lsi_splat_bwd_m')
+
+  for _ in range(3):
+    launch()
+  e0 = torch.cuda.Event(enable_timing=True)
+  e1 = torch.cuda.Event(enable_timing=True)
+  torch.cuda.synchronize()
+  e0.record()
+  for _ in range(iters):
+    launch()
+  e1.record()
+  torch.cuda.synchronize()
+  return e0.elapsed_time(e1) * 1e3 / iters
+
+
+if args.grad_m:  # interleaved: plain, with g_M, plain, ...
+  pairs = [(bench.time_backward(r), time_backward_m(r)) for _ in range(5)]
+  bwd, bwd_m = min(p[0] for p in pairs), min(p[1] for p in pairs)
+else:
+  bwd, bwd_m = min(bench.time_backward(r) for _ in range(3)), None
 both = [min(x) for x in zip(*[bench.time_both(r) for _ in range(3)])]
 
 def time_disp(path, indep=False):
@@ -75,5 +122,5 @@ print(json.dumps({'workload': args.workload, 'batch': b_local,
                   'lib': os.environ.get('LSI_HIP_LIB', ''),
                   'bwd_stream': os.environ.get('LSI_BWD_STREAM', '1'),
                   'rows': os.environ.get('LSI_BWD_STREAM_ROWS', ''),
-                  'bwd_us': bwd, 'fwd_both_us': both[0], 'bwd_both_us': both[1],
+                  'bwd_us': bwd, 'bwd_grad_m_us': bwd_m, 'fwd_both_us': both[0], 'bwd_both_us': both[1],
                   'bwd_frac': bench.backward_bytes(nl, b_local, h, w) / (bwd * 1e-6) / 1e9 / bench.HBM_PEAK_GBPS}))

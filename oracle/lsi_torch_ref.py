@@ -216,6 +216,18 @@ def view_synthesis_loss(recons_splat, to_recons_img, splat_bdry_ignore=0.05):
   return pw[:, y_min:ht - y_min, x_min:wt - x_min].mean()
 
 
+def view_synthesis_loss_even_ties(recons_splat, to_recons_img,
+                                  splat_bdry_ignore=0.05):
+  """view_synthesis_loss with TF's reduce_min gradient: torch.amin splits the
+  gradient evenly among tied layers, as TF does.  Same forward value."""
+  _, _, ht, wt, _ = recons_splat.shape
+  tgt = area_downsample(to_recons_img, ht, wt)
+  pw = torch.amin(torch.mean(torch.abs(tgt.unsqueeze(0) - recons_splat), dim=4),
+                  dim=0)
+  x_min, y_min = py2_round(wt * splat_bdry_ignore), py2_round(ht * splat_bdry_ignore)
+  return pw[:, y_min:ht - y_min, x_min:wt - x_min].mean()
+
+
 def soft_z_buffering(layer_masks, layer_disps, depth_softmax_temp=1):
   """helpers.py:140-160: p_l ~ (mask + 1e-8) * exp(-1 / (relu(d) * temp)),
   max-subtracted softmax over the layers."""

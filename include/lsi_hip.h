@@ -800,6 +800,54 @@ int lsi_conv2d_first_wgrad(const LsiConvDesc* d, const void* x, int32_t x_bf16, 
                            float* g_weight, int32_t weight_layout, void* workspace,
                            size_t workspace_bytes, lsi_stream_t stream);
 
+/*
+ * The same convolutions in EXACT fp32 (the reference network's own arithmetic,
+ * nets.py:29-114, 244-348: slim.conv2d k x k stride 1 | 2 TF `SAME`,
+ * slim.conv2d_transpose 4 x 4 stride 2, fp32 NHWC; TF autodiff for the
+ * gradients) on the matrix cores: v_mfma_f32_16x16x4_f32, whose result is a
+ * k-ordered chain of fp32 fmas -- no reduced-precision inputs.  Activations,
+ * gradients and packed weights are fp32 channels-last, 16-byte aligned
+ * (LSI_EUNSUPPORTED otherwise, before any launch).  The descriptor and the
+ * roles are those of the bf16 entries above (a transposed convolution is the
+ * data gradient of the descriptor's convolution).
+ * lsi_conv2d_f32_supported(d): 1 if d is taken -- Cin a multiple of 32, Cout of
+ *   16, KH, KW <= 7, stride 1 or 2, pad < kernel size; the data gradient (mode
+ *   1) also needs Cout a multiple of 32 (it is the kernel's input there).
+ * lsi_conv2d_f32_pack / _pack_job / _pack_many: as lsi_conv2d_pack / _pack_job
+ *   / _pack_many (mode 0 | 1, | 2 for a channels-last parameter), writing fp32
+ *   [tap][out ch][in ch] into lsi_conv2d_f32_packed_bytes(d) bytes; the jobs of
+ *   lsi_conv2d_f32_pack_job go to lsi_conv2d_f32_pack_many only.
+ * lsi_conv2d_f32_run(d, mode, io): lsi_conv2d_run in fp32 -- two input tensors
+ *   (mode 0), two gradient tensors (mode 1; c1 a multiple of the kernel's block
+ *   of output channels: 64 when Cin is a multiple of 64, else 32), the split over
+ *   the input channels with a workspace of lsi_conv2d_f32_workspace_bytes(d,
+ *   mode) bytes (0: no split), folded in a fixed order; io->bn_workspace must be
+ *   NULL (the batch-norm statistics stay with the two-pass kernels).  out is
+ *   written, fp32.
+ * lsi_conv2d_wgrad_f32: lsi_conv2d_wgrad_cat in fp32 (x1, x2, gy fp32;
+ *   g_weight written in weight_layout 0 | 2); K = output pixels on the matrix
+ *   cores, partial sums of the pixel blocks in the workspace
+ *   (lsi_conv2d_wgrad_f32_workspace_bytes(d): 0 for shapes it does not take --
+ *   the bottleneck layers whose partial sums would exceed 96 MB), folded in a
+ *   fixed order.  Every result is deterministic for a given geometry.
+ */
+int lsi_conv2d_f32_supported(const LsiConvDesc* d);
+size_t lsi_conv2d_f32_packed_bytes(const LsiConvDesc* d);
+int lsi_conv2d_f32_pack(const LsiConvDesc* d, int32_t mode, const float* weight, void* packed,
+                        size_t packed_bytes, lsi_stream_t stream);
+int lsi_conv2d_f32_pack_job(const LsiConvDesc* d, int32_t mode, const float* weight,
+                            void* packed, size_t packed_bytes, LsiPackJob* job,
+                            int32_t* nblocks);
+int lsi_conv2d_f32_pack_many(const LsiPackJob* jobs_device, int32_t njobs, int32_t total_blocks,
+                             lsi_stream_t stream);
+size_t lsi_conv2d_f32_workspace_bytes(const LsiConvDesc* d, int32_t mode);
+int lsi_conv2d_f32_run(const LsiConvDesc* d, int32_t mode, const LsiConvIO* io,
+                       lsi_stream_t stream);
+size_t lsi_conv2d_wgrad_f32_workspace_bytes(const LsiConvDesc* d);
+int lsi_conv2d_wgrad_f32(const LsiConvDesc* d, const void* x1, const void* x2, int32_t c1,
+                         const void* gy, float* g_weight, int32_t weight_layout,
+                         void* workspace, size_t workspace_bytes, lsi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

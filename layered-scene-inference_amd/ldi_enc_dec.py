@@ -94,6 +94,12 @@ def build_parser():
     '(BASELINE config 4: "bf16 convs + fp32 splat"); the renderer and the losses '
     'are fp32 either way.  false = the reference\'s own arithmetic (fp32 '
     'convolutions): through the library (MIOpen), DESIGN.md 4.8')
+  a('--fp32_convs', choices=('library', 'own'),
+    default='own' if os.environ.get('LSI_F32_CONV', '') == '1' else 'library',
+    help='with --bf16 false: the batch-normed convolutions on the library '
+    '(MIOpen) or on the exact-fp32 MFMA kernels of csrc/lsi_conv_f32.hip (forward, '
+    'data and weight gradients; DESIGN.md 4.7b).  Default: library (own when '
+    'LSI_F32_CONV=1)')
   a('--batched_pairs', type=_bool, default=True,
     help='source and target images go through the network in one pass, every '
     'batch norm with separate statistics per view (same arithmetic as two passes)')

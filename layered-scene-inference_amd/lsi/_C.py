@@ -150,6 +150,17 @@ SIGNATURES = {
     'lsi_conv2d_first_fwd': (ctypes.c_int, [_CP, _VP, _I32, _VP, _I32, _VP, _VP, _I32, _VP]),
     'lsi_conv2d_first_wgrad_workspace_bytes': (_SZ, [_CP]),
     'lsi_conv2d_first_wgrad': (ctypes.c_int, [_CP, _VP, _I32, _VP, _VP, _I32, _VP, _SZ, _VP]),
+    'lsi_conv2d_f32_supported': (ctypes.c_int, [_CP]),
+    'lsi_conv2d_f32_packed_bytes': (_SZ, [_CP]),
+    'lsi_conv2d_f32_pack': (ctypes.c_int, [_CP, _I32, _VP, _VP, _SZ, _VP]),
+    'lsi_conv2d_f32_pack_job': (ctypes.c_int, [_CP, _I32, _VP, _VP, _SZ,
+                                               ctypes.POINTER(LsiPackJob), _c_i]),
+    'lsi_conv2d_f32_pack_many': (ctypes.c_int, [_VP, _I32, _I32, _VP]),
+    'lsi_conv2d_f32_workspace_bytes': (_SZ, [_CP, _I32]),
+    'lsi_conv2d_f32_run': (ctypes.c_int, [_CP, _I32, ctypes.POINTER(LsiConvIO), _VP]),
+    'lsi_conv2d_wgrad_f32_workspace_bytes': (_SZ, [_CP]),
+    'lsi_conv2d_wgrad_f32': (ctypes.c_int, [_CP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _SZ,
+                                            _VP]),
     'lsi_bn_workspace_floats': (_SZ, [_I64, _I32, _I32, _I32]),
     'lsi_bn_relu_fwd': (ctypes.c_int, [_VP] * 5 + [_I64, _I32, _I32, _I32, _F32, _I32, _VP]),
     'lsi_bn_relu_bwd': (ctypes.c_int, [_VP] * 7 + [_I64, _I32, _I32, _I32, _I32, _VP]),

@@ -380,10 +380,12 @@ import weakref
 
 class _Pack(object):
   """One layer's weights in the kernel's operand order for one direction."""
-  __slots__ = ('wref', 'version', 'geo', 'buf', 'mode', 'desc', 'managed')
+  __slots__ = ('wref', 'version', 'geo', 'buf', 'mode', 'desc', 'managed', 'dtype')
 
 
-_PACKED = {}   # (id(weight), mode) -> _Pack
+# (id(weight), mode, dtype of the pack: torch.bfloat16 for the bf16 kernels,
+# torch.float32 for the fp32 ones) -> _Pack
+_PACKED = {}
 _PACK_TABLE = {}  # device index -> {key: (key, device table, njobs, blocks)}
 
 
@@ -437,8 +439,19 @@ def _after_optimizer_step(optimizer, args, kwargs):
     repack_all(_owned=owned)
 
 
-def _packed(desc, mode, weight, training=False):
-  """The layer's weights in the kernel's operand order (lsi_conv2d_pack).
+# the pack entries per pack dtype: (packed_bytes, pack, pack_job, pack_many)
+_PACK_FNS = {
+    torch.bfloat16: ('lsi_conv2d_packed_bytes', 'lsi_conv2d_pack', 'lsi_conv2d_pack_job',
+                     'lsi_conv2d_pack_many'),
+    torch.float32: ('lsi_conv2d_f32_packed_bytes', 'lsi_conv2d_f32_pack',
+                    'lsi_conv2d_f32_pack_job', 'lsi_conv2d_f32_pack_many'),
+}
+
+
+def _packed(desc, mode, weight, training=False, dtype=torch.bfloat16):
+  """The layer's weights in the kernel's operand order (lsi_conv2d_pack; with
+  dtype=torch.float32 lsi_conv2d_f32_pack: the fp32 kernels' pack, cached
+  apart from the bf16 one of the same parameter).
 
   Who keeps a pack fresh.  Frozen parameters: the version counter (load_state_dict,
   copy_, in-place ops move it).  Trainable parameters: torch's fused optimisers
@@ -457,7 +470,7 @@ def _packed(desc, mode, weight, training=False):
   What is left uncovered is a write through `.data` (no counter, no optimiser)
   to a parameter whose packs are managed; LSI_PACK_CHECK=N verifies every Nth
   trusted pack against a fresh one and raises."""
-  key = (id(weight), mode)
+  key = (id(weight), mode, dtype)
   hit = _PACKED.get(key)
   # (`training`: a forward call -- not the backward of one, which takes what the
   # forward left -- with a parameter somebody may be updating)
@@ -465,7 +478,7 @@ def _packed(desc, mode, weight, training=False):
   if training:
     _install_optimizer_hook()
   if training and not (hit is not None and hit.managed):
-    _PACKED.pop((id(weight), 1 - mode), None)   # (this step's backward packs afresh)
+    _PACKED.pop((id(weight), 1 - mode, dtype), None)   # (this step's backward packs afresh)
     hit_ok = False
   else:
     hit_ok = True
@@ -479,21 +492,24 @@ def _packed(desc, mode, weight, training=False):
       return hit.buf
   lib = _C.lib()
   dev = weight.device
-  nbytes = lib.lsi_conv2d_packed_bytes(ctypes.byref(desc))
+  fns = _PACK_FNS[dtype]
+  esz = 2 if dtype == torch.bfloat16 else 4
+  nbytes = getattr(lib, fns[0])(ctypes.byref(desc))
   if (hit is not None and hit.wref() is weight and hit.buf.device == dev and
-      hit.buf.numel() * 2 == nbytes and hit.geo == geo):
+      hit.buf.numel() * esz == nbytes and hit.geo == geo):
     buf = hit.buf          # (same place: a captured graph or a job table keeps its address)
   else:
-    buf = torch.empty((nbytes // 2,), dtype=torch.bfloat16, device=dev)
+    buf = torch.empty((nbytes // esz,), dtype=dtype, device=dev)
   src, cl = _pack_source(weight)
-  rc = lib.lsi_conv2d_pack(ctypes.byref(desc), mode | cl, _C.ptr(src), _C.ptr(buf),
-                           nbytes, _C.stream_ptr(dev))
-  _C.check(rc, 'lsi_conv2d_pack')
+  rc = getattr(lib, fns[1])(ctypes.byref(desc), mode | cl, _C.ptr(src), _C.ptr(buf),
+                            nbytes, _C.stream_ptr(dev))
+  _C.check(rc, fns[1])
   e = _Pack()
   e.wref = weakref.ref(weight, lambda _r, k=key: _PACKED.pop(k, None))
   e.version = weight._version
   e.geo = geo
   e.buf, e.mode, e.desc = buf, mode, desc
+  e.dtype = dtype
   e.managed = False
   _PACKED[key] = e
   return buf
@@ -503,9 +519,10 @@ def _verify_pack(e, weight):
   """LSI_PACK_CHECK: the trusted pack against a fresh one (synchronises)."""
   src, cl = _pack_source(weight)
   fresh = torch.empty_like(e.buf)
-  rc = _C.lib().lsi_conv2d_pack(ctypes.byref(e.desc), e.mode | cl, _C.ptr(src), _C.ptr(fresh),
-                                fresh.numel() * 2, _C.stream_ptr(weight.device))
-  _C.check(rc, 'lsi_conv2d_pack')
+  pack = _PACK_FNS[e.dtype][1]
+  rc = getattr(_C.lib(), pack)(ctypes.byref(e.desc), e.mode | cl, _C.ptr(src), _C.ptr(fresh),
+                               fresh.numel() * fresh.element_size(), _C.stream_ptr(weight.device))
+  _C.check(rc, pack)
   if not torch.equal(fresh, e.buf):
     raise RuntimeError('stale packed weights: a %s parameter was updated behind the '
                        'optimiser hook and the version counter (a write through .data?); '
@@ -514,7 +531,8 @@ def _verify_pack(e, weight):
 
 
 def repack_all(device=None, _owned=None):
-  """Re-packs, with ONE launch per device (lsi_conv2d_pack_many), the weights of
+  """Re-packs, with ONE launch per device and pack dtype (lsi_conv2d_pack_many,
+  lsi_conv2d_f32_pack_many for the fp32 kernels' packs), the weights of
   every layer the implicit-GEMM kernels have run so far.  The global optimiser
   hook calls it after every optimiser step (`_owned`: the ids of the stepping
   optimiser's parameters -- only their packs are refreshed and, from then on,
@@ -543,23 +561,24 @@ def repack_all(device=None, _owned=None):
       continue
     if not w.requires_grad and e.version == w._version:
       continue   # (a frozen parameter that has not moved)
-    by_dev.setdefault(w.device.index, []).append((e, w))
+    by_dev.setdefault((w.device.index, e.dtype), []).append((e, w))
   n = 0
-  for idx, items in by_dev.items():
+  for (idx, dtype), items in by_dev.items():
+    fns = _PACK_FNS[dtype]
     key = tuple((w.data_ptr(), e.buf.data_ptr(), e.mode) for e, w in items)
     # (every table ever built stays alive under its key: a captured graph has
     # its device address baked in)
-    tabs = _PACK_TABLE.setdefault(idx, {})
+    tabs = _PACK_TABLE.setdefault(idx if dtype == torch.bfloat16 else (idx, dtype), {})
     tab = tabs.get(key)
     if tab is None:
       jobs = (_C.LsiPackJob * len(items))()
       nb = ctypes.c_int32(0)
       blocks = 0
       for j, (e, w) in enumerate(items):
-        rc = lib.lsi_conv2d_pack_job(ctypes.byref(e.desc), e.mode | _pack_layout(w), w.data_ptr(),
-                                     e.buf.data_ptr(), e.buf.numel() * 2,
-                                     ctypes.byref(jobs[j]), ctypes.byref(nb))
-        _C.check(rc, 'lsi_conv2d_pack_job')
+        rc = getattr(lib, fns[2])(ctypes.byref(e.desc), e.mode | _pack_layout(w), w.data_ptr(),
+                                  e.buf.data_ptr(), e.buf.numel() * e.buf.element_size(),
+                                  ctypes.byref(jobs[j]), ctypes.byref(nb))
+        _C.check(rc, fns[2])
         jobs[j].block0 = blocks
         blocks += nb.value
       host = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8)
@@ -567,8 +586,8 @@ def repack_all(device=None, _owned=None):
       tabs[key] = tab
     dev = items[0][1].device
     with torch.cuda.device(dev):
-      rc = lib.lsi_conv2d_pack_many(tab[1].data_ptr(), tab[2], tab[3], _C.stream_ptr(dev))
-    _C.check(rc, 'lsi_conv2d_pack_many')
+      rc = getattr(lib, fns[3])(tab[1].data_ptr(), tab[2], tab[3], _C.stream_ptr(dev))
+    _C.check(rc, fns[3])
     for e, w in items:
       e.version = w._version
       if _owned is not None:
@@ -955,3 +974,273 @@ class _Conv2dFirst(torch.autograd.Function):
 
 def conv2d_first(x, weight, stride, pad_t, pad_l, oh, ow, bn_groups=0):
   return _Conv2dFirst.apply(x, weight, stride, pad_t, pad_l, oh, ow, bn_groups)
+
+
+# ---- exact fp32 convolutions (csrc/lsi_conv_f32.hip) --------------------------------
+# The fp32 counterparts of _Conv2dIgemm, _Conv2dCatIgemm and _ConvTranspose2dIgemm on
+# fp32 channels-last activations (the reference's own arithmetic: --bf16 false),
+# opted into with nets.F32_CONV (LSI_F32_CONV=1, the trainer's --fp32_convs own).
+# Forward, data gradient and weight gradient on the matrix cores
+# (v_mfma_f32_16x16x4_f32: exact fp32, deterministic folds); the batch norm behind
+# them stays on the two-pass kernels (no statistics in the epilogue).  The weight
+# gradients the kernel does not take (partial sums over the workspace cap: the
+# bottleneck layers) go to aten.
+_F32_OK = {}
+_F32_WGRAD_BYTES = {}
+_F32_RUN_BYTES = {}
+USED_F32 = [0]   # kernel launches of this route (tests check that it ran)
+
+
+def _cl_f32(t):
+  return (t.is_cuda and t.dim() == 4 and t.dtype == torch.float32 and
+          t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0)
+
+
+def _f32_desc_supported(n, h, w, cin, oh, ow, cout, k, stride, pad):
+  """lsi_conv2d_f32_supported for the geometry, cached; the forward's AND the data
+  gradient's channel rules (the data gradient takes Cout as its input)."""
+  key = (n, h, w, cin, oh, ow, cout, k, stride, pad)
+  ok = _F32_OK.get(key)
+  if ok is None:
+    d = _conv_desc(n, h, w, cin, oh, ow, cout, k, k, stride, pad, pad)
+    ok = _F32_OK[key] = bool(_C.lib().lsi_conv2d_f32_supported(ctypes.byref(d))) and \
+        cout % 32 == 0
+  return ok
+
+
+def f32_supported(x, cin, cout, k, stride):
+  """fp32 channels-last 16-byte aligned GPU activations, channel counts that are
+  multiples of 32, kernels up to 7 x 7, stride 1 or 2 (lsi_conv2d_f32_supported)."""
+  if not (_cl_f32(x) and x.shape[1] == cin and 1 <= k <= 7 and stride in (1, 2)):
+    return False
+  n, _, h, w = x.shape
+  oh, ow = -(-h // stride), -(-w // stride)
+  pad = max((oh - 1) * stride + k - h, 0) // 2
+  return _f32_desc_supported(n, h, w, cin, oh, ow, cout, k, stride, pad)
+
+
+def f32_cat_supported(x1, x2, cout, k, stride):
+  """A convolution over tf.concat([x1, x2], axis=3) on the fp32 kernels, read from
+  the two tensors: both fp32 channels-last with the same N, H, W; x1's channels a
+  multiple of the data-gradient kernel's block (64 when the sum is a multiple of
+  64, else 32)."""
+  if not (_cl_f32(x1) and _cl_f32(x2)):
+    return False
+  if x1.shape[0] != x2.shape[0] or x1.shape[2:] != x2.shape[2:]:
+    return False
+  c1, c2 = x1.shape[1], x2.shape[1]
+  blk = 64 if (c1 + c2) % 64 == 0 else 32
+  if not (c1 % 32 == 0 and c2 % 32 == 0 and c1 % blk == 0 and 1 <= k <= 7 and
+          stride in (1, 2)):
+    return False
+  n, _, h, w = x1.shape
+  oh, ow = -(-h // stride), -(-w // stride)
+  pad = max((oh - 1) * stride + k - h, 0) // 2
+  return _f32_desc_supported(n, h, w, c1 + c2, oh, ow, cout, k, stride, pad)
+
+
+def f32_convt_supported(x, cin, cout, k, stride):
+  """A transposed convolution (k x k, stride 2, padding 1) on the fp32 kernels."""
+  if not (_cl_f32(x) and x.shape[1] == cin and k <= 7 and stride == 2):
+    return False
+  n, _, h, w = x.shape
+  return _f32_desc_supported(n, stride * h, stride * w, cout, h, w, cin, k, stride, 1)
+
+
+def f32_wgrad_bytes(d):
+  """lsi_conv2d_wgrad_f32_workspace_bytes per geometry (0: the library takes it)."""
+  key = (d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout, d.KH, d.KW, d.stride, d.pad_t, d.pad_l)
+  n = _F32_WGRAD_BYTES.get(key)
+  if n is None:
+    n = _F32_WGRAD_BYTES[key] = int(_C.lib().lsi_conv2d_wgrad_f32_workspace_bytes(ctypes.byref(d)))
+  return n
+
+
+def _cl_f32_copy(t):
+  """t as an fp32 channels-last 16-byte aligned tensor (a copy only if needed)."""
+  t = t.float().contiguous(memory_format=torch.channels_last)
+  if t.data_ptr() % 16:
+    t = t.clone(memory_format=torch.channels_last)
+  return t
+
+
+def _empty_cl_f32(n, c, h, w, dev):
+  return torch.empty((n, c, h, w), dtype=torch.float32, device=dev,
+                     memory_format=torch.channels_last)
+
+
+def _run_f32(desc, mode, weight, dev, x, out, x2=None, out2=None, c1=0, training=False):
+  """lsi_conv2d_f32_run: forward (mode 0) / data gradient (mode 1) with the
+  fp32 pack of `weight`, the split over the input channels where the library
+  asks for a workspace."""
+  if training:
+    _FWD_SEQ[0] += 1
+  packed = _packed(desc, mode, weight, training, torch.float32)
+  io = _C.LsiConvIO()
+  io.x, io.packed, io.out = x.data_ptr(), packed.data_ptr(), out.data_ptr()
+  io.x2 = x2.data_ptr() if x2 is not None else None
+  io.out2 = out2.data_ptr() if out2 is not None else None
+  io.c1 = int(c1)
+  key = (mode, desc.N, desc.H, desc.W, desc.Cin, desc.OH, desc.OW, desc.Cout, desc.KH,
+         desc.KW, desc.stride, desc.pad_t, desc.pad_l)
+  nb = _F32_RUN_BYTES.get(key)
+  if nb is None:
+    nb = _F32_RUN_BYTES[key] = int(_C.lib().lsi_conv2d_f32_workspace_bytes(ctypes.byref(desc), mode))
+  if nb and SPLITK:
+    ws = _wgrad_workspace(dev, nb)
+    io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+  rc = _C.lib().lsi_conv2d_f32_run(ctypes.byref(desc), mode, ctypes.byref(io), _C.stream_ptr(dev))
+  if rc:
+    _C.check(rc, 'lsi_conv2d_f32_run(mode %d)' % mode)
+  USED_F32[0] += 1
+  return out
+
+
+def _f32_wgrad(d, x, gy, weight, x2=None):
+  """lsi_conv2d_wgrad_f32: x (and x2) = the descriptor's input, gy its output
+  gradient; the gradient in the parameter's own memory layout."""
+  dev = x.device
+  ws = _wgrad_workspace(dev, f32_wgrad_bytes(d))
+  cl = 2 if (weight.dim() == 4 and not weight.is_contiguous() and
+             weight.is_contiguous(memory_format=torch.channels_last)) else 0
+  gw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=dev,
+                   memory_format=torch.channels_last if cl else torch.contiguous_format)
+  rc = _C.lib().lsi_conv2d_wgrad_f32(
+      ctypes.byref(d), x.data_ptr(), x2.data_ptr() if x2 is not None else 0,
+      x.shape[1] if x2 is not None else 0, gy.data_ptr(), gw.data_ptr(), cl, ws.data_ptr(),
+      ws.numel() * 4, _C.stream_ptr(dev))
+  if rc:
+    _C.check(rc, 'lsi_conv2d_wgrad_f32')
+  USED_F32[0] += 1
+  return gw if weight.dtype == torch.float32 else gw.to(weight.dtype)
+
+
+def _aten_wgrad(d, x, g, weight, transposed=False):
+  """dL/dW on aten (MIOpen): explicit padding where TF SAME is asymmetric."""
+  if transposed:
+    return torch.ops.aten.convolution_backward(
+        g, x, weight.to(g.dtype), None, [d.stride, d.stride], [d.pad_t, d.pad_l], [1, 1], True,
+        [0, 0], 1, [False, True, False])[1].to(weight.dtype)
+  pb = max((d.OH - 1) * d.stride + d.KH - d.H - d.pad_t, 0)
+  pr = max((d.OW - 1) * d.stride + d.KW - d.W - d.pad_l, 0)
+  if pb == d.pad_t and pr == d.pad_l:
+    xp, pad = x, [d.pad_t, d.pad_l]
+  else:
+    xp, pad = torch.nn.functional.pad(x, (d.pad_l, pr, d.pad_t, pb)), [0, 0]
+  return torch.ops.aten.convolution_backward(
+      g, xp, weight.to(g.dtype), None, [d.stride, d.stride], pad, [1, 1], False,
+      [0, 0], 1, [False, True, False])[1].to(weight.dtype)
+
+
+class _Conv2dF32(torch.autograd.Function):
+  """slim.conv2d without bias in exact fp32: forward and data gradient on
+  lsi_conv2d_f32_run, the weight gradient on lsi_conv2d_wgrad_f32 (aten where
+  its workspace bytes are 0)."""
+
+  @staticmethod
+  def forward(ctx, x, weight, stride, pad_t, pad_l, oh, ow):
+    n, cin, h, w = x.shape
+    cout, _, kh, kw = weight.shape
+    desc = _conv_desc(n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l)
+    ctx.desc = desc
+    ctx.save_for_backward(x, weight)
+    return _run_f32(desc, 0, weight, x.device, x, _empty_cl_f32(n, cout, oh, ow, x.device),
+                    training=True)
+
+  @staticmethod
+  def backward(ctx, g):
+    x, weight = ctx.saved_tensors
+    d = ctx.desc
+    g = _cl_f32_copy(g)
+    gx = gw = None
+    if ctx.needs_input_grad[1]:   # (first: it may go to the side stream)
+      def wgrad():
+        if f32_wgrad_bytes(d) > 0:
+          return _f32_wgrad(d, x, g, weight)
+        return _aten_wgrad(d, x, g, weight)
+      gw = _wgrad_async(weight, wgrad, x, g)
+    if ctx.needs_input_grad[0]:
+      gx = _run_f32(d, 1, weight, x.device, g, _empty_cl_f32(d.N, d.Cin, d.H, d.W, x.device))
+    return gx, gw, None, None, None, None, None
+
+
+def conv2d_f32(x, weight, stride, pad_t, pad_l, oh, ow):
+  return _Conv2dF32.apply(x, weight, stride, pad_t, pad_l, oh, ow)
+
+
+class _Conv2dCatF32(torch.autograd.Function):
+  """slim.conv2d over a skip connection's concatenation in exact fp32, without
+  the concatenated tensor (forward, data gradient into two tensors, weight
+  gradient)."""
+
+  @staticmethod
+  def forward(ctx, x1, x2, weight, stride, pad_t, pad_l, oh, ow):
+    n, c1, h, w = x1.shape
+    cout, cin, kh, kw = weight.shape
+    assert cin == c1 + x2.shape[1]
+    desc = _conv_desc(n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l)
+    ctx.desc = desc
+    ctx.save_for_backward(x1, x2, weight)
+    return _run_f32(desc, 0, weight, x1.device, x1, _empty_cl_f32(n, cout, oh, ow, x1.device),
+                    x2=x2, c1=c1, training=True)
+
+  @staticmethod
+  def backward(ctx, g):
+    x1, x2, weight = ctx.saved_tensors
+    d = ctx.desc
+    dev = x1.device
+    c1 = x1.shape[1]
+    g = _cl_f32_copy(g)
+    gx1 = gx2 = gw = None
+    if ctx.needs_input_grad[2]:
+      def wgrad():
+        if f32_wgrad_bytes(d) > 0:
+          return _f32_wgrad(d, x1, g, weight, x2)
+        return _aten_wgrad(d, torch.cat([x1, x2], 1), g, weight)
+      gw = _wgrad_async(weight, wgrad, x1, x2, g)
+    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+      gx1 = _empty_cl_f32(d.N, c1, d.H, d.W, dev)
+      gx2 = _empty_cl_f32(d.N, d.Cin - c1, d.H, d.W, dev)
+      _run_f32(d, 1, weight, dev, g, gx1, out2=gx2, c1=c1)
+    return gx1, gx2, gw, None, None, None, None, None
+
+
+def conv2d_cat_f32(x1, x2, weight, stride, pad_t, pad_l, oh, ow):
+  return _Conv2dCatF32.apply(x1, x2, weight, stride, pad_t, pad_l, oh, ow)
+
+
+class _ConvTranspose2dF32(torch.autograd.Function):
+  """slim.conv2d_transpose 4 x 4 stride 2 in exact fp32: the data gradient of the
+  forward convolution {2h x 2w x Cout_T -> h x w x Cin_T} (four parity classes);
+  its own data gradient is that forward convolution; its weight gradient that
+  convolution's with the roles of the tensors swapped."""
+
+  @staticmethod
+  def forward(ctx, x, weight, stride, pad):
+    n, cin_t, h, w = x.shape
+    _, cout_t, kh, kw = weight.shape
+    desc = _conv_desc(n, stride * h, stride * w, cout_t, h, w, cin_t, kh, kw, stride, pad, pad)
+    ctx.desc = desc
+    ctx.save_for_backward(x, weight)
+    return _run_f32(desc, 1, weight, x.device, x,
+                    _empty_cl_f32(n, cout_t, stride * h, stride * w, x.device), training=True)
+
+  @staticmethod
+  def backward(ctx, g):
+    x, weight = ctx.saved_tensors
+    d = ctx.desc
+    g = _cl_f32_copy(g)
+    gx = gw = None
+    if ctx.needs_input_grad[1]:
+      def wgrad():
+        if f32_wgrad_bytes(d) > 0:
+          return _f32_wgrad(d, g, x, weight)
+        return _aten_wgrad(d, x, g, weight, transposed=True)
+      gw = _wgrad_async(weight, wgrad, x, g)
+    if ctx.needs_input_grad[0]:
+      gx = _run_f32(d, 0, weight, x.device, g, _empty_cl_f32(d.N, d.Cout, d.OH, d.OW, x.device))
+    return gx, gw, None, None
+
+
+def conv_transpose2d_f32(x, weight, stride=2, pad=1):
+  return _ConvTranspose2dF32.apply(x, weight, stride, pad)

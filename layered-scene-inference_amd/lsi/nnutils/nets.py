@@ -4,7 +4,9 @@ activations (the trainer's default: --bf16 / --channels_last) every convolution
 runs on this repo's own MFMA kernels (csrc/lsi_conv*.hip: first layer, implicit
 GEMM, the heads' 32-channel layers, all weight gradients) and every batch norm
 on csrc/lsi_bn.hip; fp32 activations (--bf16 false: the reference's own
-arithmetic) go through the library (MIOpen) -- DESIGN.md 4.8 says why.
+arithmetic) go through the library (MIOpen) -- DESIGN.md 4.8 says why -- unless
+F32_CONV (LSI_F32_CONV=1, --fp32_convs own) sends the batch-normed
+convolutions to the exact-fp32 MFMA kernels (csrc/lsi_conv_f32.hip).
 
 Conventions kept from the reference (tf.contrib.slim, nets.py:29-348):
   * tensors at the module boundary are B x H x W x C (channels-last logical
@@ -61,6 +63,21 @@ BF16_BATCH_NORM = os.environ.get('LSI_BF16_BN', '1') != '0'
 # the own kernel.
 IGEMM_CONV = os.environ.get('LSI_IGEMM_CONV', '1') != '0'
 IGEMM_MIN_PIXELS = int(os.environ.get('LSI_IGEMM_MIN_PIXELS', '0'))
+# fp32 activations outside bf16 autocast (--bf16 false) on the exact-fp32 MFMA
+# kernels (csrc/lsi_conv_f32.hip): every batch-normed convolution with channel
+# counts that are multiples of 32, its data and weight gradients; `cnv1`, the
+# `pred_l` heads and the weight gradients whose partial sums exceed the kernel's
+# workspace cap stay on the library.  Off by default (LSI_F32_CONV=1 or the
+# trainer's --fp32_convs own switch it on).
+F32_CONV = os.environ.get('LSI_F32_CONV', '') == '1'
+
+
+def _f32_route(x):
+  """fp32 GPU activations the fp32 kernels may take (not under bf16 autocast,
+  which would round them for the library's convolution)."""
+  return (F32_CONV and x.is_cuda and x.dtype == torch.float32 and
+          not (torch.is_autocast_enabled('cuda') and
+               torch.get_autocast_dtype('cuda') != torch.float32))
 
 
 def _igemm_pays(x, stride):
@@ -264,6 +281,15 @@ class SlimConv2d(nn.Module):
         # matrix-core kernel (K = pixels)
         x = _hip_conv.conv3x3_lib_own_wgrad(x, self.conv.weight)
         return self._bn_act(x)
+    if self.bn is not None and _f32_route(x):
+      from lsi.nnutils import _hip_conv  # pylint: disable=g-import-not-at-top
+      cout, cin = self.conv.weight.shape[:2]
+      if _hip_conv.f32_supported(x, cin, cout, self.k, self.stride):
+        ph = _same_pad(x.shape[2], self.k, self.stride)
+        pw = _same_pad(x.shape[3], self.k, self.stride)
+        x = _hip_conv.conv2d_f32(x, self.conv.weight, self.stride, ph[0], pw[0],
+                                 -(-x.shape[2] // self.stride), -(-x.shape[3] // self.stride))
+        return self._bn_act(x)
     ph = _same_pad(x.shape[2], self.k, self.stride)
     pw = _same_pad(x.shape[3], self.k, self.stride)
     # Symmetric SAME padding (the stride-1 layers) goes into the convolution:
@@ -304,6 +330,21 @@ class SlimConv2d(nn.Module):
         if st:
           return _bn_relu(self.bn, y, True)
         return self._bn_act(y)
+    if self.bn is not None and _f32_route(x1) and x2.dtype == torch.float32:
+      from lsi.nnutils import _hip_conv  # pylint: disable=g-import-not-at-top
+      cout = self.conv.weight.shape[0]
+      ph = _same_pad(x1.shape[2], self.k, self.stride)
+      pw = _same_pad(x1.shape[3], self.k, self.stride)
+      oh, ow = -(-x1.shape[2] // self.stride), -(-x1.shape[3] // self.stride)
+      # (the two tensors where the weight gradient runs on the kernel too; the
+      # concatenation otherwise: its weight gradient goes to the library)
+      if (_hip_conv.f32_cat_supported(x1, x2, cout, self.k, self.stride) and
+          _hip_conv.f32_wgrad_bytes(_hip_conv._conv_desc(
+              x1.shape[0], x1.shape[2], x1.shape[3], x1.shape[1] + x2.shape[1], oh, ow,
+              cout, self.k, self.k, self.stride, ph[0], pw[0])) > 0):
+        y = _hip_conv.conv2d_cat_f32(x1, x2, self.conv.weight, self.stride, ph[0], pw[0],
+                                     oh, ow)
+        return self._bn_act(y)
     return self.forward(torch.cat([x1, x2], dim=1))
 
   def _bn_act(self, x):
@@ -339,6 +380,11 @@ class SlimConvTranspose2d(nn.Module):
         st = _stats_bn(self.bn, 'relu', x.shape[0], cout)
         y = _hip_conv.conv_transpose2d(x, self.conv.weight, 2, 1, st)
         return _bn_relu(self.bn, y, bool(st))
+    if _f32_route(x):
+      from lsi.nnutils import _hip_conv  # pylint: disable=g-import-not-at-top
+      cin, cout = self.conv.weight.shape[:2]
+      if _hip_conv.f32_convt_supported(x, cin, cout, 4, 2):
+        return _bn_relu(self.bn, _hip_conv.conv_transpose2d_f32(x, self.conv.weight, 2, 1))
     return _bn_relu(self.bn, self.conv(x))
 
 

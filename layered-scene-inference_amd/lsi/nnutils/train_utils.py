@@ -160,6 +160,10 @@ class Trainer(object):
       nets.enable_head_streams(
           self.world == 1 and not self.flat_grads and
           (env == '1' or (env != '0' and not self.use_graph)))
+      # --fp32_convs: fp32 convolutions on the library or on the exact-fp32
+      # kernels (nets.F32_CONV; no effect under --bf16)
+      if getattr(opts, 'fp32_convs', None) is not None:
+        nets.F32_CONV = opts.fp32_convs == 'own'
     self.resume()
     if self.flat_grads:
       self._setup_flat_grads()

@@ -34,7 +34,8 @@ def main():
     print(json.dumps({'metric': 'training samples/s', 'value': opts.batch_size * tr.world * steps / dt,
                       'ms_per_step': dt * 1e3 / steps, 'n_gpus': tr.world, 'batch_per_gpu': opts.batch_size,
                       'n_layers': opts.n_layers, 'hw': [opts.img_height, opts.img_width],
-                      'bf16': bool(opts.bf16), 'peak_mem_GB': torch.cuda.max_memory_allocated() / 1e9}))
+                      'bf16': bool(opts.bf16), 'fp32_convs': getattr(opts, 'fp32_convs', None),
+                      'peak_mem_GB': torch.cuda.max_memory_allocated() / 1e9}))
   if tr.dist is not None: tr.dist.destroy_process_group()
 
 if __name__ == '__main__':

@@ -259,6 +259,51 @@ int lsi_splat_bwd_m(const LsiSplatDesc* desc, const float* tex,
                     size_t workspace_bytes, lsi_stream_t stream);
 
 /*
+ * lsi_splat_bwd_m plus the gradient through out_disp, the target disparity
+ * (ldi.py:147-171: the third splat of D * pw, divide_safe, reduce_max), as TF
+ * autodiff gives it.  desc is the forward's descriptor and must carry
+ * LSI_WANT_DISP (else LSI_EINVAL); out_disp [nl,B,Ht,Wt,1] is the forward's
+ * output and g_disp_out its incoming gradient (same layout, contiguous; both
+ * required, LSI_ENULL).  Everything else is as lsi_splat_bwd_m: g_M B x 4 x 4
+ * required iff LSI_GRAD_M (it then includes the disparity's share), the other
+ * pointers and layouts as lsi_splat_bwd.  Per target cell and layer l, with
+ * S_l = sum c_k pw D (no background) and W_l = bg + sum c_k pw:
+ *   disp_l = S_l / W'_l,  W'_l = W_l + 1e-8 [W_l == 0]   (divide_safe: bg = 0
+ *            and no pixel landing gives W' = 1e-8; its indicator has no gradient)
+ *   composed: out = max_l disp_l, g_l = g [disp_l == out] / n with n the
+ *            number of layers at the maximum (TF's reduce_max gradient: an even
+ *            split among ties -- every cell no layer reaches is an L-way tie at
+ *            0; a tie here is disp_l >= out - |out| 2^-19, see below); per
+ *            layer: g_l = g
+ *   gS_l = g_l / W'_l,  gW_l = g_l * (-disp_l / W'_l)
+ * and a source pixel's corner k gains gW_l + D gS_l on dL/d(c_k pw) and
+ * pw c_k gS_l on dL/dD; the zero-gradient conventions of lsi_splat_bwd hold
+ * (a landed pixel whose pw is 0, e.g. mask 0, still gives its mask c_k D zw gS).
+ * Composed calls do not have the per-layer W_l and disp_l: this call renders
+ * them again from tex / disp / mask / M (one per-layer LSI_PATH_TILE forward
+ * into the workspace), so the tie set is taken from the same per-layer values
+ * as the canvas gradients; per-layer calls read them from out_wts / out_disp.
+ * That render adds each cell's terms in no fixed order, so layers equal in
+ * exact arithmetic may differ in their last bits (hence the 2^-19 tie
+ * window), and a composed call's gradients are reproducible to rounding, not
+ * bitwise; per-layer calls are bitwise reproducible for the same outputs.
+ * A pre-pass writes the per-layer (gS, gW) canvases; the backward kernel of
+ * lsi_splat_bwd_m (streamed or gather, chosen as there for the descriptor
+ * without LSI_WANT_DISP) reads them at each pixel's corners.
+ * workspace: lsi_splat_bwd_disp_workspace_bytes(desc) bytes of device scratch.
+ */
+size_t lsi_splat_bwd_disp_workspace_bytes(const LsiSplatDesc* desc);
+
+int lsi_splat_bwd_disp(const LsiSplatDesc* desc, const float* tex,
+                       const float* disp, const float* mask, const float* M,
+                       const float* out_img, const float* out_wts,
+                       const float* out_disp, const float* g_img,
+                       const float* g_wts, const float* g_disp_out,
+                       float* g_tex, float* g_disp_in, float* g_mask,
+                       float* g_M, void* workspace, size_t workspace_bytes,
+                       lsi_stream_t stream);
+
+/*
  * forward_splat's two variants of one source view in ONE sweep: the reference's
  * training step renders every LDI twice, once per layer (compose_layers=False)
  * and once composed (compose_layers=True), ldi_enc_dec.py:302-334, repeating

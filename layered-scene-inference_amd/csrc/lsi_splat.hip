@@ -388,13 +388,17 @@ __global__ __launch_bounds__(256) void splat_bwd_pre_kernel(
 // gradient need no division at all.
 // GRAD_M (LSI_GRAD_M): the pixel's dL/dM share is added to `acc` as well
 // (grad_m_add); the other outputs are the same bit for bit.
+// WANT_DISP (lsi_splat_bwd_disp): GDb is the layer's (gS, gW) canvas of the
+// target disparity (splat_bwd_disp_pre_kernel).  Corner k's update of the
+// disparity canvas is c_k * pw * D and of the weight canvas c_k * pw, so
+// dL/d(c_k pw) gains gW + D gS and dL/dD gains pw * sum_k c_k gS.
 struct BwdPx { float gt0, gt1, gt2, gm, gd; };
 
-template <bool SIMPLE_M, bool GRAD_M>
+template <bool SIMPLE_M, bool GRAD_M, bool WANT_DISP>
 __device__ __forceinline__ BwdPx splat_bwd_core(
     const LsiSplatDesc& d, const float* __restrict__ m, int y, int x, float dv,
     float mk, float t0, float t1, float t2, const float4* __restrict__ Gb,
-    float (&acc)[16]) {
+    const float2* __restrict__ GDb, float (&acc)[16]) {
   const float s = d.trg_downsampling;
   const float inv_md = div_rn(1.0f, d.max_disp);
   Proj p;
@@ -429,14 +433,19 @@ __device__ __forceinline__ BwdPx splat_bwd_core(
     project_px(m, (float)x + 0.5f, (float)y + 0.5f, dv, mk, s, d.max_disp,
                d.zbuf_scale, d.Ht, d.Wt, p);
   }
-  float gt0 = 0.f, gt1 = 0.f, gt2 = 0.f, gpw = 0.f;
+  float gt0 = 0.f, gt1 = 0.f, gt2 = 0.f, gpw = 0.f, gsd = 0.f;
   float gwk[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     gwk[k] = 0.0f;
     if (!p.ok || p.w[k] == 0.0f) continue;  // clamped / invalid: zero grad
     const float4 gg = Gb[p.idx[k]];
-    const float S = t0 * gg.x + t1 * gg.y + t2 * gg.z + gg.w;
+    float S = t0 * gg.x + t1 * gg.y + t2 * gg.z + gg.w;
+    if (WANT_DISP) {
+      const float2 ge = GDb[p.idx[k]];
+      S += ge.y + p.dd * ge.x;
+      gsd += p.w[k] * ge.x;
+    }
     gt0 += p.w[k] * gg.x;
     gt1 += p.w[k] * gg.y;
     gt2 += p.w[k] * gg.z;
@@ -457,9 +466,10 @@ __device__ __forceinline__ BwdPx splat_bwd_core(
   // pw = zw * mask ; zw = exp((clip(xn,0,1)-.5)*scale)*[xn>0], xn = D/max_disp
   const float xn = SIMPLE_M ? p.dd * inv_md : p.dd / d.max_disp;
   const float inr = (xn >= 0.0f && xn <= 1.0f) ? 1.0f : 0.0f;
-  const float gD = SIMPLE_M
-                       ? gpw * mk * p.zw * d.zbuf_scale * inr * inv_md
-                       : gpw * mk * p.zw * d.zbuf_scale * inr / d.max_disp;
+  float gD = SIMPLE_M
+                 ? gpw * mk * p.zw * d.zbuf_scale * inr * inv_md
+                 : gpw * mk * p.zw * d.zbuf_scale * inr / d.max_disp;
+  if (WANT_DISP) gD += gsd * p.pw;
   // u = q0/n' * s, v = q1/n' * s, D = q3/n'
   float gd;
   if (SIMPLE_M) {  // n' == 1, M[2][3] == 0, M[3][3] == 1
@@ -495,11 +505,12 @@ constexpr int BWD_ROWS = 8;
 
 struct BwdIn { float dv, mk, t0, t1, t2; };
 
-template <bool SIMPLE_M, bool GRAD_M>
+template <bool SIMPLE_M, bool GRAD_M, bool WANT_DISP>
 __device__ __forceinline__ void splat_bwd_rows(
     const SplatArgs& a, const float* __restrict__ m, int b, int l, int y0, int x,
-    const float4* __restrict__ G, float* __restrict__ g_tex,
-    float* __restrict__ g_disp, float* __restrict__ g_mask, float (&acc)[16]) {
+    const float4* __restrict__ G, const float2* __restrict__ GD,
+    float* __restrict__ g_tex, float* __restrict__ g_disp,
+    float* __restrict__ g_mask, float (&acc)[16]) {
   const LsiSplatDesc& d = a.d;
   const bool has_mask = d.flags & LSI_HAS_MASK;
   const float* dbase = a.disp + l * d.disp_sl + b * d.disp_sb + x * d.disp_sx;
@@ -523,6 +534,7 @@ __device__ __forceinline__ void splat_bwd_rows(
   const size_t P = (size_t)d.Ht * d.Wt;
   const int lo = (d.flags & LSI_COMPOSE) ? 0 : l;
   const float4* Gb = G + ((size_t)lo * d.B + b) * P;
+  const float2* GDb = WANT_DISP ? GD + ((size_t)l * d.B + b) * P : nullptr;
   const size_t obase = ((size_t)l * d.B + b) * ((size_t)d.H * d.W) + x;
   BwdIn cur = load(y0);
 #pragma unroll
@@ -530,8 +542,8 @@ __device__ __forceinline__ void splat_bwd_rows(
     const int y = y0 + r;
     const BwdIn nxt = load(y + 1);
     if (y < d.H) {
-      const BwdPx g = splat_bwd_core<SIMPLE_M, GRAD_M>(d, m, y, x, cur.dv, cur.mk,
-                                                       cur.t0, cur.t1, cur.t2, Gb, acc);
+      const BwdPx g = splat_bwd_core<SIMPLE_M, GRAD_M, WANT_DISP>(
+          d, m, y, x, cur.dv, cur.mk, cur.t0, cur.t1, cur.t2, Gb, GDb, acc);
       const size_t o = obase + (size_t)y * d.W;
       // one 12-byte store per lane: a wave writes 768 contiguous bytes
       *reinterpret_cast<float3*>(g_tex + 3 * o) = make_float3(g.gt0, g.gt1, g.gt2);
@@ -544,12 +556,14 @@ __device__ __forceinline__ void splat_bwd_rows(
 
 // GRAD_M: every workgroup also writes its 16-float share of dL/dM to
 // gm_part[16 * (flat workgroup index)] (b-major: blockIdx.z = b * L + l), which
-// grad_m_fold_kernel sums per batch element.
-template <bool GRAD_M>
+// grad_m_fold_kernel sums per batch element.  WANT_DISP: GD holds the
+// per-layer (gS, gW) canvases [L][B][Ht * Wt] of the target disparity.
+template <bool GRAD_M, bool WANT_DISP>
 __global__ __launch_bounds__(256) void splat_bwd_kernel(
     SplatArgs a, float inv_l, const float4* __restrict__ G,
     float* __restrict__ g_tex, float* __restrict__ g_disp,
-    float* __restrict__ g_mask, float* __restrict__ gm_part) {
+    float* __restrict__ g_mask, float* __restrict__ gm_part,
+    const float2* __restrict__ GD) {
   const LsiSplatDesc& d = a.d;
   const int y0 = blockIdx.y * BWD_ROWS;
   // blockIdx.z = b * L + l: the layers of a batch element run back to back and
@@ -570,9 +584,11 @@ __global__ __launch_bounds__(256) void splat_bwd_kernel(
                           m[11] == 0.0f && m[12] == 0.0f && m[13] == 0.0f &&
                           m[14] == 0.0f && m[15] == 1.0f;
     if (simple_m)
-      splat_bwd_rows<true, GRAD_M>(a, m, b, l, y0, x, G, g_tex, g_disp, g_mask, acc);
+      splat_bwd_rows<true, GRAD_M, WANT_DISP>(a, m, b, l, y0, x, G, GD, g_tex, g_disp,
+                                              g_mask, acc);
     else
-      splat_bwd_rows<false, GRAD_M>(a, m, b, l, y0, x, G, g_tex, g_disp, g_mask, acc);
+      splat_bwd_rows<false, GRAD_M, WANT_DISP>(a, m, b, l, y0, x, G, GD, g_tex, g_disp,
+                                               g_mask, acc);
   }
   if (GRAD_M) {
     __shared__ float red[4 * 16];
@@ -584,15 +600,63 @@ __global__ __launch_bounds__(256) void splat_bwd_kernel(
 
 static void launch_bwd(const SplatArgs& a, const float4* G, float* g_tex,
                        float* g_disp, float* g_mask, float* gm_part,
-                       hipStream_t stream) {
+                       hipStream_t stream, const float2* GD = nullptr) {
   const LsiSplatDesc* d = &a.d;
   const dim3 grid((d->W + 255) / 256, (d->H + BWD_ROWS - 1) / BWD_ROWS, d->L * d->B);
-  if (gm_part)
-    hipLaunchKernelGGL(splat_bwd_kernel<true>, grid, dim3(256), 0, stream, a,
-                       1.0f / (float)d->L, G, g_tex, g_disp, g_mask, gm_part);
-  else
-    hipLaunchKernelGGL(splat_bwd_kernel<false>, grid, dim3(256), 0, stream, a,
-                       1.0f / (float)d->L, G, g_tex, g_disp, g_mask, nullptr);
+  const float inv_l = 1.0f / (float)d->L;
+  if (GD) {
+    if (gm_part)
+      hipLaunchKernelGGL((splat_bwd_kernel<true, true>), grid, dim3(256), 0, stream, a,
+                         inv_l, G, g_tex, g_disp, g_mask, gm_part, GD);
+    else
+      hipLaunchKernelGGL((splat_bwd_kernel<false, true>), grid, dim3(256), 0, stream, a,
+                         inv_l, G, g_tex, g_disp, g_mask, nullptr, GD);
+  } else if (gm_part) {
+    hipLaunchKernelGGL((splat_bwd_kernel<true, false>), grid, dim3(256), 0, stream, a,
+                       inv_l, G, g_tex, g_disp, g_mask, gm_part, nullptr);
+  } else {
+    hipLaunchKernelGGL((splat_bwd_kernel<false, false>), grid, dim3(256), 0, stream, a,
+                       inv_l, G, g_tex, g_disp, g_mask, nullptr, nullptr);
+  }
+}
+
+// Pre-pass of lsi_splat_bwd_disp, one thread per (b, target cell) when the
+// layers are composed (else per (l, b, cell)): the gradient of the target
+// disparity w.r.t. each layer's disparity canvas S_l and weight canvas W_l
+// (ldi.py:164-171).  disp_l = S_l / W'_l (divide_safe: W' = W + 1e-8 [W == 0]);
+// composed, out = max_l disp_l and layer l's share is g [disp_l == out] / n,
+// n the number of layers at the maximum (TF's reduce_max gradient: ties split
+// evenly).  A tie is disp_l >= out - |out| 2^-19: the per-layer values come
+// from a re-render whose sums are not added in a fixed order, so layers that
+// are equal in exact arithmetic (duplicated layers) may differ in their last
+// bits.  Then, as TF's RealDiv gradient:
+//   gS_l = g_l / W'_l        gW_l = g_l * ((-S_l / W'_l) / W'_l)
+// Wl / Dl: the per-layer W_l and disp_l [L][B][P]; GD[(l B + b) P + p] = (gS, gW).
+__global__ __launch_bounds__(256) void splat_bwd_disp_pre_kernel(
+    size_t n, int L, int compose, const float* __restrict__ g_dsp,
+    const float* __restrict__ Wl, const float* __restrict__ Dl,
+    float2* __restrict__ GD) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float g = g_dsp[i];
+  if (!compose) {
+    const float wd = safe_den(Wl[i]);
+    GD[i] = make_float2(div_rn(g, wd), g * div_rn(-Dl[i], wd));
+    return;
+  }
+  float out = Dl[i];
+  for (int l = 1; l < L; ++l) out = fmaxf(out, Dl[(size_t)l * n + i]);
+  const float lo = out - fabsf(out) * 0x1p-19f;
+  int ties = 0;
+  for (int l = 0; l < L; ++l) ties += Dl[(size_t)l * n + i] >= lo ? 1 : 0;
+  const float share = div_rn(1.0f, (float)ties) * g;
+  for (int l = 0; l < L; ++l) {
+    const size_t j = (size_t)l * n + i;
+    const float dl = Dl[j];
+    const float gl = dl >= lo ? share : 0.0f;
+    const float wd = safe_den(Wl[j]);
+    GD[j] = make_float2(div_rn(gl, wd), gl * div_rn(-dl, wd));
+  }
 }
 
 // dL/dM of batch element blockIdx.x: the sum of its `nper` workgroup partials
@@ -977,6 +1041,129 @@ int lsi_splat_bwd_m(const LsiSplatDesc* d, const float* tex, const float* disp,
   if ((long)d->B * d->L > 65535 || d->H > 65535) return LSI_EINVAL;  // grid.y / z
   launch_bwd(a, (const float4*)workspace, g_tex, g_disp_in,
              (d->flags & LSI_HAS_MASK) ? g_mask : nullptr, gm_part, stream);
+  if (g_M) return grad_m_fold(d, gm_part, (int)(grad_m_gather_parts(d) / d->B), g_M, stream);
+  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+}
+
+}  // extern "C"
+
+namespace {
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// lsi_splat_bwd_disp's recomputation of the per-layer canvases of a composed
+// call: the forward's own inputs, one per-layer LSI_WANT_DISP render on the
+// any-pose TILE path (no caller state: no kept workspace, no adaptive record).
+LsiSplatDesc disp_layers_desc(const LsiSplatDesc* d) {
+  LsiSplatDesc r = *d;
+  r.flags = (d->flags & (LSI_HAS_MASK | LSI_PACKED_RGBD | LSI_DETERMINISTIC)) |
+            LSI_WANT_DISP;
+  r.path = LSI_PATH_TILE;
+  r.tune_rows = r.tune_threads = r.tune_window = r.reserved = 0;
+  r.adapt = nullptr;
+  return r;
+}
+
+// lsi_splat_bwd_disp's workspace: [lsi_splat_bwd_workspace_bytes(d)] [GD: the
+// per-layer (gS, gW) float2 canvases] and, composed, [per-layer img, wts, disp]
+// [the TILE forward's workspace]; every part 256-byte aligned.
+struct DispWs { size_t gd, img, wts, dsp, fws, fws_bytes, total; };
+
+DispWs disp_ws_layout(const LsiSplatDesc* d) {
+  DispWs w;
+  const size_t n = (size_t)d->L * d->B * d->Ht * d->Wt;
+  w.gd = align256(lsi_splat_bwd_workspace_bytes(d));
+  w.total = w.gd + align256(n * sizeof(float2));
+  w.img = w.wts = w.dsp = w.fws = w.fws_bytes = 0;
+  if (d->flags & LSI_COMPOSE) {
+    const LsiSplatDesc r = disp_layers_desc(d);
+    w.img = w.total;
+    w.wts = w.img + align256(n * 3 * sizeof(float));
+    w.dsp = w.wts + align256(n * sizeof(float));
+    w.fws = w.dsp + align256(n * sizeof(float));
+    w.fws_bytes = lsi_splat_workspace_bytes(&r);
+    w.total = w.fws + align256(w.fws_bytes);
+  }
+  return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t lsi_splat_bwd_disp_workspace_bytes(const LsiSplatDesc* d) {
+  if (check_desc(d) != LSI_OK) return 0;
+  return disp_ws_layout(d).total;
+}
+
+int lsi_splat_bwd_disp(const LsiSplatDesc* d, const float* tex, const float* disp,
+                       const float* mask, const float* M, const float* out_img,
+                       const float* out_wts, const float* out_disp,
+                       const float* g_img, const float* g_wts,
+                       const float* g_disp_out, float* g_tex, float* g_disp_in,
+                       float* g_mask, float* g_M, void* workspace,
+                       size_t workspace_bytes, lsi_stream_t stream_) {
+  int rc = check_desc(d);
+  if (rc != LSI_OK) return rc;
+  if (!(d->flags & LSI_WANT_DISP)) return LSI_EINVAL;
+  if (!tex || !disp || !M || !out_img || !out_wts || !out_disp || !g_img ||
+      !g_disp_out || !g_tex || !g_disp_in || !workspace)
+    return LSI_ENULL;
+  rc = grad_m_args(d, g_M);
+  if (rc != LSI_OK) return rc;
+  if ((d->flags & LSI_HAS_MASK) && !mask) return LSI_ENULL;
+  if (!packed_ok(d, tex, disp)) return LSI_EINVAL;
+  const DispWs ws = disp_ws_layout(d);
+  if (workspace_bytes < ws.total) return LSI_EWORKSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  char* const base = (char*)workspace;
+  float* const gm_part = g_M ? (float*)(base + grad_m_part_offset(d)) : nullptr;
+  float2* const GD = (float2*)(base + ws.gd);
+  const bool compose = (d->flags & LSI_COMPOSE) != 0;
+  // per-layer W_l and disp_l: the forward's outputs, or (composed) rendered
+  // again per layer -- the tie set and the canvas gradients then come from the
+  // same values
+  const float* Wl = out_wts;
+  const float* Dl = out_disp;
+  if (compose) {
+    const LsiSplatDesc r = disp_layers_desc(d);
+    rc = lsi_splat_fwd(&r, tex, disp, mask, M, (float*)(base + ws.img),
+                       (float*)(base + ws.wts), (float*)(base + ws.dsp),
+                       base + ws.fws, ws.fws_bytes, stream_);
+    if (rc != LSI_OK) return rc;
+    Wl = (const float*)(base + ws.wts);
+    Dl = (const float*)(base + ws.dsp);
+  }
+  const size_t n = (compose ? 1 : (size_t)d->L) * d->B * d->Ht * d->Wt;
+  hipLaunchKernelGGL(splat_bwd_disp_pre_kernel, dim3((unsigned)((n + 255) / 256)),
+                     dim3(256), 0, stream, n, d->L, compose ? 1 : 0, g_disp_out,
+                     Wl, Dl, GD);
+  if (hipGetLastError() != hipSuccess) return LSI_ELAUNCH;
+  // the streamed kernel where lsi_splat_bwd_m would take it for the same
+  // descriptor without the disparity output
+  LsiSplatDesc ds = *d;
+  ds.flags &= ~LSI_WANT_DISP;
+  if (lsi_bwd_stream_applies(&ds, tex, disp, mask, g_tex, g_disp_in, g_mask)) {
+    const LsiBwdCanvas ci = {out_img, out_wts, g_img, g_wts};
+    int nper = 0;
+    rc = lsi_bwd_stream_launch(d, tex, disp, mask, M, &ci, nullptr, g_tex,
+                               g_disp_in, g_mask, gm_part, &nper, stream, GD);
+    if (rc != LSI_OK || !g_M) return rc;
+    return grad_m_fold(d, gm_part, nper, g_M, stream);
+  }
+  if ((long)d->B * d->L > 65535 || d->H > 65535) return LSI_EINVAL;  // grid.y / z
+  hipLaunchKernelGGL(splat_bwd_pre_kernel, dim3((unsigned)((n + 255) / 256)),
+                     dim3(256), 0, stream, n, out_img, out_wts, g_img, g_wts,
+                     (float4*)workspace);
+  SplatArgs a;
+  a.d = *d;
+  a.tex = tex; a.disp = disp; a.mask = mask; a.M = M;
+  a.out_img = a.out_wts = a.out_disp = a.canvas = nullptr;
+  a.ws_bytes = 0;
+  a.nch = 4; a.ncanv = 1; a.shared = 0; a.band_rows = 0;
+  a.out_img_c = a.out_wts_c = nullptr;
+  launch_bwd(a, (const float4*)workspace, g_tex, g_disp_in,
+             (d->flags & LSI_HAS_MASK) ? g_mask : nullptr, gm_part, stream, GD);
   if (g_M) return grad_m_fold(d, gm_part, (int)(grad_m_gather_parts(d) / d->B), g_M, stream);
   return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
 }

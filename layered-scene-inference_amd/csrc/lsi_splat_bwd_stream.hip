@@ -28,6 +28,10 @@
 //   values, not their gradients): each lane adds its pixels' dL/dq (x) p to 16
 //   registers, and the workgroup writes their sum as one partial
 //   (grad_m_block_sum) -- BSArgs.gm_part[16 * (band + nbands * (layer + NZ b))].
+// * WANT_DISP (lsi_splat_bwd_disp): the gradient of the target disparity as
+//   well.  Each layer's (gS, gW) canvas (BSArgs.gd, splat_bwd_disp_pre_kernel)
+//   is read at the four corners from memory, like the band-does-not-fit
+//   fallback; the terms are splat_bwd_core<WANT_DISP>'s.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -88,6 +92,7 @@ struct BSArgs {
   int RS;       // source rows per band
   int GR;       // canvas rows the LDS tile holds (0: always gather from global)
   float* gm_part;  // GRAD_M: the workgroups' dL/dM partials
+  const float2* gd;  // WANT_DISP: per-layer (gS, gW) canvases [L][B][Ht * Wt]
 };
 
 struct BSIn { float4 d4, t0, t1, t2, mk; };
@@ -165,7 +170,7 @@ typedef const __attribute__((address_space(3))) bs_f4v bs_lds_f4;
 
 // The wave's items, two register sets of loads in flight.  IN_LDS: the band's
 // canvas rows glo .. are in the LDS tile `gt`; else gathered from Gb.
-template <bool IN_LDS, bool PACK, bool MASK, bool GRAD_M>
+template <bool IN_LDS, bool PACK, bool MASK, bool GRAD_M, bool WANT_DISP>
 __device__ __forceinline__ void bs_run(const BSArgs& a, const float (&m)[8],
                                        BSIn (&set)[2], const float4* gt,
                                        size_t obi, size_t obc, int b,
@@ -262,6 +267,19 @@ __device__ __forceinline__ void bs_run(const BSArgs& a, const float (&m)[8],
         g2 = bs_G(a, obi + rb + c0, obc + rb + c0);
         g3 = bs_G(a, obi + rb + c1, obc + rb + c1);
       }
+      // target disparity: the corners' (gS, gW) of this layer; dL/d(c_k pw)
+      // gains gW + d gS (folded into G_k.w), dL/dd gains pw * sum_k c_k gS
+      float gsd = 0.0f;
+      if (WANT_DISP) {
+        const float2* gdl = a.gd + ((size_t)(l_lo + l) * a.B + b) * ((size_t)a.Ht * Wt);
+        const size_t ra = (size_t)r0 * Wt, rb = (size_t)r1 * Wt;
+        const float2 e0 = gdl[ra + c0], e1 = gdl[ra + c1];
+        const float2 e2 = gdl[rb + c0], e3 = gdl[rb + c1];
+        const float dz = ok ? d : 0.0f;  // (a dropped pixel's weights are 0)
+        g0.w = g0.w + (e0.y + dz * e0.x); g1.w = g1.w + (e1.y + dz * e1.x);
+        g2.w = g2.w + (e2.y + dz * e2.x); g3.w = g3.w + (e3.y + dz * e3.x);
+        gsd = __fmaf_rn(w3, e3.x, __fmaf_rn(w2, e2.x, __fmaf_rn(w1, e1.x, w0 * e0.x)));
+      }
       // exp((clip(d/max,0,1) - 0.5)*scale) [d/max > 0] = exp2(clip(d,0,max)*zA + zB)
       // (the forward compact instance's form; ~1e-6 relative)
       const float xn = d * inv_md;
@@ -288,7 +306,8 @@ __device__ __forceinline__ void bs_run(const BSArgs& a, const float (&m)[8],
       // corner weights -> X: d wx0/dX = -v0, d wx1/dX = +v1
       const float gX = -ax.v0 * (k0 * ay.w0 + k2 * ay.w1) + ax.v1 * (k1 * ay.w0 + k3 * ay.w1);
       const float inr = (xn >= 0.0f && xn <= 1.0f) ? 1.0f : 0.0f;
-      const float gD = gpw * pw * zs_md * inr;
+      float gD = gpw * pw * zs_md * inr;
+      if (WANT_DISP) gD += gsd * pw;
       // (M[1][3] == 0: the row coordinate does not move with the disparity)
       const float gd = (gX * s) * m[3] + gD;
       od[i] = ok ? gd : 0.0f;
@@ -338,7 +357,7 @@ __device__ __forceinline__ void bs_run(const BSArgs& a, const float (&m)[8],
   }
 }
 
-template <bool PACK, bool MASK, bool GRAD_M>
+template <bool PACK, bool MASK, bool GRAD_M, bool WANT_DISP>
 __global__ __launch_bounds__(BS_T, LSI_BS_WPE) void splat_bwd_stream_kernel(BSArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float4* const gt = reinterpret_cast<float4*>(smem);  // [GR][Wt]
@@ -451,11 +470,11 @@ __global__ __launch_bounds__(BS_T, LSI_BS_WPE) void splat_bwd_stream_kernel(BSAr
   if (!GRAD_M && nitem <= 0) return;
   if (nitem > 0) {
     if (in_lds)
-      bs_run<true, PACK, MASK, GRAD_M>(a, m, set, gt, obi, obc, b, l_lo, NL, ys, nitem,
-                                       glo, wave, lane, acc);
+      bs_run<true, PACK, MASK, GRAD_M, WANT_DISP>(a, m, set, gt, obi, obc, b, l_lo, NL,
+                                                  ys, nitem, glo, wave, lane, acc);
     else
-      bs_run<false, PACK, MASK, GRAD_M>(a, m, set, gt, obi, obc, b, l_lo, NL, ys, nitem,
-                                        glo, wave, lane, acc);
+      bs_run<false, PACK, MASK, GRAD_M, WANT_DISP>(a, m, set, gt, obi, obc, b, l_lo, NL,
+                                                   ys, nitem, glo, wave, lane, acc);
   }
   if (GRAD_M) {
     __shared__ float red[BS_NW * 16];
@@ -505,9 +524,11 @@ int lsi_bwd_stream_launch(const LsiSplatDesc* d, const float* tex,
                           const float* disp, const float* mask, const float* M,
                           const LsiBwdCanvas* ci, const LsiBwdCanvas* cc,
                           float* g_tex, float* g_disp, float* g_mask,
-                          float* gm_part, int* gm_nper, hipStream_t stream) {
+                          float* gm_part, int* gm_nper, hipStream_t stream,
+                          const float2* gd) {
   BSArgs a;
   a.gm_part = gm_part;
+  a.gd = gd;
   a.tex = tex; a.disp = disp; a.M = M; a.g_tex = g_tex; a.g_disp = g_disp;
   {
     // Plain stores: a lane's four 16-byte stores are a third of the 48 bytes it
@@ -559,16 +580,28 @@ int lsi_bwd_stream_launch(const LsiSplatDesc* d, const float* tex,
   size_t lds = bytes_for(rs);
   if (lds > cap) { a.GR = 0; lds = 0; }
   const void* fn;
-  if (gm_part)
+  if (gd) {
+    if (gm_part)
+      fn = (d->flags & LSI_PACKED_RGBD)
+               ? (const void*)splat_bwd_stream_kernel<true, false, true, true>
+               : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, true, true>
+                           : (const void*)splat_bwd_stream_kernel<false, false, true, true>);
+    else
+      fn = (d->flags & LSI_PACKED_RGBD)
+               ? (const void*)splat_bwd_stream_kernel<true, false, false, true>
+               : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, false, true>
+                           : (const void*)splat_bwd_stream_kernel<false, false, false, true>);
+  } else if (gm_part) {
     fn = (d->flags & LSI_PACKED_RGBD)
-             ? (const void*)splat_bwd_stream_kernel<true, false, true>
-             : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, true>
-                         : (const void*)splat_bwd_stream_kernel<false, false, true>);
-  else
+             ? (const void*)splat_bwd_stream_kernel<true, false, true, false>
+             : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, true, false>
+                         : (const void*)splat_bwd_stream_kernel<false, false, true, false>);
+  } else {
     fn = (d->flags & LSI_PACKED_RGBD)
-             ? (const void*)splat_bwd_stream_kernel<true, false, false>
-             : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, false>
-                         : (const void*)splat_bwd_stream_kernel<false, false, false>);
+             ? (const void*)splat_bwd_stream_kernel<true, false, false, false>
+             : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, false, false>
+                         : (const void*)splat_bwd_stream_kernel<false, false, false, false>);
+  }
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)(lds > 0 ? lds : 16)) != hipSuccess) {
     // a device that does not grant the LDS asked for: corners from the arrays

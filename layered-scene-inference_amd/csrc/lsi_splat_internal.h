@@ -61,11 +61,14 @@ bool lsi_bwd_stream_applies(const LsiSplatDesc* d, const float* tex,
                             const float* g_mask);
 // gm_part != NULL (LSI_GRAD_M): every workgroup also writes its 16-float share
 // of dL/dM there, `*gm_nper` of them per batch element (b-major).
+// gd != NULL (lsi_splat_bwd_disp): the per-layer (gS, gW) canvases of the
+// target disparity, [L][B][Ht * Wt], read from memory at each corner.
 int lsi_bwd_stream_launch(const LsiSplatDesc* d, const float* tex,
                           const float* disp, const float* mask, const float* M,
                           const LsiBwdCanvas* ci, const LsiBwdCanvas* cc,
                           float* g_tex, float* g_disp, float* g_mask,
-                          float* gm_part, int* gm_nper, hipStream_t stream);
+                          float* gm_part, int* gm_nper, hipStream_t stream,
+                          const float2* gd = nullptr);
 
 // LSI_PATH_TILE launcher and workspace need (lsi_splat_tile.hip).
 size_t lsi_tile_workspace_bytes(const LsiSplatDesc* d);

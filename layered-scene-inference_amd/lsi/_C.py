@@ -98,6 +98,8 @@ SIGNATURES = {
     'lsi_splat_bwd_workspace_bytes': (_SZ, [_DP]),
     'lsi_splat_bwd': (ctypes.c_int, [_DP] + [_VP] * 12 + [_SZ, _VP]),
     'lsi_splat_bwd_m': (ctypes.c_int, [_DP] + [_VP] * 13 + [_SZ, _VP]),
+    'lsi_splat_bwd_disp_workspace_bytes': (_SZ, [_DP]),
+    'lsi_splat_bwd_disp': (ctypes.c_int, [_DP] + [_VP] * 15 + [_SZ, _VP]),
     'lsi_splat_fwd_both': (ctypes.c_int, [_DP] + [_VP] * 9 + [_SZ, _VP]),
     'lsi_splat_bwd_both': (ctypes.c_int, [_DP] + [_VP] * 16 + [_SZ, _VP]),
     'lsi_splat_bwd_both_m': (ctypes.c_int, [_DP] + [_VP] * 17 + [_SZ, _VP]),

@@ -226,7 +226,8 @@ def _grad_m_desc(desc):
 
 class _ForwardSplat(torch.autograd.Function):
   """lsi_splat_fwd / lsi_splat_bwd (include/lsi_hip.h); lsi_splat_bwd_m when
-  the matrices need their gradient."""
+  the matrices need their gradient; lsi_splat_bwd_disp when the target
+  disparity (compute_trg_disp=True) received a gradient."""
 
   @staticmethod
   def forward(ctx, tex, mask, disp, mat, mat_host, cfg):
@@ -280,27 +281,48 @@ class _ForwardSplat(torch.autograd.Function):
     _C.check(rc, 'lsi_splat_fwd')
     ctx.desc = desc
     ctx.has_mask = mask is not None
-    ctx.save_for_backward(tex, mask if mask is not None else tex.new_empty(0),
-                          disp, mat, img, wts)
+    # (an output without a gradient reaches backward as None: a call whose
+    # target disparity feeds no loss then takes today's launches)
+    ctx.set_materialize_grads(False)
     if dsp is None:
       dsp = img.new_empty(0)
-    ctx.mark_non_differentiable(dsp)
+      ctx.mark_non_differentiable(dsp)
+    ctx.save_for_backward(tex, mask if mask is not None else tex.new_empty(0),
+                          disp, mat, img, wts, dsp)
     return img, wts, dsp
 
   @staticmethod
-  def backward(ctx, g_img, g_wts, _g_dsp):
-    tex, mask, disp, mat, img, wts = ctx.saved_tensors
+  def backward(ctx, g_img, g_wts, g_dsp):
+    tex, mask, disp, mat, img, wts, dsp = ctx.saved_tensors
     mask = mask if ctx.has_mask else None
     desc = ctx.desc
     dev = tex.device
     nl, b, h, w, _ = tex.shape
+    # (None: what autograd materialised as zeros before -- the same pointers'
+    # contents, so the same bits)
     g_img = g_img.contiguous() if g_img is not None else torch.zeros_like(img)
-    g_wts = g_wts.contiguous() if g_wts is not None else None
+    g_wts = g_wts.contiguous() if g_wts is not None else torch.zeros_like(wts)
     g_tex = torch.empty((nl, b, h, w, 3), dtype=torch.float32, device=dev)
     g_disp = torch.empty((nl, b, h, w, 1), dtype=torch.float32, device=dev)
     g_mask = (torch.empty((nl, b, h, w, 1), dtype=torch.float32, device=dev)
               if mask is not None else None)
     lib = _C.lib()
+    if g_dsp is not None and dsp.numel():
+      g_dsp = g_dsp.contiguous()
+      g_m = None
+      if ctx.needs_input_grad[3]:
+        desc = _grad_m_desc(desc)
+        g_m = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
+      ws_bytes = int(lib.lsi_splat_bwd_disp_workspace_bytes(ctypes.byref(desc)))
+      ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+      rc = lib.lsi_splat_bwd_disp(ctypes.byref(desc), _C.ptr(tex), _C.ptr(disp),
+                                  _C.ptr(mask), _C.ptr(mat), _C.ptr(img),
+                                  _C.ptr(wts), _C.ptr(dsp), _C.ptr(g_img),
+                                  _C.ptr(g_wts), _C.ptr(g_dsp), _C.ptr(g_tex),
+                                  _C.ptr(g_disp), _C.ptr(g_mask), _C.ptr(g_m),
+                                  _C.ptr(ws), ws_bytes, _C.stream_ptr(dev))
+      _C.check(rc, 'lsi_splat_bwd_disp')
+      return g_tex, g_mask, g_disp, g_m, None, None
     if ctx.needs_input_grad[3]:
       desc = _grad_m_desc(desc)
       g_m = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
@@ -462,7 +484,9 @@ def forward_splat_matrix(ldi_src, src2trg_mat, compose_layers=True,
   `deterministic` (LSI_DETERMINISTIC) asks for bitwise run-to-run reproducible
   sums on the stream path (fixed merge order; a little slower).
   A `src2trg_mat` that requires grad gets its gradient (lsi_splat_bwd_m:
-  reduced in the backward kernels, bitwise reproducible).
+  reduced in the backward kernels, bitwise reproducible).  The target
+  disparity (compute_trg_disp=True) is differentiable (lsi_splat_bwd_disp);
+  when it feeds no loss the backward is the one without it.
   """
   tex, mask, disp = ldi_src
   if mat_host is None and path not in ('atomic', 'tile'):

@@ -529,6 +529,47 @@ int lsi_compose_depth_fwd(int32_t L, int64_t N, const float* masks,
                           lsi_stream_t stream);
 
 /*
+ * Fused renderer of batches of planar scenes (lsi/data/synthetic_planes.py):
+ * B worlds of P textured planes, V views each, in ONE launch.  Per view pixel
+ * and plane: q = hom (x + .5, y + .5, 1), divide_safe, the four bilinear taps
+ * of the RGBA texel (A = the plane's mask), the analytic disparity
+ * dmat (x + .5, y + .5, 1); then layers.compose (hard: first maximum of the
+ * soft z-buffer probabilities; or soft) and layers.compose_depth
+ * (bg_layer = False) over the P planes + the white background layer at
+ * min_disp.  The result is, bit for bit, what homography.transform_plane_imgs
+ * -> trg_disp_maps -> lsi_compose_fwd / lsi_compose_depth_fwd give; the warped
+ * layers are never written to memory.  The *_ROOM outputs are the same
+ * composition with the masks of the planes [n_box, P) taken as 0 (the room
+ * without its objects).
+ *   tex_rgba [B,P,Hs,Ws,4] (16-byte aligned; Hs*Ws <= 2^24)
+ *   hom      [B,V,P,9]  homography.inv_homography, row-major (view px -> texture px)
+ *   dmat     [B,V,P,3]  homography.inv_homography_dmat
+ *   img / img_room   [B,V,H,W,3]     disp / disp_room [B,V,H,W,1]
+ * Only the outputs named in `outputs` are written; their pointers must not be
+ * NULL (LSI_ENULL), the others may be.  1 <= P <= LSI_SCENE_MAX_PLANES,
+ * 0 <= n_box <= P, positive sizes, at least one known output bit -- else
+ * LSI_EINVAL, before any launch.  No workspace, no state.
+ */
+#define LSI_SCENE_MAX_PLANES 16
+#define LSI_SCENE_IMG 1u
+#define LSI_SCENE_DISP 2u
+#define LSI_SCENE_IMG_ROOM 4u
+#define LSI_SCENE_DISP_ROOM 8u
+typedef struct LsiSceneDesc {
+  int32_t B, V, P;        /* worlds, views per world, planes per world       */
+  int32_t Hs, Ws;         /* plane texture size                              */
+  int32_t H, W;           /* view size                                       */
+  int32_t n_box;          /* planes [n_box, P) are objects (*_ROOM outputs)  */
+  int32_t soft;           /* layers.compose(soft=...) for the images         */
+  float min_disp, temp;   /* compose / compose_depth arguments               */
+  uint32_t outputs;       /* LSI_SCENE_* bits                                */
+} LsiSceneDesc;
+int lsi_render_planes(const LsiSceneDesc* desc, const float* tex_rgba,
+                      const float* hom, const float* dmat, float* img,
+                      float* disp, float* img_room, float* disp_room,
+                      lsi_stream_t stream);
+
+/*
  * Fused batch norm (batch statistics) + beta + ReLU of the reference's conv
  * layers: slim.batch_norm(center=True, scale=False, epsilon, is_training=True)
  * followed by tf.nn.relu (nets.py:44-67, 95-111, 265-347).  x, y, dy, dx:

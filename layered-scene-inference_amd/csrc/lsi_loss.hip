@@ -20,6 +20,7 @@
 
 #include "../../include/lsi_hip.h"
 #include "lsi_common.h"
+#include "lsi_layers.h"
 
 using namespace lsi;
 
@@ -423,10 +424,7 @@ __device__ __forceinline__ float layer_logp(const CArgs& a, long n, int l) {
   } else {
     dsel = a.min_disp;
   }
-  dsel = fmaxf(dsel, 0.0f);                                   // helpers.py:152
-  const float depth = div_rn(1.0f, safe_den(dsel));           // divide_safe(1, d)
-  const float lp = div_rn(-depth, a.temp);
-  return logf(m + 1e-8f) + lp;
+  return layer_logp_of(m, dsel, a.temp);  // lsi_layers.h, shared with lsi_scene.hip
 }
 
 __global__ __launch_bounds__(TPB) void compose_kernel(CArgs a, float* out) {

@@ -75,10 +75,12 @@ def build_parser():
   # build-specific switches
   # synthetic planar worlds (reference ldi_enc_dec.py:52-55, 86-123): procedural
   # textures replace the SUN / PASCAL images
-  a('--synth_scene', default='pairs', choices=['pairs', 'planes'],
+  a('--synth_scene', default='pairs', choices=['pairs', 'planes', 'planes_batched'],
     help="synthetic inputs: 'pairs' = shifted smooth images generated on the "
     "device (throughput runs); 'planes' = box room + billboard objects "
-    'rendered through planar_transform + compose (lsi/data/synthetic_planes)')
+    'rendered through planar_transform + compose (lsi/data/synthetic_planes); '
+    "'planes_batched' = the same scenes, textures made on the device and the "
+    'whole batch rendered by one fused launch (synthetic_planes.BatchedDataLoader)')
   a('--debug_synth_texture', type=_bool, default=False,
     help='feed the ground-truth fg / bg disparities in place of the predicted '
     'ones (n_layers = 2, --synth_scene planes): the renderer must then '
@@ -250,7 +252,8 @@ class Trainer(train_utils.Trainer):
 
   def define_data_loader(self):
     opts = self.opts
-    if opts.dataset == 'synthetic' and (opts.synth_scene == 'planes' or
+    if opts.dataset == 'synthetic' and (opts.synth_scene in ('planes',
+                                                             'planes_batched') or
                                         opts.debug_synth_texture):
       from lsi.data import synthetic_planes  # pylint: disable=g-import-not-at-top
       if opts.debug_synth_texture and opts.n_layers != 2:
@@ -258,8 +261,10 @@ class Trainer(train_utils.Trainer):
                          'n_layers must be 2')
       opts.synth_dl_eval_data = (bool(opts.debug_synth_texture) or
                                  bool(getattr(opts, 'synth_dl_eval_data', False)))
-      self.data_loader = synthetic_planes.DataLoader(
-          opts, device=self.device, seed=1234 + self.rank)
+      loader = (synthetic_planes.BatchedDataLoader
+                if opts.synth_scene == 'planes_batched' else
+                synthetic_planes.DataLoader)
+      self.data_loader = loader(opts, device=self.device, seed=1234 + self.rank)
     elif opts.dataset == 'kitti' and not opts.kitti_procedural:
       # reference ldi_enc_dec.py:134-137
       from lsi.data.kitti import data as kitti_data  # pylint: disable=g-import-not-at-top

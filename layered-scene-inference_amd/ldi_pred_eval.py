@@ -152,7 +152,7 @@ class Tester(object):
 
 def main(argv=None):
   opts = train_script.apply_dataset_overrides(build_parser().parse_args(argv))
-  if opts.dataset == 'synthetic' and opts.synth_scene == 'planes':
+  if opts.dataset == 'synthetic' and opts.synth_scene in ('planes', 'planes_batched'):
     # ground truth for the depth / disocclusion / fg-bg metrics
     opts.debug_synth_texture = False
     opts.synth_dl_eval_data = True

@@ -23,6 +23,8 @@ LSI_PACKED_RGBD = 32
 LSI_GRAD_M = 64
 LSI_PATH_AUTO, LSI_PATH_ATOMIC, LSI_PATH_ROWBAND, LSI_PATH_STREAM = 0, 1, 2, 3
 LSI_PATH_TILE = 4
+LSI_SCENE_IMG, LSI_SCENE_DISP, LSI_SCENE_IMG_ROOM, LSI_SCENE_DISP_ROOM = 1, 2, 4, 8
+LSI_SCENE_MAX_PLANES = 16
 PATH_NAMES = {1: 'atomic', 2: 'rowband', 3: 'stream', 4: 'tile'}
 
 _c_f = ctypes.POINTER(ctypes.c_float)
@@ -65,6 +67,13 @@ class LsiLossDesc(ctypes.Structure):
 class LsiConvDesc(ctypes.Structure):
   _fields_ = [(n, ctypes.c_int32) for n in (
       'N', 'H', 'W', 'Cin', 'OH', 'OW', 'Cout', 'KH', 'KW', 'stride', 'pad_t', 'pad_l')]
+
+
+class LsiSceneDesc(ctypes.Structure):
+  _fields_ = ([(n, ctypes.c_int32) for n in ('B', 'V', 'P', 'Hs', 'Ws', 'H', 'W',
+                                             'n_box', 'soft')] +
+              [('min_disp', ctypes.c_float), ('temp', ctypes.c_float),
+               ('outputs', ctypes.c_uint32)])
 
 
 class LsiPackJob(ctypes.Structure):
@@ -131,6 +140,7 @@ SIGNATURES = {
                         [_I32, _F32, _F32, _VP, _VP]),
     'lsi_compose_depth_fwd': (ctypes.c_int, [_I32, _I64] + [_VP] * 2 +
                               [_I32, _F32, _F32, _F32, _VP, _VP]),
+    'lsi_render_planes': (ctypes.c_int, [ctypes.POINTER(LsiSceneDesc)] + [_VP] * 8),
     'lsi_conv2d_supported': (ctypes.c_int, [_CP]),
     'lsi_conv2d_packed_bytes': (_SZ, [_CP]),
     'lsi_conv2d_pack': (ctypes.c_int, [_CP, _I32, _VP, _VP, _SZ, _VP]),

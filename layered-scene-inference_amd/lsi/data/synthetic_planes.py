@@ -132,14 +132,21 @@ def _texture(gen, h, w):
   return (tex[0].permute(1, 2, 0) * 0.85 + checker[..., None]).numpy()
 
 
+def _silhouette_params(rs):
+  """The random numbers of one silhouette: (cx, cy, rx, ry) of its two
+  ellipses, as fractions of the texture's width / height."""
+  return [(rs.uniform(0.35, 0.65), rs.uniform(0.45, 0.7),
+           rs.uniform(0.2, 0.42), rs.uniform(0.28, 0.45)) for _ in range(2)]
+
+
 def _silhouette(rs, h, w):
   """Object alpha mask (the reference's PASCAL object crops fill their texture
   with an alpha channel): a union of two ellipses touching the bottom edge."""
   yy, xx = np.meshgrid(np.arange(h) + 0.5, np.arange(w) + 0.5, indexing='ij')
   m = np.zeros((h, w), np.float32)
-  for _ in range(2):
-    cx, cy = rs.uniform(0.35, 0.65) * w, rs.uniform(0.45, 0.7) * h
-    rx, ry = rs.uniform(0.2, 0.42) * w, rs.uniform(0.28, 0.45) * h
+  for fx, fy, frx, fry in _silhouette_params(rs):
+    cx, cy = fx * w, fy * h
+    rx, ry = frx * w, fry * h
     m = np.maximum(m, ((((xx - cx) / rx)**2 + ((yy - cy) / ry)**2) < 1)
                    .astype(np.float32))
   m[int(0.8 * h):, int(0.35 * w):int(0.65 * w)] = 1.0   # stands on the floor
@@ -197,24 +204,33 @@ class WorldGenerator(object):
             'x_dir': np.array([1, 0, 0]), 'y_dir': np.array([0, 1, 0]),
             'w': w_obj, 'h': h_obj, 'off_x': 0.5, 'off_y': 1}
 
-  def forward(self):
+  def forward(self, raster=True):
     """rot_w2s, t_w2s [bs,3,3 / bs,3,1] (canonical plane frame -> world), k_w
     [bs,3,3], n_hat_w [bs,1,3], a_w [bs,1,1], imgs_w [bs,h,w,3], masks_w
-    [bs,h,w,1] (data.py:204-290)."""
+    [bs,h,w,1] (data.py:204-290).  raster=False draws the same geometry but no
+    textures: the last two entries are then n_obj and the objects' silhouette
+    parameters (`_silhouette_params`), for a caller that evaluates textures and
+    silhouettes itself (BatchedDataLoader, textures='device')."""
     bs, h, w, nb = self.bs, self.h, self.w, self.n_box_planes
-    imgs_w = np.ones((bs, h, w, 3), np.float32)
-    masks_w = np.zeros((bs, h, w, 1), np.float32)
+    imgs_w = masks_w = None
+    if raster:
+      imgs_w = np.ones((bs, h, w, 3), np.float32)
+      masks_w = np.zeros((bs, h, w, 1), np.float32)
     n_hat_w = np.tile(np.array([[[0.0, 0.0, 1.0]]]), (bs, 1, 1))
     a_w = np.tile(np.array([[[-1.0]]]), (bs, 1, 1))
     planes = box_planes(EXTENT)[0:nb]
-    for i in range(len(planes)):
+    for i in range(len(planes) if raster else 0):
       masks_w[i] = 1
       imgs_w[i] = _texture(self.gen, h, w)
     n_obj = self.rs.randint(self.n_obj_min, self.n_obj_max + 1)
+    sil = []
     for ix in range(self.n_obj_max):
       if ix < n_obj:
-        imgs_w[ix + nb] = _texture(self.gen, h, w)
-        masks_w[ix + nb, :, :, 0] = _silhouette(self.rs, h, w)
+        if raster:
+          imgs_w[ix + nb] = _texture(self.gen, h, w)
+          masks_w[ix + nb, :, :, 0] = _silhouette(self.rs, h, w)
+        else:
+          sil.append(_silhouette_params(self.rs))
         aspect_tex = self.rs.uniform(0.7, 1.6)   # crop height / width
         planes.append(self.random_obj_plane(EXTENT, aspect_tex, fixed_plane=ix))
       else:
@@ -230,6 +246,8 @@ class WorldGenerator(object):
       # (the reference passes (h, w) for (w_tex, h_tex), data.py:288 -- the
       # same thing for its square textures; the texture here may not be square)
       k_w[ix] = dims2kmat(pl['w'], pl['h'], w, h)
+    if not raster:
+      return rot_w2s, t_w2s, k_w, n_hat_w, a_w, n_obj, sil
     return rot_w2s, t_w2s, k_w, n_hat_w, a_w, imgs_w, masks_w
 
 
@@ -399,3 +417,149 @@ class SceneGenerator(object):
   def forward(self, bs):
     out = self.loader.forward(bs)
     return (out[0], out[1], out[2], out[3], out[4], out[5], out[8], out[10])
+
+
+class BatchedDataLoader(object):
+  """DataLoader's batches without its per-instance loop: the worlds of a batch
+  are rendered, both views and (with synth_dl_eval_data) the room-alone
+  outputs, by ONE lsi_render_planes launch (layers.render_planes), after one
+  batched evaluation of the B x 2 x P plane homographies.  forward(bs) returns
+  DataLoader.forward's list (6 outputs, 14 with synth_dl_eval_data; the
+  background disparities of compose_depth(bg_layer=True), which DataLoader
+  computes and drops, are not computed).
+
+  textures='host': worlds from WorldGenerator(seed) and views from
+  RandomState(seed + 1), exactly DataLoader's -- the same batches, bit for bit
+  (the textures are still made on the CPU and uploaded, once per batch).
+  textures='device': the plane geometry and the silhouette parameters are drawn
+  on the host (a few hundred numbers), the B x P textures (torch.rand on a
+  device generator, bicubic up-sampling, checker: `_texture`'s recipe) and the
+  ellipse silhouettes (`_silhouette`'s) are evaluated on the device in batched
+  torch calls; nothing of image size crosses PCIe.  Same distribution as
+  DataLoader's scenes, not the same values."""
+
+  def __init__(self, opts, device='cuda', seed=0, textures='device'):
+    if textures not in ('host', 'device'):
+      raise ValueError("textures: 'host' or 'device' (got %r)" % (textures,))
+    self.device = torch.device(device)
+    if self.device.type != 'cuda':
+      raise RuntimeError(
+          'BatchedDataLoader renders with lsi_render_planes on a ROCm GPU (got '
+          'device %s); there is no CPU fallback' % self.device)
+    self.opts, self.textures = opts, textures
+    self.output_gt = bool(getattr(opts, 'synth_dl_eval_data', False))
+    self.ds = int(getattr(opts, 'synth_ds_factor', 1))
+    self.w, self.h = opts.img_width * self.ds, opts.img_height * self.ds
+    self.n_box_planes = getattr(opts, 'n_box_planes', 5)
+    self.n_obj_max = getattr(opts, 'n_obj_max', 4)
+    self.generator = WorldGenerator(h=self.h, w=self.w, n_obj_max=self.n_obj_max,
+                                    n_obj_min=getattr(opts, 'n_obj_min', 1),
+                                    n_box_planes=self.n_box_planes, seed=seed)
+    f_x, f_y = float(self.w), float(self.h)
+    self.k_s = np.array([[f_x, 0, f_x / 2.0], [0, f_y, f_y / 2.0], [0, 0, 1]])
+    self.k_t = np.copy(self.k_s)
+    self.rs = np.random.RandomState(seed + 1)
+    self.gen = torch.Generator(device=self.device).manual_seed(seed)
+    yy, xx = torch.meshgrid(torch.arange(self.h, device=self.device),
+                            torch.arange(self.w, device=self.device), indexing='ij')
+    self._checker = (((yy // 16) + (xx // 16)) % 2).float() * 0.15
+    self._yy, self._xx = yy.float() + 0.5, xx.float() + 0.5
+
+  def _t(self, a):
+    # (fp64 -> fp32 on the host, as Renderer._t: the device sees the same bits)
+    return torch.as_tensor(np.asarray(a), dtype=torch.float32).to(
+        self.device, non_blocking=True)
+
+  def _device_textures(self, n_objs, sils):
+    """RGBA textures B x P x h x w x 4 of worlds with n_objs[b] objects whose
+    silhouette parameters are sils[b]: `_texture` / `_silhouette` evaluated for
+    the whole batch on the device."""
+    bs, nb, no, h, w = len(n_objs), self.n_box_planes, self.n_obj_max, self.h, self.w
+    npl = nb + no
+    lo = torch.rand((bs * npl, 3, h // 16 + 2, w // 16 + 2), generator=self.gen,
+                    device=self.device)
+    rgb = torch.nn.functional.interpolate(lo, size=(h, w), mode='bicubic',
+                                          align_corners=False).clamp(0, 1)
+    rgb = rgb * 0.85 + self._checker
+    tex = torch.empty((bs, npl, h, w, 4), dtype=torch.float32, device=self.device)
+    tex[..., :3] = rgb.reshape(bs, npl, 3, h, w).permute(0, 1, 3, 4, 2)
+    tex[:, :nb, :, :, 3] = 1.0
+    if no:
+      # per object slot: used flag + (cx, cy, rx, ry) of two ellipses, in pixels
+      par = np.ones((bs, no, 9), np.float32)
+      par[:, :, 0] = 0.0
+      for b in range(bs):
+        for i, ell in enumerate(sils[b]):
+          par[b, i, 0] = 1.0
+          par[b, i, 1:] = [v * s for e in ell for v, s in zip(e, (w, h, w, h))]
+      par = torch.from_numpy(par).to(self.device, non_blocking=True)
+      p = lambda k: par[:, :, k, None, None]
+      yy, xx = self._yy, self._xx
+      m = torch.zeros((bs, no, h, w), dtype=torch.float32, device=self.device)
+      for e in (1, 5):
+        m = torch.maximum(m, ((((xx - p(e)) / p(e + 2))**2 +
+                               ((yy - p(e + 1)) / p(e + 3))**2) < 1).float())
+      m[:, :, int(0.8 * h):, int(0.35 * w):int(0.65 * w)] = 1.0   # stands on the floor
+      used = p(0)
+      tex[:, nb:, :, :, 3] = m * used
+      # unused slots: WorldGenerator's white, fully transparent planes
+      tex[:, nb:, :, :, :3] = torch.where(used[..., None] > 0,
+                                          tex[:, nb:, :, :, :3],
+                                          torch.ones((), device=self.device))
+    return tex
+
+  def forward(self, bs):
+    """bs instances, every output with the batch axis first: img_s, img_t, k_s,
+    k_t, rot, trans[, n_hat, a, disp_s_fg, disp_s_bg, disp_t_fg, disp_t_bg,
+    img_s_bg, img_t_bg] (DataLoader.forward's list and placement: cameras and
+    poses on the host, everything rendered on the device)."""
+    host = self.textures == 'host'
+    worlds = [self.generator.forward(raster=host) for _ in range(bs)]
+    views = [sample_views(1, self.rs)[0] for _ in range(bs)]
+    stack = lambda i: self._t(np.stack([wd[i] for wd in worlds]))
+    rot_w2s, t_w2s, k_w, n_hat_w, a_w = [stack(i) for i in range(5)]
+    if host:
+      rgba = np.concatenate([np.stack([wd[5] for wd in worlds]),
+                             np.stack([wd[6] for wd in worlds])], axis=-1)
+      tex = torch.from_numpy(rgba).pin_memory().to(self.device, non_blocking=True)
+    else:
+      tex = self._device_textures([wd[5] for wd in worlds],
+                                  [wd[6] for wd in worlds])
+    # views: 0 = source (the world frame), 1 = target
+    rot_src, trans_src = np.eye(3), np.zeros((3, 1))
+    rv = self._t(np.stack([np.stack([rot_src, v[0]]) for v in views]))    # B,2,3,3
+    tv = self._t(np.stack([np.stack([trans_src, v[1]]) for v in views]))  # B,2,3,1
+    k_v = self._t(np.stack([self.k_s, self.k_t]))[None]                   # 1,2,3,3
+    # world -> view composed with every plane's canonical -> world transform
+    # (Renderer._warp), for the B x 2 x P (view, plane) pairs at once
+    rv, tv = rv[:, :, None], tv[:, :, None]
+    rot_w2t = nn_helpers.seq_matmul(rv, rot_w2s[:, None])
+    t_w2t = tv + nn_helpers.seq_matmul(rv, t_w2s[:, None])
+    out = layers.render_planes(
+        tex, None, k_w[:, None], k_v[:, :, None], rot_w2t, t_w2t,
+        n_hat_w[:, None], a_w[:, None], (self.h, self.w), soft=False,
+        min_disp=MIN_DISP, depth_softmax_temp=SOFTMAX_TEMP,
+        n_box=self.n_box_planes if self.output_gt else None)
+
+    def down(x):   # one view of the B x 2 x ... rendering, as its own tensor
+      if self.ds == 1:
+        return x.contiguous()
+      from lsi.loss import loss  # pylint: disable=g-import-not-at-top
+      return loss.area_downsample(x, self.h // self.ds, self.w // self.ds)
+
+    img = out[0]
+    k_s = resize_instrinsic(self.k_s, 1.0 / self.ds, 1.0 / self.ds)
+    k_t = resize_instrinsic(self.k_t, 1.0 / self.ds, 1.0 / self.ds)
+    rots = [np.matmul(v[0], rot_src.T) for v in views]
+    trans = [v[1] - np.matmul(r, trans_src) for v, r in zip(views, rots)]
+    f32 = lambda x: torch.tensor(np.asarray(x), dtype=torch.float32)
+    res = [down(img[:, 0]), down(img[:, 1]), f32(np.stack([k_s] * bs)),
+           f32(np.stack([k_t] * bs)), f32(np.stack(rots)), f32(np.stack(trans))]
+    if self.output_gt:
+      _, disp, img_room, disp_room = out
+      n_hat, a = homography.transform_plane_eqns(rot_w2t[:, 0], t_w2t[:, 0],
+                                                 n_hat_w, a_w)
+      res += [n_hat, a, down(disp[:, 0]), down(disp_room[:, 0]),
+              down(disp[:, 1]), down(disp_room[:, 1]), down(img_room[:, 0]),
+              down(img_room[:, 1])]
+    return res

@@ -24,6 +24,7 @@ SOURCES = ['lsi_splat.hip', 'lsi_splat_stream.hip', 'lsi_splat_stream2.hip',
 HEADERS = [os.path.join(CSRC, 'lsi_common.h'),
            os.path.join(CSRC, 'lsi_layers.h'),
            os.path.join(CSRC, 'lsi_splat_internal.h'),
+           os.path.join(CSRC, 'lsi_bn_ws.h'),
            os.path.join(ROOT, 'include', 'lsi_hip.h')]
 
 HIPCC_FLAGS = [

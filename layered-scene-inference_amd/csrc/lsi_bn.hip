@@ -27,7 +27,7 @@
 #include <stdlib.h>
 
 #include "../../include/lsi_hip.h"
-#include "lsi_splat_internal.h"
+#include "lsi_bn_ws.h"
 
 namespace {
 

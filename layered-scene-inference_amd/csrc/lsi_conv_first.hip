@@ -37,6 +37,7 @@
 #include <string.h>
 
 #include "../../include/lsi_hip.h"
+#include "lsi_bn_ws.h"
 #include "lsi_splat_internal.h"
 
 namespace {

@@ -49,16 +49,9 @@ using namespace lsi;
 
 namespace {
 
-#ifndef LSI_BS_WPE
-#define LSI_BS_WPE 2          // waves per SIMD the register budget allows (4: spills, 1.7x slower)
-#endif
-#ifndef LSI_BS_FENCE
-#define LSI_BS_FENCE 1        // pixels gathered at a time: 1 << LSI_BS_FENCE (0 1 2)
-#endif
-#ifndef LSI_BS_T
-#define LSI_BS_T 512
-#endif
-constexpr int BS_T = LSI_BS_T;  // threads per workgroup
+constexpr int BS_WPE = 2;     // waves per SIMD the register budget allows (4: spills, 1.7x slower)
+constexpr int BS_FENCE = 1;   // pixels gathered at a time: 1 << BS_FENCE (0 1 2)
+constexpr int BS_T = 512;     // threads per workgroup
 constexpr int BS_NW = BS_T / 64;
 constexpr int BS_SEG = 256;   // source pixels per item
 
@@ -322,7 +315,7 @@ __device__ __forceinline__ void bs_run(const BSArgs& a, const float (&m)[8],
       }
       // (the gathers of the next pixels stay behind this pixel's arithmetic:
       // 16 of them in flight at once cost more registers than they hide)
-      if (((i + 1) & ((1 << LSI_BS_FENCE) - 1)) == 0 && i < 3) asm volatile("" ::: "memory");
+      if (((i + 1) & ((1 << BS_FENCE) - 1)) == 0 && i < 3) asm volatile("" ::: "memory");
     }
     const size_t po = (size_t)l * lay_px + (size_t)y * a.W + (size_t)sg * BS_SEG;
     if (sg * BS_SEG + 4 * lane < a.W) {
@@ -358,7 +351,7 @@ __device__ __forceinline__ void bs_run(const BSArgs& a, const float (&m)[8],
 }
 
 template <bool PACK, bool MASK, bool GRAD_M, bool WANT_DISP>
-__global__ __launch_bounds__(BS_T, LSI_BS_WPE) void splat_bwd_stream_kernel(BSArgs a) {
+__global__ __launch_bounds__(BS_T, BS_WPE) void splat_bwd_stream_kernel(BSArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float4* const gt = reinterpret_cast<float4*>(smem);  // [GR][Wt]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -483,8 +476,6 @@ __global__ __launch_bounds__(BS_T, LSI_BS_WPE) void splat_bwd_stream_kernel(BSAr
   }
 }
 
-bool aligned16b(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 // Descriptor-level test: what lsi_splat_bwd / lsi_splat_bwd_both ask before
@@ -504,7 +495,7 @@ bool lsi_bwd_stream_applies(const LsiSplatDesc* d, const float* tex,
     const int64_t ms[] = {d->mask_sl, d->mask_sb, d->mask_sy};
     for (int64_t v : ms)
       if (v < 0 || v > 0x7fffffffLL || v % 4) return false;
-    if (!aligned16b(mask) || !aligned16b(g_mask)) return false;
+    if (!aligned16(mask) || !aligned16(g_mask)) return false;
   }
   if (d->W % 4 != 0 || d->W < 4 || d->L < 1) return false;
   // (LSI_PACKED_RGBD: the entry points have verified the caller's statement)
@@ -513,8 +504,8 @@ bool lsi_bwd_stream_applies(const LsiSplatDesc* d, const float* tex,
   const int64_t st[] = {d->tex_sl, d->tex_sb, d->tex_sy, d->disp_sl, d->disp_sb, d->disp_sy};
   for (int64_t v : st)
     if (v < 0 || v > 0x7fffffffLL || v % 4) return false;
-  if (!aligned16b(tex) || (!pack && !aligned16b(disp)) || !aligned16b(g_tex) ||
-      !aligned16b(g_disp))
+  if (!aligned16(tex) || (!pack && !aligned16(disp)) || !aligned16(g_tex) ||
+      !aligned16(g_disp))
     return false;
   if ((long)d->B > 65535 || (long)d->L > 65535) return false;
   return true;
@@ -549,8 +540,8 @@ int lsi_bwd_stream_launch(const LsiSplatDesc* d, const float* tex,
   a.vec4 = d->Wt % 4 == 0;
   for (const BSCanvas* c : {&a.ci, &a.cc})
     if (c->g_img)
-      a.vec4 = a.vec4 && aligned16b(c->img) && aligned16b(c->wts) &&
-               aligned16b(c->g_img) && aligned16b(c->g_wts);
+      a.vec4 = a.vec4 && aligned16(c->img) && aligned16(c->wts) &&
+               aligned16(c->g_img) && aligned16(c->g_wts);
   a.B = d->B; a.H = d->H; a.W = d->W; a.Ht = d->Ht; a.Wt = d->Wt; a.L = d->L;
   a.nseg = (d->W + BS_SEG - 1) / BS_SEG;
   a.tex_sb = (int)d->tex_sb; a.tex_sl = (int)d->tex_sl; a.tex_sy = (int)d->tex_sy;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/lsi_hip.h"
+#include "lsi_common.h"
 
 struct SplatArgs {
   LsiSplatDesc d;
@@ -86,29 +87,108 @@ int lsi_sweep_launch(const SplatArgs& a, const float2* range, hipStream_t stream
 // kernel with the same plan thousands of times (lsi_splat.hip).
 int lsi_ensure_dynamic_lds(const void* fn, size_t bytes);
 
-// Batch-norm workspace layout per group, in floats (lsi_bn.hip; the convolution
-// kernels that accumulate the statistics in their epilogue write the same
-// places): [0] arrival counter (int), [ACC, ACC + 4096) the accumulators -- both
-// zero between launches --, from CONST the 2 C constants of the second pass and
-// (backward) the group's C sums of dz.
-#define LSI_BN_WS_ACC 16
-#define LSI_BN_WS_CONST (16 + 4096)
-#define LSI_BN_WS_STRIDE (16 + 4096 + 3 * 2048)
-// Statistics left by a convolution's epilogue (lsi_conv2d_*_bnstats): plain sums
-// of y and y * y in `lsi_bn_stat_slots(C)` copies of the accumulators (slot s of
-// a group: ACC + s * 2 C; thousands of workgroups adding to the same two cache
-// lines would take ~8 ns each, one after the other), folded, turned into the
-// constants and cleared by lsi_bn_relu_norm.
-// The hand-over is checked on the device: the producer's first workgroup of a
-// group leaves LSI_BN_TAG(C, groups) in the group's word [1]; lsi_bn_relu_norm
-// expects exactly that tag, the kernels that accumulate their own statistics
-// (lsi_bn_relu_fwd / _bwd) expect 0.  A kernel that finds something else writes
-// NaN constants (its output is NaN: loud in any loss), and clears accumulators
-// and tag, so that the calls after it are right again.
-#define LSI_BN_WS_TAG 1
-#define LSI_BN_TAG(C, groups) (0x5A000000 | (((groups) & 0xfff) << 12) | ((C) & 0xfff))
-static inline int lsi_bn_stat_slots(int C) {
-  int ns = 1;
-  while (ns < 32 && 2 * ns * 2 * C <= 4096) ns *= 2;
-  return ns;
+// ---- device primitives of the STREAM kernels --------------------------------
+// One definition for lsi_splat_stream.hip, its compact instance
+// lsi_splat_stream2.hip and the sweep / backward kernels: the two STREAM kernels
+// promise identical index and clamp decisions, and these are what decides them.
+// (Index-critical products below rely on lsi_common.h's fp contract(off).)
+
+// compiler-only memory barrier: orders a wave's plain LDS accesses in the code
+#define LSI_COMPILER_FENCE() asm volatile("" ::: "memory")
+#define LSI_RFL(x) __builtin_amdgcn_readfirstlane(x)
+
+namespace lsi {
+
+// (host) 16-byte alignment, what the kernels' dwordx4 accesses need
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// n / d for 0 <= n < 2^22, d > 0, rcp = fl(1/d): no integer-division sequence
+__device__ __forceinline__ int div_small(int n, int d, float rcp) {
+  int q = (int)((float)n * rcp);
+  const int r = n - q * d;
+  q += (r >= d) ? 1 : 0;
+  q -= (r < 0) ? 1 : 0;
+  return q;
 }
+
+// n-th float above / below a positive finite float
+__device__ __forceinline__ float next_up(float t) {
+  return __int_as_float(__float_as_int(t) + 1);
+}
+__device__ __forceinline__ float next_down(float t) {
+  return __int_as_float(__float_as_int(t) - 1);
+}
+
+// Smallest side weight w with fl(w * wy) > 1e-3f (sampling.py:218-222 keeps a
+// corner iff its rounded weight product exceeds 1e-3).  fp32 rounding is
+// monotone, so "w >= threshold" is EXACTLY "fl(w*wy) > 1e-3f" for every w:
+// one compare instead of a multiply and a compare in the hot loop.  +Inf when
+// no weight <= 1 qualifies.
+__device__ __forceinline__ float clamp_threshold(float wy) {
+  if (!(wy > 0.0f)) return __builtin_inff();
+  float t = div_rn(1.0e-3f, wy);
+  if (!(t < 4.0f)) return __builtin_inff();
+  for (int k = 0; k < 8; ++k) {
+    const float p = next_down(t);
+    if (p * wy > 1.0e-3f) t = p; else break;
+  }
+  for (int k = 0; k < 8; ++k) {
+    if (!(t * wy > 1.0e-3f)) t = next_up(t); else break;
+  }
+  return t;
+}
+
+// lane l-1's value by DPP wave_shr:1 (VALU, no LDS round trip); lane 0 gets 0
+__device__ __forceinline__ float lane_below(float v) {
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xf,
+                                                 0xf, true));
+}
+
+// accumulations are not index-critical: fused multiply-add
+__device__ __forceinline__ float4 f4_fma(float4 t, float4 v, float w) {
+  t.x = __fmaf_rn(v.x, w, t.x); t.y = __fmaf_rn(v.y, w, t.y);
+  t.z = __fmaf_rn(v.z, w, t.z); t.w = __fmaf_rn(v.w, w, t.w);
+  return t;
+}
+
+// Try-lock / unlock of one LDS lock word (byte address): writes 1, returns what
+// was there (0 = acquired).  Integer LDS exchanges are cheap; `ds_add_f32` is not.
+__device__ __forceinline__ void cell_try2(unsigned a0, unsigned a1, int& o0, int& o1) {
+  const int one = 1;
+  asm volatile(
+      "ds_wrxchg_rtn_b32 %0, %2, %4\n\tds_wrxchg_rtn_b32 %1, %3, %4\n\ts_waitcnt lgkmcnt(0)"
+      : "=&v"(o0), "=&v"(o1)
+      : "v"(a0), "v"(a1), "v"(one)
+      : "memory");
+}
+__device__ __forceinline__ int cell_try1(unsigned a0) {
+  int o;
+  const int one = 1;
+  asm volatile("ds_wrxchg_rtn_b32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(o) : "v"(a0), "v"(one) : "memory");
+  return o;
+}
+__device__ __forceinline__ void cell_unlock(unsigned a0) {
+  const int zero = 0;
+  asm volatile("ds_write_b32 %0, %1" : : "v"(a0), "v"(zero) : "memory");
+}
+
+// Folded fields: several lanes of a wave name the same window cell and must add
+// one after the other.  `cnt` is the wave's table of one byte per window cell
+// (four cells per word, zero between uses): ONE returning integer LDS add per
+// lane yields its rank among the lanes of its cell (a wave has 64 lanes: a byte
+// never carries into its neighbour); the caller runs rounds k = 0, 1, ... in
+// which the lanes of rank k add (distinct cells within a round), then clears
+// the words it touched.  (Round 3 elected one lane per cell and round through a
+// byte written and read back: two more LDS operations per round.)
+__device__ __forceinline__ int cell_rank(unsigned char* cnt, int cell, bool act) {
+  if (!act) return -1;
+  const unsigned sh = 8u * ((unsigned)cell & 3u);
+  const unsigned old = atomicAdd(reinterpret_cast<unsigned*>(cnt + (cell & ~3)), 1u << sh);
+  return (int)((old >> sh) & 0xffu);
+}
+__device__ __forceinline__ void cell_rank_reset(unsigned char* cnt, int cell, bool act) {
+  if (act) *reinterpret_cast<unsigned*>(cnt + (cell & ~3)) = 0u;
+}
+
+}  // namespace lsi

@@ -81,10 +81,8 @@ constexpr int SEG = 256;   // source pixels per task (64 lanes x 4)
 // (16 waves, 128 VGPRs) the pixel loop spills 8-15 registers (33-53 in the
 // general mode) and every workload measured slower: cfg3 93 vs 88 us, a 4-view
 // shard of cfg3 37 vs 33 us, fwd_both 280 vs 224 us.
-#ifndef LSI_STREAM_MAXT
-#define LSI_STREAM_MAXT 768
-#endif
-constexpr int MAXNW = LSI_STREAM_MAXT / 64;
+constexpr int STREAM_MAXT = 768;
+constexpr int MAXNW = STREAM_MAXT / 64;
 
 // Per-task table entries, filled for a whole chunk of tasks at once (one task
 // per lane: by wave 0 in the prologue, by all threads for later chunks) so that
@@ -124,8 +122,6 @@ struct alignas(16) StreamCfg {  // (kernarg offset: see epilogue_args)
                  // 0: bands own target rows and re-read one halo row pair
 };
 
-#define LSI_COMPILER_FENCE() asm volatile("" ::: "memory")
-
 typedef float f2 __attribute__((ext_vector_type(2)));
 
 // exp(a) for a packed pair; same compensated scheme as lsi::exp_accurate
@@ -141,21 +137,6 @@ __device__ __forceinline__ f2 exp_accurate2(f2 a) {
   f2 o = {__fmaf_rn(e.x, rl.x, e.x), __fmaf_rn(e.y, rl.y, e.y)};
   return o;
 }
-
-// n / d for 0 <= n < 2^22, d > 0, rcp = fl(1/d): no integer-division sequence
-__device__ __forceinline__ int div_small(int n, int d, float rcp) {
-  int q = (int)((float)n * rcp);
-  const int r = n - q * d;
-  q += (r >= d) ? 1 : 0;
-  q -= (r < 0) ? 1 : 0;
-  return q;
-}
-
-// Memory order of the arrival counter of the boundary-row exchange (see the
-// hand-off in the epilogue; DESIGN.md 4.1 for the measurement)
-#ifndef LSI_XCHG_ORDER
-#define LSI_XCHG_ORDER __ATOMIC_RELAXED
-#endif
 
 // Device-coherent accesses for the boundary-row exchange: agent-scope relaxed
 // atomics are write-through / cache-bypassing (sc1), so no L2 write-back or
@@ -190,13 +171,6 @@ __device__ __forceinline__ float4 f4_pkfma(float4 t, float4 v, float w) {
   lo = __builtin_elementwise_fma(vlo, ww, lo);
   hi = __builtin_elementwise_fma(vhi, ww, hi);
   return make_float4(lo.x, lo.y, hi.x, hi.y);
-}
-
-// accumulations are not index-critical: fused multiply-add
-__device__ __forceinline__ float4 f4_fma(float4 t, float4 v, float w) {
-  t.x = __fmaf_rn(v.x, w, t.x); t.y = __fmaf_rn(v.y, w, t.y);
-  t.z = __fmaf_rn(v.z, w, t.z); t.w = __fmaf_rn(v.w, w, t.w);
-  return t;
 }
 
 // Exact slow path for one source pixel (rare): the reference's x-axis
@@ -266,52 +240,10 @@ __device__ __forceinline__ UnitArgs unit_args() {
   return u;
 }
 
-// n-th float above / below a positive finite float
-__device__ __forceinline__ float next_up(float t) {
-  return __int_as_float(__float_as_int(t) + 1);
-}
-__device__ __forceinline__ float next_down(float t) {
-  return __int_as_float(__float_as_int(t) - 1);
-}
-
-// Smallest side weight w with fl(w * wy) > 1e-3f (sampling.py:218-222 keeps a
-// corner iff its rounded weight product exceeds 1e-3).  fp32 rounding is
-// monotone, so "w >= threshold" is EXACTLY "fl(w*wy) > 1e-3f" for every w:
-// one compare instead of a multiply and a compare in the hot loop.  +Inf when
-// no weight <= 1 qualifies.
-__device__ __forceinline__ float clamp_threshold(float wy) {
-  if (!(wy > 0.0f)) return __builtin_inff();
-  float t = div_rn(1.0e-3f, wy);
-  if (!(t < 4.0f)) return __builtin_inff();
-  for (int k = 0; k < 8; ++k) {
-    const float p = next_down(t);
-    if (p * wy > 1.0e-3f) t = p; else break;
-  }
-  for (int k = 0; k < 8; ++k) {
-    if (!(t * wy > 1.0e-3f)) t = next_up(t); else break;
-  }
-  return t;
-}
-
-// lane l-1's value by DPP wave_shr:1 (VALU, no LDS round trip); lane 0 gets 0
-__device__ __forceinline__ float lane_below(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xf,
-                                                 0xf, true));
-}
-
-#define LSI_RFL(x) __builtin_amdgcn_readfirstlane(x)
-
 // streamed inputs: every byte is read once (halo rows: twice)
-typedef float lsi_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4_stream(const float* p) {
-#ifdef LSI_STREAM_NT
-  const lsi_f4 v = __builtin_nontemporal_load(reinterpret_cast<const lsi_f4*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-#else
+__device__ __forceinline__ float4 ld4(const float* p) {
   return *reinterpret_cast<const float4*>(p);
-#endif
 }
-#define LSI_LD4(p) ld4_stream(p)
 
 // SIMPLE: the normaliser is exactly 1 and row 3 of M is (0,0,0,1) for every
 // batch element (rectified stereo): u = q0 and D = d with no division.
@@ -319,45 +251,7 @@ __device__ __forceinline__ float4 ld4_stream(const float* p) {
 // configuration) with halo / exchange bands: the code and scalar registers of
 // the other modes are gone.  MODE 0: everything, decided at run time.
 // FULL: W is a multiple of the 256-pixel segment: every lane always has pixels.
-// Try-lock / unlock of one LDS lock word (byte address): writes 1, returns what
-// was there (0 = acquired).  Integer LDS exchanges are cheap; `ds_add_f32` is not.
-__device__ __forceinline__ void cell_try2(unsigned a0, unsigned a1, int& o0, int& o1) {
-  const int one = 1;
-  asm volatile(
-      "ds_wrxchg_rtn_b32 %0, %2, %4\n\tds_wrxchg_rtn_b32 %1, %3, %4\n\ts_waitcnt lgkmcnt(0)"
-      : "=&v"(o0), "=&v"(o1)
-      : "v"(a0), "v"(a1), "v"(one)
-      : "memory");
-}
-__device__ __forceinline__ int cell_try1(unsigned a0) {
-  int o;
-  const int one = 1;
-  asm volatile("ds_wrxchg_rtn_b32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
-               : "=&v"(o) : "v"(a0), "v"(one) : "memory");
-  return o;
-}
-__device__ __forceinline__ void cell_unlock(unsigned a0) {
-  const int zero = 0;
-  asm volatile("ds_write_b32 %0, %1" : : "v"(a0), "v"(zero) : "memory");
-}
-
-// Folded fields: the lanes of a wave that name the same window cell add one
-// after the other.  `cnt`: the wave's table of one byte per window cell (four
-// cells per word, zero between uses).  One returning integer LDS add gives a
-// lane its rank among the lanes of its cell (64 lanes: a byte never carries);
-// round k is rank k's turn, then the words touched are cleared.  (As in
-// lsi_splat_stream2.hip; round 4.)
-__device__ __forceinline__ int cell_rank(unsigned char* cnt, int cell, bool act) {
-  if (!act) return -1;
-  const unsigned sh = 8u * ((unsigned)cell & 3u);
-  const unsigned old = atomicAdd(reinterpret_cast<unsigned*>(cnt + (cell & ~3)), 1u << sh);
-  return (int)((old >> sh) & 0xffu);
-}
-__device__ __forceinline__ void cell_rank_reset(unsigned char* cnt, int cell, bool act) {
-  if (act) *reinterpret_cast<unsigned*>(cnt + (cell & ~3)) = 0u;
-}
-
-template <int LAYOUT, bool SIMPLE, int MODE, bool FULL, int MAXT = LSI_STREAM_MAXT>  // LAYOUT 0: channels-last, 1: planar
+template <int LAYOUT, bool SIMPLE, int MODE, bool FULL, int MAXT = STREAM_MAXT>  // LAYOUT 0: channels-last, 1: planar
 __global__ __launch_bounds__(MAXT) void splat_stream_kernel(SplatArgs a,
                                                            StreamCfg cfg) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -572,12 +466,8 @@ __global__ __launch_bounds__(MAXT) void splat_stream_kernel(SplatArgs a,
         // tg / per_row etc. without integer divisions (tg < 2^20: exact)
         const int yi = (int)(((float)tg + 0.5f) * inv_per_row);
         const int rem = tg - yi * per_row;
-#ifdef LSI_NO_INTERLEAVE
-        const int yr = yi;
-#else
         const int y5 = (int)(((float)yi + 0.5f) * 0.2f);
         const int yr = (yi - 5 * y5) * q5 + y5;
-#endif
         const int sg = (int)(((float)rem + 0.5f) * inv_ngrp);
         const int grp = rem - sg * NGRP;
         const int y = ylo + yr;
@@ -767,16 +657,16 @@ __global__ __launch_bounds__(MAXT) void splat_stream_kernel(SplatArgs a,
       // has the same number of loads in flight, and the compiler can wait for
       // one register set while the other one's loads stay outstanding.
       auto load_layer = [&](PxData& o) {
-        o.d4 = LSI_LD4(p_disp);
+        o.d4 = ld4(p_disp);
         if (LAYOUT == 0) {
-          o.t0 = LSI_LD4(p_tex); o.t1 = LSI_LD4(p_tex + 4);
-          o.t2 = LSI_LD4(p_tex + 8);
+          o.t0 = ld4(p_tex); o.t1 = ld4(p_tex + 4);
+          o.t2 = ld4(p_tex + 8);
         } else {
-          o.t0 = LSI_LD4(p_tex);
-          o.t1 = LSI_LD4(p_tex + tex_sc);
-          o.t2 = LSI_LD4(p_tex + 2 * tex_sc);
+          o.t0 = ld4(p_tex);
+          o.t1 = ld4(p_tex + tex_sc);
+          o.t2 = ld4(p_tex + 2 * tex_sc);
         }
-        if (has_mask) o.m4 = LSI_LD4(p_mask);
+        if (has_mask) o.m4 = ld4(p_mask);
         p_disp += disp_sl;
         p_tex += tex_sl;
         if (has_mask) p_mask += mask_sl;
@@ -1427,42 +1317,14 @@ __global__ __launch_bounds__(MAXT) void splat_stream_kernel(SplatArgs a,
               }
             }
           } else {
-#ifndef LSI_MERGE_BATCHED
-          for (int c = lane; c < t_wwin; c += 64) {
-            float4* wc = rb + (c >> 1) + (c & 1) * WHS;
-            const float4 v = *wc;
-            *wc = make_float4(0.f, 0.f, 0.f, 0.f);  // ready for the next task
-            const bool inside = (unsigned)(t_wlo + c) < (unsigned)Wt;
-            if (use_a && inside) trow[c] = f4_fma(trow[c], v, wy0);
-            if (use_b && inside) trow[Wt + c] = f4_fma(trow[Wt + c], v, wy1);
-          }
-#else
-          // two cells per lane and round: all reads first, then all writes
-          // (one LDS round trip for six accesses)
-          for (int c0 = 0; c0 < t_wwin; c0 += 128) {
-            const int ca = c0 + lane, cb = ca + 64;
-            const bool va = ca < t_wwin, vb = cb < t_wwin;
-            float4* wa = rb + (ca >> 1) + (ca & 1) * WHS;
-            float4* wb = rb + (cb >> 1) + (cb & 1) * WHS;
-            const bool ia = va && (unsigned)(t_wlo + ca) < (unsigned)Wt;
-            const bool ib = vb && (unsigned)(t_wlo + cb) < (unsigned)Wt;
-            const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            float4 xa = z4, xb = z4, a0 = z4, a1 = z4, b0 = z4, b1 = z4;
-            if (va) xa = *wa;
-            if (vb) xb = *wb;
-            if (use_a && ia) a0 = trow[ca];
-            if (use_b && ia) a1 = trow[Wt + ca];
-            if (use_a && ib) b0 = trow[cb];
-            if (use_b && ib) b1 = trow[Wt + cb];
-            LSI_COMPILER_FENCE();
-            if (va) *wa = z4;  // ready for the next task
-            if (vb) *wb = z4;
-            if (use_a && ia) trow[ca] = f4_fma(a0, xa, wy0);
-            if (use_b && ia) trow[Wt + ca] = f4_fma(a1, xa, wy1);
-            if (use_a && ib) trow[cb] = f4_fma(b0, xb, wy0);
-            if (use_b && ib) trow[Wt + cb] = f4_fma(b1, xb, wy1);
-          }
-#endif
+            for (int c = lane; c < t_wwin; c += 64) {
+              float4* wc = rb + (c >> 1) + (c & 1) * WHS;
+              const float4 v = *wc;
+              *wc = make_float4(0.f, 0.f, 0.f, 0.f);  // ready for the next task
+              const bool inside = (unsigned)(t_wlo + c) < (unsigned)Wt;
+              if (use_a && inside) trow[c] = f4_fma(trow[c], v, wy0);
+              if (use_b && inside) trow[Wt + c] = f4_fma(trow[Wt + c], v, wy1);
+            }
           }
           if (ordered) {
             pass_turn(slot);
@@ -1556,19 +1418,22 @@ __global__ __launch_bounds__(MAXT) void splat_stream_kernel(SplatArgs a,
     LSI_TSTAMP();
     if (top_shared || bot_shared) {
       // the partial rows are performed (write-through stores, waited for by
-      // every thread) before one thread announces this band on each boundary
+      // every thread) before one thread announces this band on each boundary.
+      // The counter is relaxed: the waits and barriers around it are the
+      // ordering, and acq_rel would have the compiler write back and invalidate
+      // the XCD's L2 around it, +11 us per launch (measured: DESIGN.md 4.1)
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __builtin_amdgcn_s_waitcnt(0);
       __syncthreads();
       if (tid == 0) {
         ctl[4] = top_shared
                      ? __hip_atomic_fetch_add(&ea.xcount[xb + band], 1,
-                                              LSI_XCHG_ORDER,
+                                              __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_AGENT)
                      : 0;
         ctl[5] = bot_shared
                      ? __hip_atomic_fetch_add(&ea.xcount[xb + band + 1], 1,
-                                              LSI_XCHG_ORDER,
+                                              __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_AGENT)
                      : 0;
       }
@@ -1642,8 +1507,6 @@ int tex_layout(const LsiSplatDesc* d) {
   if (d->tex_sx == 1 && d->tex_sc % 4 == 0) return 1;
   return -1;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

@@ -85,17 +85,6 @@ struct S2Args {
   unsigned* route_ctr;
 };
 
-#define S2_FENCE() asm volatile("" ::: "memory")
-#define S2_RFL(x) __builtin_amdgcn_readfirstlane(x)
-
-__device__ __forceinline__ int s2_div_small(int n, int d, float rcp) {
-  int q = (int)((float)n * rcp);
-  const int r = n - q * d;
-  q += (r >= d) ? 1 : 0;
-  q -= (r < 0) ? 1 : 0;
-  return q;
-}
-
 // Ticket order of a band with `nsrc` source rows (see Unit above, and the row
 // interleave: consecutive tickets go to source rows a fifth of the band apart,
 // so that the units in flight merge into different tile rows; short bands keep
@@ -115,9 +104,7 @@ __host__ __device__ __forceinline__ int s2_rows_padded(int nsrc, int ilv, int hf
   const int nin = nsrc - edge;
   return edge + (ilv ? (nin + 4) / 5 * 5 : nin);
 }
-// `wg`: a number that differs between workgroups (S2X_STAGGER builds: every
-// workgroup walks its units from another starting point)
-__device__ __forceinline__ BandOrder s2_band_order(const S2Args& a, int nsrc, int wg = 0) {
+__device__ __forceinline__ BandOrder s2_band_order(const S2Args& a, int nsrc) {
   BandOrder o;
   o.nsrc = nsrc;
   o.hf = (a.hf && nsrc >= 6) ? 1 : 0;
@@ -130,11 +117,7 @@ __device__ __forceinline__ BandOrder s2_band_order(const S2Args& a, int nsrc, in
   o.lsub = max(a.lsub, 1);
   o.ntask = o.nfull + o.nsplit * ((a.L + o.lsub - 1) / o.lsub);
   o.inv_nsplit = __builtin_amdgcn_rcpf((float)max(o.nsplit, 1));
-#ifdef S2X_STAGGER
-  o.rot = o.nfull > 0 ? (int)((unsigned)wg % (unsigned)o.nfull) : 0;
-#else
-  o.rot = 0;
-#endif
+  o.rot = 0;  // every band walks its whole units from the first (staggered starts lost)
   return o;
 }
 __device__ __forceinline__ Unit s2_unit_of(const S2Args& a, const BandOrder& o, int tg) {
@@ -146,7 +129,7 @@ __device__ __forceinline__ Unit s2_unit_of(const S2Args& a, const BandOrder& o, 
     return un;
   }
   const int j = tg - o.nfull;
-  const int part = s2_div_small(j, o.nsplit, o.inv_nsplit);
+  const int part = div_small(j, o.nsplit, o.inv_nsplit);
   un.u = o.nfull + (j - part * o.nsplit);
   un.l0 = part * o.lsub;
   un.nl = min(o.lsub, a.L - un.l0);
@@ -190,56 +173,6 @@ __device__ __forceinline__ Aim s2_own_unit(const S2Args& a, const BandOrder& o, 
   return r;
 }
 
-__device__ __forceinline__ float s2_next_up(float t) {
-  return __int_as_float(__float_as_int(t) + 1);
-}
-__device__ __forceinline__ float s2_next_down(float t) {
-  return __int_as_float(__float_as_int(t) - 1);
-}
-// Smallest side weight w with fl(w * wy) > 1e-3f (sampling.py:218-222); see
-// clamp_threshold in lsi_splat_stream.hip.
-__device__ __forceinline__ float s2_clamp_threshold(float wy) {
-  if (!(wy > 0.0f)) return __builtin_inff();
-  float t = div_rn(1.0e-3f, wy);
-  if (!(t < 4.0f)) return __builtin_inff();
-  for (int k = 0; k < 8; ++k) {
-    const float p = s2_next_down(t);
-    if (p * wy > 1.0e-3f) t = p; else break;
-  }
-  for (int k = 0; k < 8; ++k) {
-    if (!(t * wy > 1.0e-3f)) t = s2_next_up(t); else break;
-  }
-  return t;
-}
-__device__ __forceinline__ float s2_lane_below(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xf,
-                                                 0xf, true));
-}
-__device__ __forceinline__ float4 s2_fma4(float4 t, float4 v, float w) {
-  t.x = __fmaf_rn(v.x, w, t.x); t.y = __fmaf_rn(v.y, w, t.y);
-  t.z = __fmaf_rn(v.z, w, t.z); t.w = __fmaf_rn(v.w, w, t.w);
-  return t;
-}
-__device__ __forceinline__ int s2_try1(unsigned a0) {
-  int o;
-  const int one = 1;
-  asm volatile("ds_wrxchg_rtn_b32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
-               : "=&v"(o) : "v"(a0), "v"(one) : "memory");
-  return o;
-}
-__device__ __forceinline__ void s2_try2(unsigned a0, unsigned a1, int& o0, int& o1) {
-  const int one = 1;
-  asm volatile(
-      "ds_wrxchg_rtn_b32 %0, %2, %4\n\tds_wrxchg_rtn_b32 %1, %3, %4\n\ts_waitcnt lgkmcnt(0)"
-      : "=&v"(o0), "=&v"(o1)
-      : "v"(a0), "v"(a1), "v"(one)
-      : "memory");
-}
-__device__ __forceinline__ void s2_unlock(unsigned a0) {
-  const int zero = 0;
-  asm volatile("ds_write_b32 %0, %1" : : "v"(a0), "v"(zero) : "memory");
-}
-
 // Row locks (workgroup scope).
 __device__ __forceinline__ void s2_lock_row(int* locks, int r, int lane) {
   if (lane == 0) {
@@ -275,13 +208,13 @@ __device__ __forceinline__ void s2_apply_queue(float4* tile4, unsigned clk_addr,
       const float4 v = pred ? qv[i] : make_float4(0.f, 0.f, 0.f, 0.f);
       const unsigned la = clk_addr + (unsigned)tcell * 4u;
       while (__ballot(pred) != 0ull) {
-        if (pred && s2_try1(la) == 0) {
+        if (pred && cell_try1(la) == 0) {
           float4* e = tile4 + tcell;
           float4 t = *e;
           t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
           *e = t;
-          S2_FENCE();
-          s2_unlock(la);
+          LSI_COMPILER_FENCE();
+          cell_unlock(la);
           pred = false;
         }
       }
@@ -326,12 +259,12 @@ __device__ __noinline__ void s2_flush_queue(unsigned tile_off, unsigned locks_of
       for (int k = 0; k < 4; ++k) v[k] = pred ? qv[4 * i + k] : 0.0f;
       const unsigned la = clk_off + (unsigned)tcell * 4u;
       while (__ballot(pred) != 0ull) {
-        if (pred && s2_try1(la) == 0) {
+        if (pred && cell_try1(la) == 0) {
           LdsF* e = tile + 4 * tcell;
 #pragma unroll
           for (int k = 0; k < 4; ++k) e[k] = e[k] + v[k];
-          S2_FENCE();
-          s2_unlock(la);
+          LSI_COMPILER_FENCE();
+          cell_unlock(la);
           pred = false;
         }
       }
@@ -371,24 +304,6 @@ __device__ __noinline__ void s2_flush_queue(unsigned tile_off, unsigned locks_of
   if (rowA >= 0) unlock(rowA);
 }
 
-// Folded fields: several lanes of a wave name the same window cell and must add
-// one after the other.  `cnt` is the wave's table of one byte per window cell
-// (four cells per word, zero between uses): ONE returning integer LDS add per
-// lane yields its rank among the lanes of its cell (a wave has 64 lanes: a byte
-// never carries into its neighbour); the caller runs rounds k = 0, 1, ... in
-// which the lanes of rank k add (distinct cells within a round), then clears
-// the words it touched.  (Round 3 elected one lane per cell and round through a
-// byte written and read back: two more LDS operations per round.)
-__device__ __forceinline__ int s2_cell_rank(unsigned char* cnt, int cell, bool act) {
-  if (!act) return -1;
-  const unsigned sh = 8u * ((unsigned)cell & 3u);
-  const unsigned old = atomicAdd(reinterpret_cast<unsigned*>(cnt + (cell & ~3)), 1u << sh);
-  return (int)((old >> sh) & 0xffu);
-}
-__device__ __forceinline__ void s2_cell_rank_reset(unsigned char* cnt, int cell, bool act) {
-  if (act) *reinterpret_cast<unsigned*>(cnt + (cell & ~3)) = 0u;
-}
-
 // 16-byte output store by epilogue mode (S2Args.ep): 1 plain, 2 write-through
 // (sc1), 3 non-temporal (what the launcher picks: see lsi_common.h)
 __device__ __forceinline__ void s2_store4(float* p, float x, float y, float z, float w,
@@ -404,11 +319,6 @@ __device__ __forceinline__ void s2_store4(float* p, float x, float y, float z, f
   }
 }
 struct Px { float4 d4, t0, t1, t2; };
-typedef float s2_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 s2_ld_nt(const float* p) {
-  const s2_f4 v = __builtin_nontemporal_load(reinterpret_cast<const s2_f4*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
 
 // BOTH: lsi_splat_fwd_both -- the per-layer views AND the composed one from one
 // sweep: one tile per layer in LDS, every item (one layer of a unit) merges its
@@ -423,7 +333,7 @@ template <int NSETS, bool CELL, int MAXT, bool BOTH = false, bool PACK = false,
 __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = S2_RFL(tid >> 6);
+  const int wave = LSI_RFL(tid >> 6);
   const int T = blockDim.x, NW = T >> 6;
   const int R = a.R, WMAX = a.wmax;
   const int Wt = a.Wt, Ht = a.Ht, H = a.H;
@@ -436,12 +346,8 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
     const unsigned xcd = lin & 7u, q = nwg >> 3, r8 = nwg & 7u;
     const unsigned base =
         xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q;
-#ifdef S2X_ROUNDROBIN  // experiment: workgroup i keeps id i (XCD i % 8: an image's bands on all XCDs)
-    const unsigned id = lin + 0 * base;
-#else
     const unsigned id = base + (lin >> 3);
-#endif
-    b = s2_div_small((int)id, (int)gridDim.x, a.inv_gx);
+    b = div_small((int)id, (int)gridDim.x, a.inv_gx);
     band = (int)id - b * (int)gridDim.x;
   }
   // band = target rows [row0, row0 + rows); it reads every source row that
@@ -504,22 +410,17 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
     p_disp = g_disp0 + (long)l0 * disp_sl + (long)y * a.disp_sy + px;
     p_tex = g_tex0 + (long)l0 * tex_sl + (long)y * a.tex_sy + (PACK ? 4 : 3) * px;
   };
-#ifdef S2X_NT  // experiment: streamed inputs loaded with the non-temporal policy
-#define S2_LD(p) s2_ld_nt(p)
-#else
-#define S2_LD(p) (*reinterpret_cast<const float4*>(p))
-#endif
   auto load_layer = [&](Px& o) {
     if (PACK) {  // d4, t0, t1, t2 = the lane's pixels 0 .. 3 as (r, g, b, d)
-      o.d4 = S2_LD(p_tex);
-      o.t0 = S2_LD(p_tex + 4);
-      o.t1 = S2_LD(p_tex + 8);
-      o.t2 = S2_LD(p_tex + 12);
+      o.d4 = *reinterpret_cast<const float4*>(p_tex);
+      o.t0 = *reinterpret_cast<const float4*>(p_tex + 4);
+      o.t1 = *reinterpret_cast<const float4*>(p_tex + 8);
+      o.t2 = *reinterpret_cast<const float4*>(p_tex + 12);
     } else {
-      o.d4 = S2_LD(p_disp);
-      o.t0 = S2_LD(p_tex);
-      o.t1 = S2_LD(p_tex + 4);
-      o.t2 = S2_LD(p_tex + 8);
+      o.d4 = *reinterpret_cast<const float4*>(p_disp);
+      o.t0 = *reinterpret_cast<const float4*>(p_tex);
+      o.t1 = *reinterpret_cast<const float4*>(p_tex + 4);
+      o.t2 = *reinterpret_cast<const float4*>(p_tex + 8);
       p_disp += disp_sl;
     }
     p_tex += tex_sl;
@@ -538,7 +439,7 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
     const float inv_s = __builtin_amdgcn_rcpf(a.s);
     const int ylo_g = (int)fminf(fmaxf(ceilf(((float)k_lo + 0.5f) * inv_s - 0.5f), 0.0f), (float)H);
     const int yhi_g = (int)fminf(fmaxf(ceilf(((float)k_hi + 1.5f) * inv_s - 0.5f), 0.0f), (float)H) - 1;
-    const BandOrder bg = s2_band_order(a, max(0, yhi_g - ylo_g + 1), b * 29 + band * 13);
+    const BandOrder bg = s2_band_order(a, max(0, yhi_g - ylo_g + 1));
     g_aim = s2_own_unit(a, bg, wave);
     g_y = ylo_g + g_aim.yr;
     if (g_aim.nl) aim(g_y, g_aim.sg, g_aim.l0);
@@ -614,7 +515,7 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
       if (good) { y_lo = lo; y_hi = hi; ranged = true; }
     }
   }
-  if (!S2_RFL(ranged ? 1 : 0)) {  // maps too flat / decreasing: scan, per wave
+  if (!LSI_RFL(ranged ? 1 : 0)) {  // maps too flat / decreasing: scan, per wave
     int lo = H, hi = -1;
     for (int y = lane; y < H; y += 64) {
       const float Y = row_Y(y);
@@ -628,9 +529,9 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
     }
     y_lo = lo; y_hi = hi;
   }
-  y_lo = S2_RFL(y_lo); y_hi = S2_RFL(y_hi);
+  y_lo = LSI_RFL(y_lo); y_hi = LSI_RFL(y_hi);
   const int nsrc = (y_hi >= y_lo) ? (y_hi - y_lo + 1) : 0;
-  const BandOrder bo = s2_band_order(a, nsrc, b * 29 + band * 13);
+  const BandOrder bo = s2_band_order(a, nsrc);
   const int ntask = bo.ntask;
   // the table holds a.cap tickets: one chunk unless the band has more source
   // rows than the planner assumed (it does not see the matrices)
@@ -656,18 +557,18 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
     }
   };
   auto issue = [&](Px& dst) -> int {
-    if (S2_RFL(ld_left) == 0 && S2_RFL(ld_done) == 0) {
+    if (LSI_RFL(ld_left) == 0 && LSI_RFL(ld_done) == 0) {
       table_ready();
       int t = 0;
       if (lane == 0) t = atomicAdd(&ctl[0], 1);
-      const int sl = S2_RFL(t);
+      const int sl = LSI_RFL(t);
       if (sl >= nchunk) {
         ld_done = 1;
       } else {
         const Task ta = task[sl];
         // rows masked at the border add nothing: not even started
-        if (S2_RFL((ta.wy0 != 0.0f || ta.wy1 != 0.0f) ? 1 : 0)) {
-          const int yx = S2_RFL(taskx[sl].yx);
+        if (LSI_RFL((ta.wy0 != 0.0f || ta.wy1 != 0.0f) ? 1 : 0)) {
+          const int yx = LSI_RFL(taskx[sl].yx);
           const Unit un = s2_unit_of(a, bo, chunk0 + sl);
           aim(yx & 0xffff, yx >> 16, un.l0);
           ld_left = un.nl; ld_slot = sl; ld_first = 1 << 20;
@@ -675,15 +576,15 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
       }
     }
     int tag = -1;
-    const bool have = S2_RFL(ld_left) != 0;
+    const bool have = LSI_RFL(ld_left) != 0;
     if (!have) { p_disp = g_disp; p_tex = g_tex; }  // harmless re-read
     load_layer(dst);
     if (have) {
-      ld_left = S2_RFL(ld_left) - 1;
+      ld_left = LSI_RFL(ld_left) - 1;
       tag = ld_slot | ld_first | (ld_left == 0 ? (1 << 21) : 0);
       ld_first = 0;
     }
-    return S2_RFL(tag);
+    return LSI_RFL(tag);
   };
 
   // ---- the exact first unit: keep the loads in flight, or aim again ---------
@@ -692,7 +593,7 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
     const int r_y = y_lo + r.yr;
     const bool same = r.nl == g_aim.nl &&
                       (r.nl == 0 || (r_y == g_y && r.sg == g_aim.sg && r.l0 == g_aim.l0));
-    if (!S2_RFL(same ? 1 : 0) && r.nl) {
+    if (!LSI_RFL(same ? 1 : 0) && r.nl) {
       aim(r_y, r.sg, r.l0);
 #pragma unroll
       for (int k = 0; k < NSETS; ++k) {
@@ -726,7 +627,7 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
       tx.yx = y | (sg << 16);
       const float wymin =
           (ay.w0 == 0.f) ? ay.w1 : ((ay.w1 == 0.f) ? ay.w0 : fminf(ay.w0, ay.w1));
-      tx.tmin = s2_clamp_threshold(wymin);
+      tx.tmin = clamp_threshold(wymin);
       // window hint: cells reachable for d in [0, max_disp] on the segment
       const int xs = sg * SEG;
       const float py = (float)y + 0.5f;
@@ -799,9 +700,9 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
   unsigned n_items = 0u;
 #ifdef S2X_STAMPS
   unsigned route_n[4] = {0u, 0u, 0u, 0u};  // items by route: A, B, B' (folded), C (general)
-#define S2_ROUTE(k) do { route_n[k] += 1u; n_items = S2_RFL(n_items + (((k) >= 2) ? 0x10001u : 1u)); } while (0)
+#define S2_ROUTE(k) do { route_n[k] += 1u; n_items = LSI_RFL(n_items + (((k) >= 2) ? 0x10001u : 1u)); } while (0)
 #else
-#define S2_ROUTE(k) (n_items = S2_RFL(n_items + (((k) >= 2) ? 0x10001u : 1u)))
+#define S2_ROUTE(k) (n_items = LSI_RFL(n_items + (((k) >= 2) ? 0x10001u : 1u)))
 #endif
   // merge: the lane's window slots (cells lane, lane + 64, ...)
   const int mslot = (lane >> 1) + (lane & 1) * WHS;
@@ -860,10 +761,10 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
       t_lay = BOTH ? s2_unit_of(a, bo, chunk0 + slot).l0 * R : 0;
       const Task ta = task[slot];
       const TaskX tx = taskx[slot];
-      t_row0 = S2_RFL(ta.row0);
-      const int t_win = S2_RFL(ta.win);
+      t_row0 = LSI_RFL(ta.row0);
+      const int t_win = LSI_RFL(ta.win);
       t_wlo = (t_win & 0xffff) - 32768; t_wwin = t_win >> 16;
-      const int yx = S2_RFL(tx.yx);
+      const int yx = LSI_RFL(tx.yx);
       const int y = yx & 0xffff, xs = (yx >> 16) * SEG;
       if (RAGGED) lane_dead = xs + 4 * lane >= a.W;
       tmin = tx.tmin;
@@ -879,15 +780,15 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
       wymax = fmaxf(wy0, wy1);
       wlo_f = (float)t_wlo;
       const int rmax = t_row0 + ((wy1 > wy0) ? 1 : 0);
-      has_max = S2_RFL(((wymax != wymin) && rmax >= 0 && rmax < rows) ? 1 : 0);
-      rmax_row = S2_RFL(rmax);
+      has_max = LSI_RFL(((wymax != wymin) && rmax >= 0 && rmax < rows) ? 1 : 0);
+      rmax_row = LSI_RFL(rmax);
       wspan = (unsigned)max(t_wwin - 2, 0);
       win_ok = t_wwin >= 2 ? 1 : 0;
       wspanA = (unsigned)max(t_wwin - 4, 0);
-      fast_ok = S2_RFL((win_ok && tmin <= 0.5f) ? 1 : 0);
-      fastA_ok = S2_RFL((t_wwin >= 4 && tmin <= 0.5f) ? 1 : 0);
-      use_a = S2_RFL((wy0 != 0.f && t_row0 >= 0 && t_row0 < rows) ? 1 : 0);
-      use_b = S2_RFL((wy1 != 0.f && t_row0 + 1 >= 0 && t_row0 + 1 < rows) ? 1 : 0);
+      fast_ok = LSI_RFL((win_ok && tmin <= 0.5f) ? 1 : 0);
+      fastA_ok = LSI_RFL((t_wwin >= 4 && tmin <= 0.5f) ? 1 : 0);
+      use_a = LSI_RFL((wy0 != 0.f && t_row0 >= 0 && t_row0 < rows) ? 1 : 0);
+      use_b = LSI_RFL((wy1 != 0.f && t_row0 + 1 >= 0 && t_row0 + 1 < rows) ? 1 : 0);
     }
     float x0v[4], w0v[4], w1v[4];
     float4 Vv[4];  // route A: the lane's 4 cell sums; else V of its 4 pixels
@@ -937,12 +838,7 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
         // helpers.py:180-193 with D = d: exp((clip(d/max,0,1) - 0.5)*scale)
         const float dc = __builtin_amdgcn_fmed3f(dv[i], 0.0f, max_disp);
         const float e = __builtin_amdgcn_exp2f(__fmaf_rn(dc, zA, zB));
-#ifdef S2X_NOEXP
-        pwv[i] = dc;
-        (void)e;
-#else
         pwv[i] = dv[i] > 0.0f ? e : 0.0f;  // (NaN disparity -> weight 0)
-#endif
         x0v[i] = x0; w0v[i] = gx; w1v[i] = fx;
       }
       // ---- route A: the lane's 4 pixels land in cells cl0 .. cl0 + 3 --------
@@ -951,21 +847,13 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
       dl[0] = 0;
       unsigned long long regA =
           __ballot((unsigned)cl0 <= wspanA) &
-          (__ballot(x0v[0] > s2_lane_below(x0v[0])) | 1ull);
+          (__ballot(x0v[0] > lane_below(x0v[0])) | 1ull);
 #pragma unroll
       for (int i = 1; i < 4; ++i) {
         dl[i] = (int)(x0v[i] - x0v[0]);
         regA &= __ballot((unsigned)dl[i] <= 2u);
       }
-      routeA = S2_RFL(((regA == ~0ull) && fastA_ok) ? 1 : 0);
-#ifdef S2X_NOSUMS
-      if (routeA) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          Vv[k] = make_float4(tx_[3 * k] * pwv[k] * w0v[k], tx_[3 * k + 1] * pwv[k] * w1v[k],
-                              tx_[3 * k + 2] * pwv[k], pwv[k]);
-      } else
-#endif
+      routeA = LSI_RFL(((regA == ~0ull) && fastA_ok) ? 1 : 0);
       if (routeA) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) Vv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -975,11 +863,7 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
           const float4 V = make_float4(tx_[3 * i] * pwv[i], tx_[3 * i + 1] * pwv[i],
                                        tx_[3 * i + 2] * pwv[i], pwv[i]);
           // clamp (at most the smaller side: tmin <= 0.5 on this route)
-#ifdef S2X_NOCLAMP
-          if (false) {
-#else
           if (__ballot(!(fminf(w0, w1) >= tmin)) != 0ull) {
-#endif
             const bool c0 = !(w0 >= tmin), c1 = !(w1 >= tmin);
             if (has_max) {
               const float kq = (c0 ? w0 : w1) * wymax;
@@ -1000,10 +884,10 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
             const float a1 = e1 ? w0 : (e0 ? w1 : 0.0f);
             const float a2 = e2 ? w0 : (e1 ? w1 : 0.0f);
             const float a3 = e2 ? w1 : 0.0f;
-            Vv[0] = s2_fma4(Vv[0], V, a0);
-            Vv[1] = s2_fma4(Vv[1], V, a1);
-            Vv[2] = s2_fma4(Vv[2], V, a2);
-            Vv[3] = s2_fma4(Vv[3], V, a3);
+            Vv[0] = f4_fma(Vv[0], V, a0);
+            Vv[1] = f4_fma(Vv[1], V, a1);
+            Vv[2] = f4_fma(Vv[2], V, a2);
+            Vv[3] = f4_fma(Vv[3], V, a3);
           }
         }
       } else {
@@ -1027,24 +911,15 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
         float4* ce = rb + hlf + par * WHS;              // cell cl0 (and cl0 + 2)
         float4* co = rb + hlf + par + (1 - par) * WHS;  // cell cl0 + 1 (and + 3)
         float4 t;
-#ifndef S2X_NOWIN
         t = ce[0]; t.x += Vv[0].x; t.y += Vv[0].y; t.z += Vv[0].z; t.w += Vv[0].w; ce[0] = t;
-        S2_FENCE();
+        LSI_COMPILER_FENCE();
         t = co[0]; t.x += Vv[1].x; t.y += Vv[1].y; t.z += Vv[1].z; t.w += Vv[1].w; co[0] = t;
-        S2_FENCE();
+        LSI_COMPILER_FENCE();
         t = ce[1]; t.x += Vv[2].x; t.y += Vv[2].y; t.z += Vv[2].z; t.w += Vv[2].w; ce[1] = t;
-        S2_FENCE();
+        LSI_COMPILER_FENCE();
         t = co[1]; t.x += Vv[3].x; t.y += Vv[3].y; t.z += Vv[3].z; t.w += Vv[3].w; co[1] = t;
-#else
-        t = ce[0]; t.x += Vv[0].x + Vv[1].x + Vv[2].x + Vv[3].x; t.y += Vv[0].y + Vv[1].y + Vv[2].y + Vv[3].y;
-        t.z += Vv[0].z + Vv[1].z + Vv[2].z + Vv[3].z; t.w += Vv[0].w + Vv[1].w + Vv[2].w + Vv[3].w;
-        if (t.x == 123.456f) ce[0] = t;
-        (void)co;
-#endif
-        S2_FENCE();
-      }
-#ifndef S2X_ONLYA
-      else {
+        LSI_COMPILER_FENCE();
+      } else {
         // every pixel inside the window (but not route A's pattern: folded or
         // steep disparity fields): per pixel, unrolled -- route B when floor(X)
         // increases strictly across the wave (distinct cells), else B': the
@@ -1055,9 +930,9 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
         for (int i = 0; i < 4; ++i) {
           clv[i] = (int)(x0v[i] - wlo_f);
           inwin &= __ballot((unsigned)clv[i] <= wspan);
-          regular &= __ballot(x0v[i] > s2_lane_below(x0v[i])) | 1ull;
+          regular &= __ballot(x0v[i] > lane_below(x0v[i])) | 1ull;
         }
-        if (S2_RFL((inwin == ~0ull && fast_ok) ? 1 : 0)) {
+        if (LSI_RFL((inwin == ~0ull && fast_ok) ? 1 : 0)) {
           const bool fold = regular != ~0ull;
           S2_ROUTE(fold ? 2 : 1);
 #pragma unroll
@@ -1080,23 +955,23 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
             float4* cell = rb + (clv[i] >> 1) + (clv[i] & 1) * WHS;
             float4* cell1 = rb + ((clv[i] + 1) >> 1) + ((clv[i] + 1) & 1) * WHS;
             if (!fold) {
-              *cell = s2_fma4(*cell, V, w0);
-              S2_FENCE();
-              *cell1 = s2_fma4(*cell1, V, w1);
-              S2_FENCE();
+              *cell = f4_fma(*cell, V, w0);
+              LSI_COMPILER_FENCE();
+              *cell1 = f4_fma(*cell1, V, w1);
+              LSI_COMPILER_FENCE();
             } else {
               // the lanes of a cell take turns: one returning LDS add gives every
-              // lane its rank among them (s2_cell_rank), round k is rank k's
-              const int rank = s2_cell_rank(sc, clv[i], true);
+              // lane its rank among them (cell_rank), round k is rank k's
+              const int rank = cell_rank(sc, clv[i], true);
               for (int k = 0; __ballot(rank >= k) != 0ull; ++k) {
                 if (rank == k) {
-                  *cell = s2_fma4(*cell, V, w0);
-                  S2_FENCE();
-                  *cell1 = s2_fma4(*cell1, V, w1);
+                  *cell = f4_fma(*cell, V, w0);
+                  LSI_COMPILER_FENCE();
+                  *cell1 = f4_fma(*cell1, V, w1);
                 }
-                S2_FENCE();
+                LSI_COMPILER_FENCE();
               }
-              s2_cell_rank_reset(sc, clv[i], true);
+              cell_rank_reset(sc, clv[i], true);
             }
           }
         } else {
@@ -1122,7 +997,7 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
           const bool inw = ((unsigned)cl <= wspan) && win_ok;
           const unsigned long long inw_mask = __ballot(inw);
           const unsigned long long mono_ok =
-              __ballot(x0 > s2_lane_below(x0)) | 1ull;
+              __ballot(x0 > lane_below(x0)) | 1ull;
           // clamped sides: !(p > 1e-3) is also true for NaN weights
           const bool c0 = !(w0 * wymin > 1.0e-3f);
           const bool c1 = !(w1 * wymin > 1.0e-3f);
@@ -1144,35 +1019,32 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
           float4* cell1 = rb + ((cl + 1) >> 1) + ((cl + 1) & 1) * WHS;
           if (mono_ok == ~0ull) {
             if (inw) {
-              *cell = s2_fma4(*cell, V, w0);
-              S2_FENCE();
-              *cell1 = s2_fma4(*cell1, V, w1);
+              *cell = f4_fma(*cell, V, w0);
+              LSI_COMPILER_FENCE();
+              *cell1 = f4_fma(*cell1, V, w1);
             }
-            S2_FENCE();
+            LSI_COMPILER_FENCE();
           } else if (inw_mask != 0ull) {
-            const int rank = s2_cell_rank(sc, cl, inw);
+            const int rank = cell_rank(sc, cl, inw);
             for (int k = 0; __ballot(rank >= k) != 0ull; ++k) {
               if (rank == k) {
-                *cell = s2_fma4(*cell, V, w0);
-                S2_FENCE();
-                *cell1 = s2_fma4(*cell1, V, w1);
+                *cell = f4_fma(*cell, V, w0);
+                LSI_COMPILER_FENCE();
+                *cell1 = f4_fma(*cell1, V, w1);
               }
-              S2_FENCE();
+              LSI_COMPILER_FENCE();
             }
-            s2_cell_rank_reset(sc, cl, inw);
+            cell_rank_reset(sc, cl, inw);
           }
         }
         }
       }
-#endif
       if (BOTH || (tg_ & (1 << 21))) {
         // ---- last layer done (BOTH: every layer): window -> two tile rows -----
-#ifndef S2X_NOLOCK
         if (!CELL) {  // ascending order: no deadlock
           if (use_a) s2_lock_row(locks, t_lay + t_row0, lane);
           if (use_b) s2_lock_row(locks, t_lay + t_row0 + 1, lane);
         }
-#endif
         if (qn != 0) {
           s2_apply_queue<CELL>(tile4, clk_addr, qv, qc, qn, lane);
           qn = 0;
@@ -1192,24 +1064,24 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
             while (__ballot(na || nb) != 0ull) {
               if (na && nb) {
                 int oa, ob;
-                s2_try2(la, lb, oa, ob);
-                if (oa == 0) { trow[c] = s2_fma4(trow[c], v, wy0); }
-                if (ob == 0) { trow[Wt + c] = s2_fma4(trow[Wt + c], v, wy1); }
-                S2_FENCE();
-                if (oa == 0) { s2_unlock(la); na = false; }
-                if (ob == 0) { s2_unlock(lb); nb = false; }
+                cell_try2(la, lb, oa, ob);
+                if (oa == 0) { trow[c] = f4_fma(trow[c], v, wy0); }
+                if (ob == 0) { trow[Wt + c] = f4_fma(trow[Wt + c], v, wy1); }
+                LSI_COMPILER_FENCE();
+                if (oa == 0) { cell_unlock(la); na = false; }
+                if (ob == 0) { cell_unlock(lb); nb = false; }
               } else if (na) {
-                if (s2_try1(la) == 0) {
-                  trow[c] = s2_fma4(trow[c], v, wy0);
-                  S2_FENCE();
-                  s2_unlock(la);
+                if (cell_try1(la) == 0) {
+                  trow[c] = f4_fma(trow[c], v, wy0);
+                  LSI_COMPILER_FENCE();
+                  cell_unlock(la);
                   na = false;
                 }
               } else if (nb) {
-                if (s2_try1(lb) == 0) {
-                  trow[Wt + c] = s2_fma4(trow[Wt + c], v, wy1);
-                  S2_FENCE();
-                  s2_unlock(lb);
+                if (cell_try1(lb) == 0) {
+                  trow[Wt + c] = f4_fma(trow[Wt + c], v, wy1);
+                  LSI_COMPILER_FENCE();
+                  cell_unlock(lb);
                   nb = false;
                 }
               }
@@ -1221,17 +1093,11 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
             const float4 v = *wc;
             *wc = make_float4(0.f, 0.f, 0.f, 0.f);  // ready for the next task
             const bool inside = (unsigned)(c_in + c) < (unsigned)Wt;
-#ifndef S2X_NOMERGE
-            if (use_a && inside) trow[c] = s2_fma4(trow[c], v, wy0);
-            if (use_b && inside) trow[Wt + c] = s2_fma4(trow[Wt + c], v, wy1);
-#else
-            if (inside && v.x == 123.456f) trow[c] = v;
-#endif
+            if (use_a && inside) trow[c] = f4_fma(trow[c], v, wy0);
+            if (use_b && inside) trow[Wt + c] = f4_fma(trow[Wt + c], v, wy1);
           }
-#ifndef S2X_NOLOCK
           if (use_b) s2_unlock_row(locks, t_lay + t_row0 + 1, lane);
           if (use_a) s2_unlock_row(locks, t_lay + t_row0, lane);
-#endif
         }
       }
       if (BOTH) t_lay += R;  // the unit's next item is its next layer
@@ -1244,7 +1110,7 @@ __global__ __launch_bounds__(MAXT) void splat_stream2_kernel(S2Args a) {
       int any = ld_done == 0;
 #pragma unroll
       for (int k = 0; k < NSETS; ++k) any |= tag[k] >= 0;
-      if (!S2_RFL(any ? 1 : 0)) break;
+      if (!LSI_RFL(any ? 1 : 0)) break;
 #pragma unroll
       for (int k = 0; k < NSETS; ++k) tag[k] = item(set[k], tag[k]);
     }
@@ -1665,12 +1531,12 @@ int s2_plan_search(const LsiSplatDesc* d, int wmax, int maxnw, bool both, S2Plan
   return LSI_OK;
 }
 
-#ifndef LSI_S2_NSETS
-#define LSI_S2_NSETS 2
-#endif
-#ifndef LSI_S2_MAXT
-#define LSI_S2_MAXT 768
-#endif
+// The narrow build: 12 waves of two register sets (items of loads in flight per
+// wave).  3 / 4 sets: cfg3 80.8 -> 83.5 / 84.7 us, a wave's loads return in
+// order; two sets under a 1024-thread bound: 12 registers spilled in the item
+// loop, cfg3 93.4 vs 81.5 us.
+constexpr int S2_NSETS = 2;
+constexpr int S2_MAXT = 768;
 
 // 16 waves x one register set (<= 128 VGPRs) instead of 12 x two
 // (lsi_stream2_launch).  Measured, same box, 12 x 2 -> 16 x 1
@@ -1695,17 +1561,17 @@ int s2_plan_search(const LsiSplatDesc* d, int wmax, int maxnw, bool both, S2Plan
 bool s2_choose(const LsiSplatDesc* d, int wmax, bool both, S2Plan* plan, bool* wide) {
   static const char* env = getenv("LSI_S2_WIDE");
   S2Plan narrow, wideplan;
-  const int rc_n = d->tune_threads > LSI_S2_MAXT
-                       ? LSI_EINVAL : s2_plan(d, wmax, LSI_S2_MAXT / 64, both, &narrow);
+  const int rc_n = d->tune_threads > S2_MAXT
+                       ? LSI_EINVAL : s2_plan(d, wmax, S2_MAXT / 64, both, &narrow);
   // (tune_threads > 768 names the build, not a wave count: as many of the 16
   // waves as fit next to the tile)
   LsiSplatDesc dw = *d;
-  if (dw.tune_threads > LSI_S2_MAXT) dw.tune_threads = 0;
-  const int rc_w = (d->tune_threads > 0 && d->tune_threads <= LSI_S2_MAXT)
+  if (dw.tune_threads > S2_MAXT) dw.tune_threads = 0;
+  const int rc_w = (d->tune_threads > 0 && d->tune_threads <= S2_MAXT)
                        ? LSI_EINVAL : s2_plan(&dw, wmax, 1024 / 64, both, &wideplan);
   bool w = rc_w == LSI_OK &&
-           (rc_n != LSI_OK || (wideplan.nw > LSI_S2_MAXT / 64 &&
-                               narrow.nunit < 2 * (LSI_S2_MAXT / 64)));
+           (rc_n != LSI_OK || (wideplan.nw > S2_MAXT / 64 &&
+                               narrow.nunit < 2 * (S2_MAXT / 64)));
   if (env && d->tune_threads <= 0) w = atoi(env) != 0 ? rc_w == LSI_OK : rc_n != LSI_OK;
   if (!w && rc_n != LSI_OK) return false;
   *plan = w ? wideplan : narrow;
@@ -1822,7 +1688,7 @@ int lsi_stream2_launch(const SplatArgs& a, int wmax, hipStream_t stream,
     adapt = s2_adapt_begin(d, stream, &want_wide, &probe);
     if (adapt && want_wide) {
       S2Plan wp;
-      if (s2_plan(d, wmax, 1024 / 64, both, &wp) == LSI_OK && wp.nw > LSI_S2_MAXT / 64) {
+      if (s2_plan(d, wmax, 1024 / 64, both, &wp) == LSI_OK && wp.nw > S2_MAXT / 64) {
         plan = wp; wide = true;
       }
     }
@@ -1892,7 +1758,7 @@ int lsi_stream2_launch(const SplatArgs& a, int wmax, hipStream_t stream,
   // (row locks with both outputs: s2_plan never picks cell locks there)
 #define S2_FN(C, B, P, R)                                                             \
   (wide ? (const void*)splat_stream2_kernel<1, C, 1024, B, P, R>                         \
-        : (const void*)splat_stream2_kernel<LSI_S2_NSETS, C, LSI_S2_MAXT, B, P, R>)
+        : (const void*)splat_stream2_kernel<S2_NSETS, C, S2_MAXT, B, P, R>)
 #define S2_PICK(C, B) (pack ? (ragged ? S2_FN(C, B, true, true) : S2_FN(C, B, true, false)) \
                             : (ragged ? S2_FN(C, B, false, true) : S2_FN(C, B, false, false)))
   const void* fn = both ? S2_PICK(false, true)

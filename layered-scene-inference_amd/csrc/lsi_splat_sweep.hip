@@ -61,13 +61,9 @@ using namespace lsi;
 namespace {
 
 constexpr int SWEEP_CAP = 4096; // item-list entries in LDS (candidates per chunk)
-#ifndef LSI_SWEEP_T
-#define LSI_SWEEP_T 1024
-#endif
-#ifndef LSI_SWEEP_WGS
-#define LSI_SWEEP_WGS 1
-#endif
-constexpr int SWEEP_T = LSI_SWEEP_T;   // threads per workgroup
+constexpr int SWEEP_T = 1024;   // threads per workgroup
+constexpr int SWEEP_WGS = 1;    // workgroups per CU the launch bounds ask for
+constexpr int SWEEP_CELLS = 4096;  // cells of a tile at most (2048 below 1024 threads)
 constexpr int SWEEP_NW = SWEEP_T / 64;  // waves
 constexpr int SWEEP_BPW = (SWEEP_CAP / 64 + SWEEP_NW - 1) / SWEEP_NW;  // blocks per wave
 constexpr int SEGW = 64;        // source pixels per item (16 lanes x 4)
@@ -87,15 +83,6 @@ struct SweepCfg {
   int stream_out;  // 1: 16-byte aligned outputs, Wt % 4 == 0: whole-line streaming stores
   float inv_nq4, inv_nlw;
 };
-
-// n / d for 0 <= n < 2^22, d > 0, rcp = fl(1/d)
-__device__ __forceinline__ int div_small(int n, int d, float rcp) {
-  int q = (int)((float)n * rcp);
-  const int r = n - q * d;
-  q += (r >= d) ? 1 : 0;
-  q -= (r < 0) ? 1 : 0;
-  return q;
-}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -223,7 +210,7 @@ __device__ __forceinline__ void div2_rn(float q0, float q1, float n, bool active
 }
 
 template <int TWL, bool VEC4, bool HAS_MASK, bool WANT_DISP>
-__global__ __launch_bounds__(SWEEP_T, LSI_SWEEP_WGS) void splat_sweep_kernel(
+__global__ __launch_bounds__(SWEEP_T, SWEEP_WGS) void splat_sweep_kernel(
     SplatArgs a, SweepCfg c, const float2* __restrict__ range) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int TW = 1 << TWL;
@@ -813,8 +800,6 @@ __global__ __launch_bounds__(SWEEP_T, LSI_SWEEP_WGS) void splat_sweep_kernel(
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // 16-byte loads of 4 consecutive pixels: channels-last texture, unit pixel
 // strides, every row / layer / batch offset a multiple of 4 floats.
 bool sweep_vec4(const SplatArgs& a) {
@@ -853,10 +838,7 @@ int lsi_sweep_launch(const SplatArgs& a, const float2* range, hipStream_t stream
   const int TW = 1 << twl;
   const bool compose = (d->flags & LSI_COMPOSE) != 0;
   const int nz = compose ? 1 : d->L;
-#ifndef LSI_SWEEP_CELLS
-#define LSI_SWEEP_CELLS (LSI_SWEEP_T < 1024 ? 2048 : 4096)
-#endif
-  c.th = LSI_SWEEP_CELLS / TW;
+  c.th = SWEEP_CELLS / TW;
   if (d->tune_rows > 0 && d->tune_rows < c.th) c.th = d->tune_rows;
   // shorter tiles when the tall ones would leave CUs idle
   while (c.th > 8 && (long)((d->Ht + c.th - 1) / c.th) *

@@ -274,9 +274,6 @@ __global__ __launch_bounds__(1024) void splat_tile_kernel(
         const float X = div_rn(q0, nden) * s - 0.5f;
         const float x0 = floorf(X);
         if (!(x0 >= ax_lo && x0 <= ax_hi)) continue;
-#ifdef LSI_TILE_EXPERIMENT_REJECT_ALL
-        if (y0 > -1.0e30f) continue;
-#endif
         const float q3 = mrow(m, 3, px, py, dv);
         const float dd = div_rn(q3, nden);
         const float pw =
@@ -320,7 +317,6 @@ __global__ __launch_bounds__(1024) void splat_tile_kernel(
         }
         // a chunk reaches only a few rows of the tile: most of a wave's cell
         // groups have nothing to gather (wave-uniform skip)
-#ifndef LSI_TILE_EXPERIMENT_SKIP_GATHER
 #pragma unroll
         for (int q = 0; q < MAXCPT; ++q) {
           while (__ballot((jl[4 * q] & jl[4 * q + 1] & jl[4 * q + 2] &
@@ -341,7 +337,6 @@ __global__ __launch_bounds__(1024) void splat_tile_kernel(
             }
           }
         }
-#endif
       }
       TILE_STAMP(2);
       __syncthreads();  // records and `next` are rewritten by the next chunk

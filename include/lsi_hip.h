@@ -599,7 +599,20 @@ int lsi_bn_relu_bwd(const void* x, const void* dy, const float* mean_rstd,
 /* lsi_bn_relu_fwd behind a producer that left the sums of x and x * x in
  * `workspace` (lsi_conv2d_fwd_bnstats / lsi_conv2d_bwd_data_bnstats on the same
  * stream): one pass -- y = relu((x - mean) * rstd + beta), mean_rstd out as from
- * lsi_bn_relu_fwd --, accumulators cleared for the next producer. */
+ * lsi_bn_relu_fwd --, accumulators cleared for the next producer.
+ *   Numerical contract (tests/test_bn_stats_cpu.py derives it, test_bn_stats_gpu.py
+ * holds every producer to it): the sums are plain fp32 and var = E[x^2] - mean^2
+ * is formed in fp32, clamped at 0, so per channel, with m and v the exact mean
+ * and biased variance of the stored tensor,
+ *     |rstd / rsqrt(v + eps) - 1|  <=  2^-20 * (v + m^2) / (v + eps) + 2^-22,
+ *     |mean - m|                   <=  1e-5 * max|x|.
+ * At mean ~ 0 that is rstd to ~1e-6; at |m| = 100 sigma up to 1e-2 is allowed
+ * (measured on the MI355X: ~1e-3, profiles/bn_stats/errors.txt) -- below the
+ * bf16 rounding of y.  A constant channel gives var within rounding of 0 and
+ * y = relu(beta).  lsi_bn_relu_fwd (sums around a per-channel shift -- the median
+ * of the channel at three pixels of the group --, fp64 finish) keeps rstd to 2e-5
+ * at every m / sigma, one of those pixels an outlier included.  Both normalise
+ * as (x - mean) * rstd + beta, which a constant channel leaves as beta exactly. */
 int lsi_bn_relu_norm(const void* x, void* y, const float* beta, float* workspace,
                      float* mean_rstd, int64_t npix, int32_t C, int32_t bf16, int32_t relu,
                      float eps, int32_t groups, lsi_stream_t stream);

@@ -15,8 +15,10 @@
 // Layout: x is N*H*W pixels x C channels, C innermost (torch channels_last),
 // fp32 or bf16; C a multiple of the 16-byte vector (4 fp32 / 8 bf16) with
 // C / vector a power of two <= 256.  Statistics are accumulated in fp32 per
-// thread (around a per-channel shift: the channel's first value, so that
-// E[(x-k)^2] - E[x-k]^2 does not cancel), per workgroup in fp32 through LDS,
+// thread (around a per-channel shift k, so that E[(x-k)^2] - E[x-k]^2 does not
+// cancel: the median of the channel's values at three pixels of the group --
+// one value alone may sit tens of sigma off, an image corner or an outlier, and
+// the fp32 sums then cancel after all), per workgroup in fp32 through LDS,
 // across workgroups by fp32 device-scope atomic adds into 2*C accumulators; the
 // workgroup that arrives LAST (a device-scope counter) turns the totals into
 // the per-channel constants the second pass reads and leaves accumulators and
@@ -143,18 +145,39 @@ __device__ __forceinline__ void* grp_out(void* p, long npix, int C) {
   return static_cast<char*>(p) + (size_t)blockIdx.y * npix * C * (BF16 ? 2 : 4);
 }
 
-// pass 2 of the forward: y = relu(x * a + b), a = rstd, b = beta - mean * rstd
+// The shift of the statistics pass: per channel the median of the values at
+// three pixels inside the group (vector `lane` of each pixel).
+template <bool BF16>
+__device__ __forceinline__ void stat_shift(const void* x, long npix, int lpp, int lane,
+                                           float* kk) {
+  constexpr int NV = Vec<BF16>::N;
+  const long pa = npix / 3, pb = npix / 2 + npix / 7, pc = npix - 1 - npix / 5;   // all < npix
+  float a[NV], b[NV], c[NV];
+  Vec<BF16>::load(x, pa * lpp + lane, a);
+  Vec<BF16>::load(x, pb * lpp + lane, b);
+  Vec<BF16>::load(x, pc * lpp + lane, c);
+#pragma unroll
+  for (int k = 0; k < NV; ++k)
+    kk[k] = fmaxf(fminf(a[k], b[k]), fminf(fmaxf(a[k], b[k]), c[k]));
+}
+
+// pass 2 of the forward: y = relu((x - mean) * rstd + beta); am = rstd, mean.
+// (x - mean first: x * rstd + (beta - mean * rstd) loses |mean| * rstd * 2^-24 to
+// the rounding of the constant -- 1e-4 at mean = 1000 sigma, and a constant
+// channel does not come out as beta.)
 template <bool BF16>
 __device__ __forceinline__ void norm_pass(const void* __restrict__ x, void* __restrict__ y,
-                                          const float* ab, long npix, int C, int relu) {
+                                          const float* am, const float* __restrict__ beta,
+                                          long npix, int C, int relu) {
   constexpr int NV = Vec<BF16>::N;
   const int lpp = C / NV, rows = BN_THREADS / lpp;
   const int lane = threadIdx.x % lpp, row = threadIdx.x / lpp;
-  float a[NV], b[NV];
+  float a[NV], mu[NV], b[NV];
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
-    a[k] = ab[lane * NV + k];
-    b[k] = ab[C + lane * NV + k];
+    a[k] = am[lane * NV + k];
+    mu[k] = am[C + lane * NV + k];
+    b[k] = beta[lane * NV + k];
   }
   const long stride = (long)gridDim.x * rows;
   long p = (long)blockIdx.x * rows + row;
@@ -166,7 +189,7 @@ __device__ __forceinline__ void norm_pass(const void* __restrict__ x, void* __re
     for (int u = 0; u < 4; ++u) {
 #pragma unroll
       for (int k = 0; k < NV; ++k) {
-        const float z = __fmaf_rn(v[u][k], a[k], b[k]);
+        const float z = __fmaf_rn(v[u][k] - mu[k], a[k], b[k]);
         v[u][k] = (relu && z < 0.0f) ? 0.0f : z;   // (not fmaxf: NaN constants must show)
       }
       Vec<BF16>::store(y, (p + u * stride) * lpp + lane, v[u]);
@@ -177,15 +200,14 @@ __device__ __forceinline__ void norm_pass(const void* __restrict__ x, void* __re
     Vec<BF16>::load(x, p * lpp + lane, v);
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
-      const float z = __fmaf_rn(v[k], a[k], b[k]);
+      const float z = __fmaf_rn(v[k] - mu[k], a[k], b[k]);
       v[k] = (relu && z < 0.0f) ? 0.0f : z;
     }
     Vec<BF16>::store(y, p * lpp + lane, v);
   }
 }
 
-// pass 1 of the forward: sums of (x - k) and (x - k)^2 per channel, k = the
-// channel's value at pixel 0
+// pass 1 of the forward: sums of (x - k) and (x - k)^2 per channel, k = stat_shift
 template <bool BF16>
 __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(
     const void* __restrict__ x_, const float* __restrict__ beta,
@@ -199,7 +221,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(
   const int rows = BN_THREADS / lpp;           // pixels per workgroup step
   const int lane = threadIdx.x % lpp, row = threadIdx.x / lpp;
   float kk[NV], s[NV], q[NV];
-  Vec<BF16>::load(x, lane, kk);
+  stat_shift<BF16>(x, npix, lpp, lane, kk);
 #pragma unroll
   for (int k = 0; k < NV; ++k) { s[k] = 0.f; q[k] = 0.f; }
   const long stride = (long)gridDim.x * rows;
@@ -227,10 +249,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(
   }
   __shared__ float tot[2 * 2048];
   if (reduce_all<NV>(s, q, lpp, C, ws, tot)) {
-    // the last workgroup: mean, rstd, and y = x * a + b
+    // the last workgroup: mean and rstd, for pass 2 and for the backward
     for (int c = threadIdx.x; c < C; c += BN_THREADS) {
       float k0[NV];
-      Vec<BF16>::load(x, c / NV, k0);
+      stat_shift<BF16>(x, npix, lpp, c / NV, k0);
       const double shift = (double)k0[c % NV];
       const double m1 = (double)tot[c] / (double)npix;
       double var = (double)tot[C + c] / (double)npix - m1 * m1;   // biased (tf.nn.moments)
@@ -240,7 +262,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(
       mean_rstd[c] = (float)mean;
       mean_rstd[C + c] = rstd;
       tot[c] = rstd;
-      tot[C + c] = beta[c] - (float)mean * rstd;
+      tot[C + c] = (float)mean;
     }
     __syncthreads();
     float* ab = ws + WS_CONST;
@@ -251,9 +273,9 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(
 template <bool BF16>
 __global__ __launch_bounds__(BN_THREADS) void bn_norm_kernel(
     const void* __restrict__ x, void* __restrict__ y, const float* __restrict__ ws,
-    long npix, int C, int relu) {
+    const float* __restrict__ beta, long npix, int C, int relu) {
   norm_pass<BF16>(grp_in<BF16>(x, npix, C), grp_out<BF16>(y, npix, C),
-                         ws + (size_t)blockIdx.y * WS_STRIDE + WS_CONST, npix, C, relu);
+                         ws + (size_t)blockIdx.y * WS_STRIDE + WS_CONST, beta, npix, C, relu);
 }
 
 // The second pass behind a producer that left plain sums of x and x * x in the
@@ -317,10 +339,11 @@ __global__ __launch_bounds__(BN_THREADS) void bn_norm_sums_kernel(
       mr[C + c] = rstd;
     }
     cst[c] = rstd;
-    cst[C + c] = __fmaf_rn(-mean, rstd, beta[c]);
+    cst[C + c] = mean;
   }
   __syncthreads();
-  norm_pass<BF16>(grp_in<BF16>(x, npix, C), grp_out<BF16>(y, npix, C), cst, npix, C, relu);
+  norm_pass<BF16>(grp_in<BF16>(x, npix, C), grp_out<BF16>(y, npix, C), cst, beta, npix, C,
+                  relu);
   // the workgroup that was counted last clears every group's accumulators (all
   // the others had read them when they were counted)
   __shared__ int last;
@@ -355,7 +378,7 @@ __device__ __forceinline__ void dx_pass(const void* __restrict__ x, const void* 
   for (int k = 0; k < NV; ++k) {
     const int c = lane * NV + k;
     mu[k] = mean_rstd[c]; rs[k] = mean_rstd[C + c];
-    be[k] = beta[c] - mu[k] * rs[k];
+    be[k] = beta[c];
     c1[k] = c12[c];
     c2[k] = c12[C + c];
   }
@@ -363,7 +386,7 @@ __device__ __forceinline__ void dx_pass(const void* __restrict__ x, const void* 
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const float xh = (v[k] - mu[k]) * rs[k];
-      const float dz = (!relu || __fmaf_rn(v[k], rs[k], be[k]) > 0.0f) ? g[k] : 0.0f;
+      const float dz = (!relu || __fmaf_rn(v[k] - mu[k], rs[k], be[k]) > 0.0f) ? g[k] : 0.0f;
       v[k] = rs[k] * (dz - c1[k] - xh * c2[k]);
     }
   };
@@ -408,8 +431,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_stats_kernel(
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
     mu[k] = mean_rstd[lane * NV + k]; rs[k] = mean_rstd[C + lane * NV + k];
-    // (the forward's z = x * rstd + (beta - mean * rstd): the same mask)
-    be[k] = beta[lane * NV + k] - mu[k] * rs[k]; s[k] = 0.f; q[k] = 0.f;
+    // (the forward's z = (x - mean) * rstd + beta: the same mask)
+    be[k] = beta[lane * NV + k]; s[k] = 0.f; q[k] = 0.f;
   }
   const long stride = (long)gridDim.x * rows;
   long p = (long)blockIdx.x * rows + row;
@@ -417,7 +440,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_stats_kernel(
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const float xh = (v[k] - mu[k]) * rs[k];
-      const float dz = (!relu || __fmaf_rn(v[k], rs[k], be[k]) > 0.0f) ? g[k] : 0.0f;
+      const float dz = (!relu || __fmaf_rn(v[k] - mu[k], rs[k], be[k]) > 0.0f) ? g[k] : 0.0f;
       s[k] += dz;
       q[k] = __fmaf_rn(dz, xh, q[k]);
     }
@@ -532,12 +555,12 @@ extern "C" int lsi_bn_relu_fwd(const void* x, void* y, const float* beta,
     hipLaunchKernelGGL(bn_stats_kernel<true>, grid, blk, 0, st, x, beta, workspace,
                        mean_rstd, (long)npix, C, eps);
     hipLaunchKernelGGL(bn_norm_kernel<true>, grid, blk, 0, st, x, y,
-                       (const float*)workspace, (long)npix, C, relu);
+                       (const float*)workspace, beta, (long)npix, C, relu);
   } else {
     hipLaunchKernelGGL(bn_stats_kernel<false>, grid, blk, 0, st, x, beta, workspace,
                        mean_rstd, (long)npix, C, eps);
     hipLaunchKernelGGL(bn_norm_kernel<false>, grid, blk, 0, st, x, y,
-                       (const float*)workspace, (long)npix, C, relu);
+                       (const float*)workspace, beta, (long)npix, C, relu);
   }
   return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
 }

@@ -527,6 +527,26 @@ int lsi_compose_depth_fwd(int32_t L, int64_t N, const float* masks,
                           const float* dmaps, int32_t bg_layer, float dmax,
                           float min_disp, float depth_softmax_temp, float* out,
                           lsi_stream_t stream);
+/*
+ * Gradients of lsi_compose_fwd / lsi_compose_depth_fwd: TF autodiff of the same
+ * op graph, per pixel, no atomics; the selected layer is the forward's.  The
+ * forward's arguments, then g_out [N,C] (compose) or [N] (compose_depth).
+ * g_imgs [L,N,C], g_masks [L,N], g_dmaps [L,N]: each may be NULL (its work is
+ * skipped); every element of a requested one is written (no zeroing needed).
+ * Hard composition passes g_out to the winning layer's image and nothing else;
+ * compose_depth passes it to the winning layer's disparity where that is > 0
+ * (the selection disparity dmax - d only chooses the layer).  The background
+ * layer takes no gradient.
+ */
+int lsi_compose_bwd(int32_t L, int64_t N, int32_t C, const float* imgs,
+                    const float* masks, const float* dmaps, int32_t soft,
+                    float min_disp, float depth_softmax_temp, const float* g_out,
+                    float* g_imgs, float* g_masks, float* g_dmaps,
+                    lsi_stream_t stream);
+int lsi_compose_depth_bwd(int32_t L, int64_t N, const float* masks,
+                          const float* dmaps, int32_t bg_layer, float dmax,
+                          float min_disp, float depth_softmax_temp,
+                          const float* g_out, float* g_dmaps, lsi_stream_t stream);
 
 /*
  * Fused renderer of batches of planar scenes (lsi/data/synthetic_planes.py):
@@ -568,6 +588,29 @@ int lsi_render_planes(const LsiSceneDesc* desc, const float* tex_rgba,
                       const float* hom, const float* dmat, float* img,
                       float* disp, float* img_room, float* disp_room,
                       lsi_stream_t stream);
+/*
+ * Gradients of lsi_render_planes' img and disp outputs (TF autodiff of the op
+ * route's graph; the layer that wins here is the layer that won there).  The
+ * descriptor is the forward's, without *_ROOM bits (LSI_EINVAL: the room
+ * outputs are forward-only).
+ *   g_img  [B,V,H,W,3], g_disp [B,V,H,W,1]: upstream gradients; either may be
+ *          NULL (zero), not both (LSI_ENULL)
+ *   g_tex  [B,P,Hs,Ws,4]: ACCUMULATED into with float atomics -- the caller
+ *          zeroes it (as g_imgs of lsi_bilinear_bwd); its summation order, and
+ *          so its last bits, vary from run to run
+ *   g_hom  [B,V,P,9], g_dmat [B,V,P,3]: written fully, reproducible bit for bit
+ * Any output may be NULL and its work is skipped.  g_hom / g_dmat need
+ * lsi_render_planes_bwd_workspace_bytes(desc) bytes of workspace (one partial
+ * sum per workgroup; LSI_ENULL / LSI_EWORKSPACE if missing / smaller; bytes
+ * beyond that size are not touched); g_tex alone needs none.  A plane-pixel
+ * whose texture coordinate is not finite samples 0 and sends no gradient.
+ */
+size_t lsi_render_planes_bwd_workspace_bytes(const LsiSceneDesc* desc);
+int lsi_render_planes_bwd(const LsiSceneDesc* desc, const float* tex_rgba,
+                          const float* hom, const float* dmat, const float* g_img,
+                          const float* g_disp, float* g_tex, float* g_hom,
+                          float* g_dmat, void* workspace, size_t workspace_bytes,
+                          lsi_stream_t stream);
 
 /*
  * Fused batch norm (batch statistics) + beta + ReLU of the reference's conv

@@ -463,6 +463,79 @@ __global__ __launch_bounds__(TPB) void compose_kernel(CArgs a, float* out) {
   }
 }
 
+// TF autodiff of compose / compose_depth, per pixel, no
+// atomics: the same max / sum / first-maximum sequence as compose_kernel, so the
+// selected layer is the forward's.  Every element of every requested gradient
+// is written.
+//   soft:  g_img_l = p_l g,  g_z_l = p_l (g . img_l - g . out),
+//          g_m_l = g_z_l / (m_l + 1e-8),  g_d_l = g_z_l [d_l > 0] / (temp d_l^2)
+//   hard:  g_img_w = g for the winner w < L, nothing else (one_hot(argmax))
+//   depth: g_d_w = g [d_w > 0] for the winner w < L; the selection disparity
+//          dmax - d only chooses the layer
+__global__ __launch_bounds__(TPB) void compose_bwd_kernel(CArgs a, const float* g_out,
+                                                          float* g_imgs, float* g_masks,
+                                                          float* g_dmaps) {
+  for (long n = (long)blockIdx.x * TPB + threadIdx.x; n < a.N;
+       n += (long)gridDim.x * TPB) {
+    float mx = layer_logp(a, n, 0);
+    for (int l = 1; l <= a.L; ++l) mx = fmaxf(mx, layer_logp(a, n, l));
+    float sum = 0.0f;
+    for (int l = 0; l <= a.L; ++l) sum += expf(layer_logp(a, n, l) - mx);
+    int arg = 0;
+    float pbest = div_rn(expf(layer_logp(a, n, 0) - mx), sum);
+    for (int l = 1; l <= a.L; ++l) {
+      const float pl = div_rn(expf(layer_logp(a, n, l) - mx), sum);
+      if (pl > pbest) { pbest = pl; arg = l; }
+    }
+    if (a.depth_mode) {
+      const float g = g_out[n];
+      for (int l = 0; l < a.L; ++l) {
+        const long i = (long)l * a.N + n;
+        g_dmaps[i] = (l == arg && a.dmaps[i] > 0.0f) ? g : 0.0f;
+      }
+      continue;
+    }
+    if (!a.soft) {
+      for (int l = 0; l < a.L; ++l) {
+        const long i = (long)l * a.N + n;
+        if (g_imgs)
+          for (int c = 0; c < a.C; ++c)
+            g_imgs[i * a.C + c] = l == arg ? g_out[n * a.C + c] : 0.0f;
+        if (g_masks) g_masks[i] = 0.0f;
+        if (g_dmaps) g_dmaps[i] = 0.0f;
+      }
+      continue;
+    }
+    // g . out, with out as the forward sums it
+    float sgo = 0.0f;
+    for (int c = 0; c < a.C; ++c) {
+      float o = 0.0f;
+      for (int l = 0; l <= a.L; ++l) {
+        const float p = div_rn(expf(layer_logp(a, n, l) - mx), sum);
+        o += p * (l < a.L ? a.imgs[((long)l * a.N + n) * a.C + c] : 1.0f);
+      }
+      sgo += g_out[n * a.C + c] * o;
+    }
+    for (int l = 0; l < a.L; ++l) {
+      const long i = (long)l * a.N + n;
+      const float p = div_rn(expf(layer_logp(a, n, l) - mx), sum);
+      float sgi = 0.0f;
+      for (int c = 0; c < a.C; ++c) {
+        const float g = g_out[n * a.C + c];
+        sgi += g * a.imgs[i * a.C + c];
+        if (g_imgs) g_imgs[i * a.C + c] = p * g;
+      }
+      const float gz = p * (sgi - sgo);
+      if (g_masks) g_masks[i] = div_rn(gz, a.masks[i] + 1e-8f);
+      if (g_dmaps) {
+        const float d = a.dmaps[i];
+        // p_l -> 0 faster than d^2: 0 at gz == 0
+        g_dmaps[i] = (d > 0.0f && gz != 0.0f) ? div_rn(gz, a.temp * (d * d)) : 0.0f;
+      }
+    }
+  }
+}
+
 int rc_of_launch() {
   return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
 }
@@ -627,6 +700,36 @@ int lsi_compose_depth_fwd(int32_t L, int64_t N, const float* masks,
   a.dmax = dmax; a.soft = 0; a.depth_mode = 1; a.bg_layer = bg_layer;
   hipLaunchKernelGGL(compose_kernel, dim3(grid_for(N)), dim3(TPB), 0,
                      (hipStream_t)stream, a, out);
+  return rc_of_launch();
+}
+
+int lsi_compose_bwd(int32_t L, int64_t N, int32_t C, const float* imgs,
+                    const float* masks, const float* dmaps, int32_t soft,
+                    float min_disp, float depth_softmax_temp, const float* g_out,
+                    float* g_imgs, float* g_masks, float* g_dmaps,
+                    lsi_stream_t stream) {
+  if (L <= 0 || N <= 0 || C <= 0 || depth_softmax_temp == 0.0f) return LSI_EINVAL;
+  if (!imgs || !masks || !dmaps || !g_out) return LSI_ENULL;
+  if (!g_imgs && !g_masks && !g_dmaps) return LSI_OK;
+  CArgs a; a.L = L; a.C = C; a.N = N; a.imgs = imgs; a.masks = masks;
+  a.dmaps = dmaps; a.min_disp = min_disp; a.temp = depth_softmax_temp;
+  a.dmax = 0.0f; a.soft = soft; a.depth_mode = 0; a.bg_layer = 0;
+  hipLaunchKernelGGL(compose_bwd_kernel, dim3(grid_for(N)), dim3(TPB), 0,
+                     (hipStream_t)stream, a, g_out, g_imgs, g_masks, g_dmaps);
+  return rc_of_launch();
+}
+
+int lsi_compose_depth_bwd(int32_t L, int64_t N, const float* masks,
+                          const float* dmaps, int32_t bg_layer, float dmax,
+                          float min_disp, float depth_softmax_temp,
+                          const float* g_out, float* g_dmaps, lsi_stream_t stream) {
+  if (L <= 0 || N <= 0 || depth_softmax_temp == 0.0f) return LSI_EINVAL;
+  if (!masks || !dmaps || !g_out || !g_dmaps) return LSI_ENULL;
+  CArgs a; a.L = L; a.C = 1; a.N = N; a.imgs = nullptr; a.masks = masks;
+  a.dmaps = dmaps; a.min_disp = min_disp; a.temp = depth_softmax_temp;
+  a.dmax = dmax; a.soft = 0; a.depth_mode = 1; a.bg_layer = bg_layer;
+  hipLaunchKernelGGL(compose_bwd_kernel, dim3(grid_for(N)), dim3(TPB), 0,
+                     (hipStream_t)stream, a, g_out, nullptr, nullptr, g_dmaps);
   return rc_of_launch();
 }
 

@@ -148,7 +148,14 @@ SIGNATURES = {
                         [_I32, _F32, _F32, _VP, _VP]),
     'lsi_compose_depth_fwd': (ctypes.c_int, [_I32, _I64] + [_VP] * 2 +
                               [_I32, _F32, _F32, _F32, _VP, _VP]),
+    'lsi_compose_bwd': (ctypes.c_int, [_I32, _I64, _I32] + [_VP] * 3 +
+                        [_I32, _F32, _F32] + [_VP] * 5),
+    'lsi_compose_depth_bwd': (ctypes.c_int, [_I32, _I64] + [_VP] * 2 +
+                              [_I32, _F32, _F32, _F32] + [_VP] * 3),
     'lsi_render_planes': (ctypes.c_int, [ctypes.POINTER(LsiSceneDesc)] + [_VP] * 8),
+    'lsi_render_planes_bwd_workspace_bytes': (_SZ, [ctypes.POINTER(LsiSceneDesc)]),
+    'lsi_render_planes_bwd': (ctypes.c_int, [ctypes.POINTER(LsiSceneDesc)] +
+                              [_VP] * 9 + [_SZ, _VP]),
     'lsi_conv2d_supported': (ctypes.c_int, [_CP]),
     'lsi_conv2d_packed_bytes': (_SZ, [_CP]),
     'lsi_conv2d_pack': (ctypes.c_int, [_CP, _I32, _VP, _VP, _SZ, _VP]),

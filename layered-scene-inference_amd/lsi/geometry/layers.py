@@ -1,27 +1,35 @@
 """Layer composition and planar transforms (mirror of the reference's
 lsi/geometry/layers.py)."""
+import ctypes
+
 import torch
 
 from lsi.geometry import homography
 
 
 def compose(imgs, masks, dmaps, soft=False, min_disp=1e-6,
-            depth_softmax_temp=1):
+            depth_softmax_temp=1, differentiable=False):
   """Composes layer images into one image with a white background layer at
   min_disp (reference layers.py:29-70).  imgs: L x [...] x C, masks/dmaps:
-  L x [...] x 1.  Returns [...] x C.  One HIP pass (lsi_compose_fwd, forward
-  only: data generation and evaluation); CPU tensors raise."""
+  L x [...] x 1.  Returns [...] x C.  One HIP pass (lsi_compose_fwd); CPU
+  tensors raise.  With differentiable=True one more pass gives the gradients of
+  imgs, masks and dmaps (lsi_compose_bwd; hard composition passes a gradient to
+  the selected layer's image only); without it an input that requires a
+  gradient raises, as it always did."""
   from lsi.loss import _hip  # pylint: disable=g-import-not-at-top
-  return _hip.compose(imgs, masks, dmaps, soft, min_disp, depth_softmax_temp)
+  return _hip.compose(imgs, masks, dmaps, soft, min_disp, depth_softmax_temp,
+                      differentiable)
 
 
 def compose_depth(masks, dmaps, bg_layer=False, min_disp=1e-6,
-                  depth_softmax_temp=1):
+                  depth_softmax_temp=1, differentiable=False):
   """Composes layer disparities into one map (reference layers.py:73-115):
-  lsi_compose_depth_fwd (forward only); CPU tensors raise."""
+  lsi_compose_depth_fwd; CPU tensors raise.  With differentiable=True the
+  selected layer's disparity takes the gradient (lsi_compose_depth_bwd);
+  without it an input that requires a gradient raises, as it always did."""
   from lsi.loss import _hip  # pylint: disable=g-import-not-at-top
   return _hip.compose_depth(masks, dmaps, bg_layer, min_disp,
-                            depth_softmax_temp)
+                            depth_softmax_temp, differentiable)
 
 
 def planar_transform(imgs, masks, pixel_coords_trg, k_s, k_t, rot, t, n_hat, a):
@@ -56,6 +64,52 @@ def plane_homographies(k_w, k_v, rot, t, n_hat, a):
           homography.inv_homography_dmat(k_v, rot, t, n_hat, a))
 
 
+class _RenderPlanes(torch.autograd.Function):
+  """lsi_render_planes (img, disp) / lsi_render_planes_bwd on tex B x P x Hs x
+  Ws x 4, hom B x V x P x 9, dmat B x V x P x 3 (contiguous fp32)."""
+
+  @staticmethod
+  def forward(ctx, tex, hom, dmat, desc):
+    from lsi import _C  # pylint: disable=g-import-not-at-top
+    dev = tex.device
+    new = lambda c: torch.empty((desc.B, desc.V, desc.H, desc.W, c),
+                                dtype=torch.float32, device=dev)
+    img, disp = new(3), new(1)
+    rc = _C.lib().lsi_render_planes(ctypes.byref(desc), _C.ptr(tex), _C.ptr(hom),
+                                    _C.ptr(dmat), _C.ptr(img), _C.ptr(disp), None,
+                                    None, _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_render_planes')
+    ctx.save_for_backward(tex, hom, dmat)
+    ctx.desc = desc
+    ctx.set_materialize_grads(False)
+    return img, disp
+
+  @staticmethod
+  def backward(ctx, g_img, g_disp):
+    from lsi import _C  # pylint: disable=g-import-not-at-top
+    tex, hom, dmat = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    if (g_img is None and g_disp is None) or not any(need[:3]):
+      return None, None, None, None
+    dev = tex.device
+    f32c = lambda g: None if g is None else g.float().contiguous()
+    g_img, g_disp = f32c(g_img), f32c(g_disp)
+    # the texture gradient is accumulated (float atomics), the others written
+    g_tex = torch.zeros_like(tex) if need[0] else None
+    g_hom = torch.empty_like(hom) if need[1] else None
+    g_dmat = torch.empty_like(dmat) if need[2] else None
+    ws, n = None, 0
+    if need[1] or need[2]:
+      n = int(_C.lib().lsi_render_planes_bwd_workspace_bytes(ctypes.byref(ctx.desc)))
+      ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+    rc = _C.lib().lsi_render_planes_bwd(
+        ctypes.byref(ctx.desc), _C.ptr(tex), _C.ptr(hom), _C.ptr(dmat),
+        _C.ptr(g_img), _C.ptr(g_disp), _C.ptr(g_tex), _C.ptr(g_hom),
+        _C.ptr(g_dmat), _C.ptr(ws), n, _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_render_planes_bwd')
+    return g_tex, g_hom, g_dmat, None
+
+
 def render_planes(imgs, masks, k_w, k_v, rot, t, n_hat, a, view_hw, soft=False,
                   min_disp=1e-6, depth_softmax_temp=1, n_box=None):
   """B worlds of P textured planes rendered into V views each by ONE HIP launch
@@ -70,13 +124,20 @@ def render_planes(imgs, masks, k_w, k_v, rot, t, n_hat, a, view_hw, soft=False,
   arguments of planar_transform, with leading dimensions that broadcast to
   B x V x P.  view_hw = (H, W).  Returns (img B x V x H x W x 3, disp B x V x H x
   W x 1); with n_box also (img_room, disp_room): the same with the masks of the
-  planes [n_box, P) taken as 0.  Forward only; CPU tensors raise."""
+  planes [n_box, P) taken as 0.  CPU tensors raise.
+
+  Without n_box the call is differentiable in imgs, masks (or the RGBA tensor)
+  and, through plane_homographies, in k_w, k_v, rot, t, n_hat and a: one more
+  launch (lsi_render_planes_bwd) gives the gradients the op route's autograd
+  gives.  The room outputs are forward-only: n_box with an input that requires
+  a gradient raises."""
   from lsi import _C  # pylint: disable=g-import-not-at-top
-  import ctypes  # pylint: disable=g-import-not-at-top
   tensors = [x for x in (imgs, masks, k_w, k_v, rot, t, n_hat, a) if x is not None]
   dev = _C.require_device(*tensors)
-  if any(x.requires_grad for x in tensors):
-    raise RuntimeError('layers.render_planes on the GPU is forward-only')
+  wants_grad = torch.is_grad_enabled() and any(x.requires_grad for x in tensors)
+  if wants_grad and n_box is not None:
+    raise RuntimeError('layers.render_planes: the room outputs (n_box) are '
+                       'forward-only; render without n_box for gradients')
   if masks is None:
     if imgs.shape[-1] != 4:
       raise ValueError('render_planes: masks=None needs RGBA textures (got %d '
@@ -103,13 +164,13 @@ def render_planes(imgs, masks, k_w, k_v, rot, t, n_hat, a, view_hw, soft=False,
   d.soft = int(bool(soft))
   d.min_disp, d.temp = float(min_disp), float(depth_softmax_temp)
   d.outputs = _C.LSI_SCENE_IMG | _C.LSI_SCENE_DISP
-  new = lambda c: torch.empty((nb, nv, h, w, c), dtype=torch.float32, device=dev)
-  out = [new(3), new(1)]
-  if n_box is not None:
-    d.outputs |= _C.LSI_SCENE_IMG_ROOM | _C.LSI_SCENE_DISP_ROOM
-    out += [new(3), new(1)]
+  if n_box is None:
+    return _RenderPlanes.apply(tex, hom, dmat, d)
+  d.outputs |= _C.LSI_SCENE_IMG_ROOM | _C.LSI_SCENE_DISP_ROOM
+  out = [torch.empty((nb, nv, h, w, c), dtype=torch.float32, device=dev)
+         for c in (3, 1, 3, 1)]
   rc = _C.lib().lsi_render_planes(
       ctypes.byref(d), _C.ptr(tex), _C.ptr(hom), _C.ptr(dmat),
-      *([_C.ptr(o) for o in out] + [None] * (4 - len(out)) + [_C.stream_ptr(dev)]))
+      *([_C.ptr(o) for o in out] + [_C.stream_ptr(dev)]))
   _C.check(rc, 'lsi_render_planes')
   return tuple(out)

@@ -164,45 +164,114 @@ def view_synthesis_loss(recons_splat, to_recons_img, x_min, y_min):
                           int(y_min))
 
 
-def compose(imgs, masks, dmaps, soft, min_disp, depth_softmax_temp):
-  """lsi_compose_fwd (reference layers.py:29-70); forward only (the reference
-  uses it in its data renderer, never under a gradient)."""
-  dev = _C.require_device(imgs, masks, dmaps)
-  if imgs.requires_grad or masks.requires_grad or dmaps.requires_grad:
-    raise RuntimeError('layers.compose on the GPU is forward-only')
+class _Compose(torch.autograd.Function):
+  """lsi_compose_fwd / lsi_compose_bwd on imgs [L,N,C], masks [L,N], dmaps
+  [L,N] (contiguous fp32)."""
+
+  @staticmethod
+  def forward(ctx, imgs, masks, dmaps, soft, min_disp, temp):
+    dev = imgs.device
+    nl, n, c = imgs.shape
+    out = torch.empty((n, c), dtype=torch.float32, device=dev)
+    rc = _C.lib().lsi_compose_fwd(nl, n, c, _C.ptr(imgs), _C.ptr(masks),
+                                  _C.ptr(dmaps), soft, min_disp, temp,
+                                  _C.ptr(out), _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_compose_fwd')
+    ctx.save_for_backward(imgs, masks, dmaps)
+    ctx.args = (soft, min_disp, temp)
+    return out
+
+  @staticmethod
+  def backward(ctx, g_out):
+    imgs, masks, dmaps = ctx.saved_tensors
+    dev = imgs.device
+    nl, n, c = imgs.shape
+    # inputs that need no gradient get no work
+    grads = [torch.empty_like(x) if need else None
+             for x, need in zip((imgs, masks, dmaps), ctx.needs_input_grad)]
+    rc = _C.lib().lsi_compose_bwd(nl, n, c, _C.ptr(imgs), _C.ptr(masks),
+                                  _C.ptr(dmaps), *ctx.args,
+                                  _C.ptr(_f32(g_out).contiguous()),
+                                  *[_C.ptr(g) for g in grads], _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_compose_bwd')
+    return tuple(grads) + (None, None, None)
+
+
+def _refuse_grad(what, tensors):
+  # an input that asks for a gradient must not lose it silently: without the
+  # caller's differentiable=True the call is the forward-only one it always was
+  if any(x.requires_grad for x in tensors):
+    raise RuntimeError('%s on the GPU is forward-only unless it is called with '
+                       'differentiable=True' % what)
+
+
+def compose(imgs, masks, dmaps, soft, min_disp, depth_softmax_temp,
+            differentiable=False):
+  """lsi_compose_fwd (reference layers.py:29-70); with differentiable=True also
+  lsi_compose_bwd: the gradients of imgs, masks and dmaps as TF differentiates
+  the reference's graph."""
+  _C.require_device(imgs, masks, dmaps)
+  if not differentiable:
+    _refuse_grad('layers.compose', (imgs, masks, dmaps))
   nl, c = imgs.shape[0], imgs.shape[-1]
   lead = tuple(imgs.shape[1:-1])
   imgs_c = _f32(imgs).reshape(nl, -1, c).contiguous()
   masks_c = _f32(masks).reshape(nl, -1).contiguous()
   dmaps_c = _f32(dmaps).reshape(nl, -1).contiguous()
-  n = imgs_c.shape[1]
-  out = torch.empty((n, c), dtype=torch.float32, device=dev)
-  rc = _C.lib().lsi_compose_fwd(nl, n, c, _C.ptr(imgs_c), _C.ptr(masks_c),
-                                _C.ptr(dmaps_c), int(bool(soft)), float(min_disp),
-                                float(depth_softmax_temp), _C.ptr(out),
-                                _C.stream_ptr(dev))
-  _C.check(rc, 'lsi_compose_fwd')
+  out = _Compose.apply(imgs_c, masks_c, dmaps_c, int(bool(soft)), float(min_disp),
+                       float(depth_softmax_temp))
   return out.reshape(lead + (c,))
 
 
-def compose_depth(masks, dmaps, bg_layer, min_disp, depth_softmax_temp):
-  """lsi_compose_depth_fwd (reference layers.py:73-115); forward only."""
-  dev = _C.require_device(masks, dmaps)
-  if masks.requires_grad or dmaps.requires_grad:
-    raise RuntimeError('layers.compose_depth on the GPU is forward-only')
+class _ComposeDepth(torch.autograd.Function):
+  """lsi_compose_depth_fwd / lsi_compose_depth_bwd on masks, dmaps [L,N]."""
+
+  @staticmethod
+  def forward(ctx, masks, dmaps, bg_layer, min_disp, temp):
+    dev = masks.device
+    nl, n = masks.shape
+    # tf.reduce_max over the relu'd maps with the background layer appended
+    dmax = 0.0
+    if bg_layer:
+      dmax = max(float(torch.relu(dmaps).max()), min_disp)
+    out = torch.empty((n,), dtype=torch.float32, device=dev)
+    rc = _C.lib().lsi_compose_depth_fwd(nl, n, _C.ptr(masks), _C.ptr(dmaps),
+                                        bg_layer, dmax, min_disp, temp,
+                                        _C.ptr(out), _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_compose_depth_fwd')
+    ctx.save_for_backward(masks, dmaps)
+    ctx.args = (bg_layer, dmax, min_disp, temp)
+    return out
+
+  @staticmethod
+  def backward(ctx, g_out):
+    masks, dmaps = ctx.saved_tensors
+    # the masks only select the layer (one_hot(argmax)): a zero gradient
+    g_masks = torch.zeros_like(masks) if ctx.needs_input_grad[0] else None
+    if not ctx.needs_input_grad[1]:
+      return g_masks, None, None, None, None
+    dev = masks.device
+    nl, n = masks.shape
+    g_dmaps = torch.empty_like(dmaps)
+    rc = _C.lib().lsi_compose_depth_bwd(nl, n, _C.ptr(masks), _C.ptr(dmaps),
+                                        *ctx.args, _C.ptr(_f32(g_out).contiguous()),
+                                        _C.ptr(g_dmaps), _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_compose_depth_bwd')
+    return g_masks, g_dmaps, None, None, None
+
+
+def compose_depth(masks, dmaps, bg_layer, min_disp, depth_softmax_temp,
+                  differentiable=False):
+  """lsi_compose_depth_fwd (reference layers.py:73-115); with
+  differentiable=True also lsi_compose_depth_bwd (the selected layer's
+  disparity takes the gradient, the masks' is zero)."""
+  _C.require_device(masks, dmaps)
+  if not differentiable:
+    _refuse_grad('layers.compose_depth', (masks, dmaps))
   nl = masks.shape[0]
   lead = tuple(masks.shape[1:-1])
   masks_c = _f32(masks).reshape(nl, -1).contiguous()
   dmaps_c = _f32(dmaps).reshape(nl, -1).contiguous()
-  n = masks_c.shape[1]
-  # tf.reduce_max over the relu'd maps with the background layer appended
-  dmax = 0.0
-  if bg_layer:
-    dmax = max(float(torch.relu(dmaps_c).max()), float(min_disp))
-  out = torch.empty((n,), dtype=torch.float32, device=dev)
-  rc = _C.lib().lsi_compose_depth_fwd(nl, n, _C.ptr(masks_c), _C.ptr(dmaps_c),
-                                      int(bool(bg_layer)), dmax, float(min_disp),
-                                      float(depth_softmax_temp), _C.ptr(out),
-                                      _C.stream_ptr(dev))
-  _C.check(rc, 'lsi_compose_depth_fwd')
+  out = _ComposeDepth.apply(masks_c, dmaps_c, int(bool(bg_layer)), float(min_disp),
+                            float(depth_softmax_temp))
   return out.reshape(lead + (1,))

@@ -548,6 +548,108 @@ int lsi_compose_depth_bwd(int32_t L, int64_t N, const float* masks,
                           float min_disp, float depth_softmax_temp,
                           const float* g_out, float* g_dmaps, lsi_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* Evaluation metrics accumulated on the device (csrc/lsi_eval.hip): the     */
+/* arithmetic of ldi_pred_eval.py:297-548 (define_metrics), one pass per     */
+/* rendered view / pair of LDIs.  The running sums live in a caller-owned    */
+/* device array `acc` of LSI_EVAL_SLOTS doubles, zeroed by the caller once;  */
+/* every call ADDS to its slots in a one-block finishing kernel on the       */
+/* caller's stream (stream order serialises the calls that share an          */
+/* accumulator and a workspace).  No atomics: the same sequence of calls     */
+/* gives the same 16 doubles bit for bit.  No host synchronisation.  A       */
+/* metric whose optional inputs are absent leaves its slots untouched.       */
+/* ------------------------------------------------------------------------ */
+#define LSI_EVAL_COMPOSE_SUM 0         /* compose_splat_loss                  */
+#define LSI_EVAL_COMPOSE_NORM 1
+#define LSI_EVAL_COMPOSE_DISOCC_SUM 2  /* compose_splat_loss_disocc           */
+#define LSI_EVAL_COMPOSE_DISOCC_NORM 3
+#define LSI_EVAL_DEPTH_SUM 4           /* depth_splat_loss                    */
+#define LSI_EVAL_DEPTH_NORM 5
+#define LSI_EVAL_DEPTH_DISOCC_SUM 6    /* depth_splat_loss_disocc             */
+#define LSI_EVAL_DEPTH_DISOCC_NORM 7
+#define LSI_EVAL_PSNR_SUM 8            /* psnr: dB summed over the calls      */
+#define LSI_EVAL_PSNR_COUNT 9
+#define LSI_EVAL_FG_TEX_SUM 10         /* fg_tex_error                        */
+#define LSI_EVAL_FG_DISP_SUM 11        /* fg_disp_error                       */
+#define LSI_EVAL_FG_NORM 12
+#define LSI_EVAL_BG_TEX_SUM 13         /* bg_tex_error                        */
+#define LSI_EVAL_BG_DISP_SUM 14        /* bg_disp_error                       */
+#define LSI_EVAL_BG_NORM 15
+#define LSI_EVAL_SLOTS 16
+
+#define LSI_EVAL_DISOCC_U8 1u  /* disocc holds one-byte bools, not floats     */
+#define LSI_EVAL_VALID_GT 2u   /* valid holds a map to threshold: a pixel is  */
+                               /* valid (1) where it exceeds valid_thresh     */
+
+/* Bytes of device scratch (partial sums) the two metric calls need. */
+size_t lsi_eval_workspace_bytes(void);
+
+/*
+ * The view-synthesis metrics of one rendered view (ldi_pred_eval.py:385-460),
+ * one pass over the B x Ht x Wt cells:
+ *   recons [nl,B,Ht,Wt,3], recons_disp [nl,B,Ht,Wt,1] (may be NULL): contiguous
+ *   target [B,H,W,3] with element strides, H = fy Ht, W = fx Wt
+ *   valid [B,H,W] (may be NULL: ones), disocc [B,H,W] fp32 or one-byte bool
+ *   (LSI_EVAL_DISOCC_U8; may be NULL), gt_disp [B,H,W] (may be NULL): contiguous
+ * Per cell every full-resolution input is box-averaged over its fy x fx block
+ * (the AREA resize); valid = mean > 0.95; centre = [x_min <= x < Wt - x_min and
+ * y_min <= y < Ht - y_min] * valid; pw = min_l mean_c |t - r_l| * centre;
+ * se = mean_c (t - r_0)^2 * centre; dm = the un-thresholded mean of disocc;
+ * pd = min_l |gt - rd_l| * centre.  Added to acc:
+ *   slots 0, 1: sum pw, sum centre          2, 3: sum pw dm, sum centre dm
+ *   slots 4, 5: sum pd, sum centre          6, 7: sum pd dm, sum centre dm
+ *   slots 8, 9: 10 log10(1 / max(sum se / sum centre, 1e-20)), 1 -- only when
+ *               sum centre > 0: a call without a scored cell adds nothing
+ * Slots 4-7 need recons_disp and gt_disp, slots 2, 3, 6, 7 need disocc.  Cells
+ * with centre = 0 are not read.
+ */
+int lsi_eval_view_metrics(int32_t nl, int32_t B, int32_t Ht, int32_t Wt,
+                          int32_t H, int32_t W, int32_t x_min, int32_t y_min,
+                          const float* recons, const float* recons_disp,
+                          const float* target, int64_t t_sb, int64_t t_sy,
+                          int64_t t_sx, int64_t t_sc, const float* valid,
+                          const void* disocc, const float* gt_disp,
+                          uint32_t flags, float valid_thresh, double* acc,
+                          void* workspace, size_t workspace_bytes,
+                          lsi_stream_t stream);
+
+/*
+ * The per-layer metrics of a pair of predicted LDIs (ldi_pred_eval.py:476-531),
+ * one pass over B x H x W for both views.  Per view a descriptor gives L, B, H, W,
+ * bg_layer_disp and the element strides of tex (img_s*) and disp (disp_s*), so
+ * permuted convolution outputs and the packed RGBD head output are read in
+ * place; only layers 0 and L - 1 are read.  img [B,H,W,3], gt_disp [B,H,W],
+ * gt_disp_bg [B,H,W] and gt_tex_bg [B,H,W,3] are contiguous; the two *_bg inputs
+ * are given for both views or for neither (else LSI_EINVAL).  The descriptors
+ * must agree in L, B, H, W and bg_layer_disp.  With v = gt_disp > bg_layer_disp
+ * and b = gt_disp > gt_disp_bg, added to acc:
+ *   slots 10, 11, 12: sum_c |tex_0 - img| v / 3, sum |disp_0 - gt_disp| v, sum v
+ *   slots 13, 14, 15: sum_c |tex_{L-1} - gt_tex_bg| b / 3,
+ *                     sum |disp_{L-1} - gt_disp_bg| b, sum b    (with the *_bg)
+ */
+int lsi_eval_layer_metrics(const LsiLossDesc* src_desc, const float* src_tex,
+                           const float* src_disp, const float* src_img,
+                           const float* src_gt_disp, const float* src_gt_disp_bg,
+                           const float* src_gt_tex_bg, const LsiLossDesc* trg_desc,
+                           const float* trg_tex, const float* trg_disp,
+                           const float* trg_img, const float* trg_gt_disp,
+                           const float* trg_gt_disp_bg, const float* trg_gt_tex_bg,
+                           double* acc, void* workspace, size_t workspace_bytes,
+                           lsi_stream_t stream);
+
+/*
+ * projection.disocclusion_mask (lsi/geometry/projection.py:109-150) for source
+ * points on the pixel-centre grid: (x + .5, y + .5, 1, disps_src) through
+ * M [B,4,4] under the floating-point contract of the renderer, divide_safe,
+ * the four taps of disps_trg [B,Ht,Wt,1] as lsi_bilinear_fwd takes them;
+ * mask [B,Hs,Ws,1] = [|d_src->trg - sampled| > thresh], 0 where the projected
+ * point leaves the target (u > Wt, v > Ht, u < 0 or v < 0).
+ */
+int lsi_disocclusion_mask(int32_t B, int32_t Hs, int32_t Ws, int32_t Ht,
+                          int32_t Wt, const float* disps_src,
+                          const float* disps_trg, const float* M, float thresh,
+                          float* mask, lsi_stream_t stream);
+
 /*
  * Fused renderer of batches of planar scenes (lsi/data/synthetic_planes.py):
  * B worlds of P textured planes, V views each, in ONE launch.  Per view pixel

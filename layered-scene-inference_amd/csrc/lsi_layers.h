@@ -38,6 +38,50 @@ __device__ __forceinline__ void taps_of(float u, float v, int Hs, int Ws,
   }
 }
 
+// sampling.py:118-123 (compose=True): valid_x * valid_y * wt_x * wt_y per tap,
+// in the order 00, 01, 10, 11 ...
+__device__ __forceinline__ void tap_weights(const Taps& t, float (&c)[4]) {
+  c[0] = t.vx0 * t.vy0 * t.wx0 * t.wy0;
+  c[1] = t.vx0 * t.vy1 * t.wx0 * t.wy1;
+  c[2] = t.vx1 * t.vy0 * t.wx1 * t.wy0;
+  c[3] = t.vx1 * t.vy1 * t.wx1 * t.wy1;
+}
+
+// ... and channel ch of the sample of ib [Hs*Ws, C], summed in that order; 0 for
+// a non-finite point.  (The one gather of lsi_bilinear_fwd and
+// lsi_disocclusion_mask.)
+__device__ __forceinline__ float bilinear_gather(const Taps& t, const float (&c)[4],
+                                                 const float* __restrict__ ib, int C,
+                                                 int ch) {
+  float o = 0.0f;
+  if (t.ok) {
+    o = c[0] * ib[(size_t)t.i00 * C + ch];
+    o = o + c[1] * ib[(size_t)t.i01 * C + ch];
+    o = o + c[2] * ib[(size_t)t.i10 * C + ch];
+    o = o + c[3] * ib[(size_t)t.i11 * C + ch];
+  }
+  return o;
+}
+
+// AREA resize for integer factors, one output cell: the box mean of the fy x fx
+// block whose first element is p (element strides sy, sx), rows then columns in
+// order, then one multiply by 1 / (fy fx).  NC channels sc apart.
+template <int NC, typename T>
+__device__ __forceinline__ void area_mean(const T* __restrict__ p, long sy, long sx,
+                                          long sc, int fy, int fx, float (&t)[NC]) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) t[c] = 0.0f;
+  for (int dy = 0; dy < fy; ++dy)
+    for (int dx = 0; dx < fx; ++dx) {
+      const T* q = p + (long)dy * sy + (long)dx * sx;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) t[c] += (float)q[c * sc];
+    }
+  const float inv = 1.0f / (float)(fy * fx);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) t[c] *= inv;
+}
+
 // helpers.py:140-160: log-probability of a layer with mask value m whose
 // (selection) disparity is dsel: log(m + 1e-8) - divide_safe(1, relu(dsel)) / temp.
 __device__ __forceinline__ float layer_logp_of(float m, float dsel, float temp) {

@@ -21,37 +21,14 @@
 #include "../../include/lsi_hip.h"
 #include "lsi_common.h"
 #include "lsi_layers.h"
+#include "lsi_reduce.h"
 
 using namespace lsi;
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int MAXBLK = 2048;  // partial sums per scalar
-
-// Block-wide sum of NV per-thread values; thread 0 stores them (fp64) to
-// part[v * MAXBLK + blockIdx.x].
-template <int NV>
-__device__ __forceinline__ void block_store_partials(const float (&v)[NV],
-                                                     double* part) {
-  __shared__ double sm[NV][TPB / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    double x = (double)v[k];
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    if (lane == 0) sm[k][wave] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      double s = 0.0;
-      for (int w = 0; w < TPB / 64; ++w) s += sm[k][w];
-      part[(size_t)k * MAXBLK + blockIdx.x] = s;
-    }
-  }
-}
+// (TPB, MAXBLK, grid_for, block_store_partials, block_total: lsi_reduce.h,
+// shared with lsi_eval.hip)
 
 // out[k] = scale[k] * sum of part[k][0..nblk)   (one block)
 struct Scales { double s[5]; };
@@ -61,16 +38,7 @@ __global__ __launch_bounds__(TPB) void finish_kernel(const double* part, int nbl
   __shared__ double sm[TPB];
   double total = 0.0;
   for (int k = 0; k < nv; ++k) {
-    double x = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += TPB) x += part[(size_t)k * MAXBLK + i];
-    sm[threadIdx.x] = x;
-    __syncthreads();
-    for (int off = TPB / 2; off > 0; off >>= 1) {
-      if (threadIdx.x < off) sm[threadIdx.x] += sm[threadIdx.x + off];
-      __syncthreads();
-    }
-    const double r = sm[0] * sc.s[k];
-    __syncthreads();
+    const double r = block_total(part + (size_t)k * MAXBLK, nblk, sm) * sc.s[k];
     if (combine < 0) {
       if (threadIdx.x == 0) out[k] = (float)r;
     } else {
@@ -84,13 +52,6 @@ __global__ __launch_bounds__(TPB) void finish_kernel(const double* part, int nbl
       }
     }
   }
-}
-
-int grid_for(long n) {
-  long g = (n + TPB - 1) / TPB;
-  if (g > MAXBLK) g = MAXBLK;
-  if (g < 1) g = 1;
-  return (int)g;
 }
 
 // ---------------------------------------------------------------------------
@@ -329,15 +290,9 @@ struct VArgs {
 __device__ __forceinline__ void area_px(const VArgs& a, int b, int yt, int xt,
                                         float (&t)[3]) {
   const int fy = a.H / a.Ht, fx = a.W / a.Wt;
-  t[0] = t[1] = t[2] = 0.0f;
-  for (int dy = 0; dy < fy; ++dy)
-    for (int dx = 0; dx < fx; ++dx) {
-      const float* p = a.target + (long)b * a.t_sb +
-                       (long)(yt * fy + dy) * a.t_sy + (long)(xt * fx + dx) * a.t_sx;
-      t[0] += p[0]; t[1] += p[a.t_sc]; t[2] += p[2 * a.t_sc];
-    }
-  const float inv = 1.0f / (float)(fy * fx);
-  t[0] *= inv; t[1] *= inv; t[2] *= inv;
+  area_mean<3>(a.target + (long)b * a.t_sb + (long)(yt * fy) * a.t_sy +
+                   (long)(xt * fx) * a.t_sx,
+               a.t_sy, a.t_sx, a.t_sc, fy, fx, t);  // lsi_layers.h
 }
 
 __device__ __forceinline__ float layer_l1(const VArgs& a, int l, int b, int yt,

@@ -126,21 +126,10 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(
   taps_of(coords[2 * ti], coords[2 * ti + 1], Hs, Ws, t);
   const float* ib = imgs + (size_t)b * Hs * Ws * C;
   // sampling.py:118-123: valid_x * valid_y * wt_x * wt_y * im, summed in the
-  // order 00, 01, 10, 11.
-  const float c00 = t.vx0 * t.vy0 * t.wx0 * t.wy0;
-  const float c01 = t.vx0 * t.vy1 * t.wx0 * t.wy1;
-  const float c10 = t.vx1 * t.vy0 * t.wx1 * t.wy0;
-  const float c11 = t.vx1 * t.vy1 * t.wx1 * t.wy1;
-  for (int ch = 0; ch < C; ++ch) {
-    float o = 0.0f;
-    if (t.ok) {
-      o = c00 * ib[(size_t)t.i00 * C + ch];
-      o = o + c01 * ib[(size_t)t.i01 * C + ch];
-      o = o + c10 * ib[(size_t)t.i10 * C + ch];
-      o = o + c11 * ib[(size_t)t.i11 * C + ch];
-    }
-    out[ti * C + ch] = o;
-  }
+  // order 00, 01, 10, 11 (lsi_layers.h)
+  float c[4];
+  tap_weights(t, c);
+  for (int ch = 0; ch < C; ++ch) out[ti * C + ch] = bilinear_gather(t, c, ib, C, ch);
 }
 
 // sampling.py:124-130 (compose=False): the four border-masked taps and the four

@@ -43,6 +43,10 @@ def build_parser():
   a('--disocc_thresh', type=float, default=1e-2)
   a('--random_weights', type=train_script._bool, default=False,
     help='evaluate an untrained model when no checkpoint exists (smoke runs)')
+  a('--device_metrics', type=train_script._bool, default=False,
+    help='accumulate the metrics on the device in the fused kernels of '
+    'csrc/lsi_eval.hip and read them back once after the last iteration '
+    '(eval_metrics.MetricAccumulator); false: the op route, one dict per view')
   return p
 
 
@@ -83,9 +87,13 @@ class Tester(object):
     nets.set_is_training(tr.model, bool(self.opts.batch_norm_training))
 
   @torch.no_grad()
-  def eval_batch(self):
+  def eval_batch(self, batch=None, acc=None):
+    """One evaluation iteration on `batch` (None: the next one of the data
+    loader).  Returns the op route's metric dicts, or, with a MetricAccumulator
+    `acc`, adds the same metrics to it on the device and returns []."""
     tr, o = self.trainer, self.opts
-    batch = tr.data_loader.forward(o.batch_size)
+    if batch is None:
+      batch = tr.data_loader.forward(o.batch_size)
     imgs_src, imgs_trg, k_s, k_t, rot, trans = batch[:6]
     dev = tr.device
     imgs_src, imgs_trg = imgs_src.to(dev), imgs_trg.to(dev)
@@ -93,6 +101,7 @@ class Tester(object):
     inv_rot = nn_helpers.transpose(rot)
     inv_trans = -torch.matmul(inv_rot, trans)
     pc = nn_helpers.pixel_coords(o.batch_size, o.img_height, o.img_width)
+    fused = acc is not None
     # ground truth by data set (ldi_pred_eval.py:226-262): synthetic planes
     # carry 14 outputs (fg / bg disparities and background textures), KITTI
     # with --kitti_dl_disparities 8 (the SPS-stereo disparities of both views)
@@ -111,7 +120,7 @@ class Tester(object):
     for ldi, k_a, k_b, r, t, target, key in (
         (ldi_src, k_s, k_t, rot, trans, imgs_trg, 'trg'),
         (ldi_trg, k_t, k_s, inv_rot, inv_trans, imgs_src, 'src')):
-      disocc = gt_disp = valid = None
+      disocc = gt_disp = valid = valid_above = None
       if kitti_disp is not None:
         # ldi_pred_eval.py:171-172: pixels the stereo matcher left empty
         disocc = (kitti_disp[key] == 0)
@@ -121,26 +130,46 @@ class Tester(object):
         a, b_ = ('trg', 'src') if key == 'trg' else ('src', 'trg')
         mat = projection.forward_projection_matrix(k_b, k_a, nn_helpers.transpose(r),
                                                    -torch.matmul(nn_helpers.transpose(r), t))
+        # (the fused kernel generates the pixel-centre grid itself)
         disocc = projection.disocclusion_mask(
             gt[a + '_gt_disp'], gt[b_ + '_gt_disp'],
-            pc.to(dev), mat.to(dev), thresh=o.disocc_thresh)
+            None if fused else pc.to(dev), mat.to(dev), thresh=o.disocc_thresh,
+            fused=fused)
         gt_disp = gt[a + '_gt_disp']
         # ldi_pred_eval.py:354-356: only pixels with geometry are scored
-        valid = (gt_disp > o.bg_layer_disp).float()
-      out.append(eval_metrics.view_synthesis_metrics(
-          ldi, pc, k_a, k_b, r, t, target, o, valid_mask=valid,
-          disocc_mask=disocc, gt_disp_trg=gt_disp))
+        if fused:
+          valid, valid_above = gt_disp, o.bg_layer_disp
+        else:
+          valid = (gt_disp > o.bg_layer_disp).float()
+      if fused:
+        acc.add_view_synthesis(
+            ldi, pc, k_a, k_b, r, t, target, o, valid_mask=valid,
+            disocc_mask=disocc, gt_disp_trg=gt_disp, valid_above=valid_above)
+      else:
+        out.append(eval_metrics.view_synthesis_metrics(
+            ldi, pc, k_a, k_b, r, t, target, o, valid_mask=valid,
+            disocc_mask=disocc, gt_disp_trg=gt_disp))
     if gt is not None:
-      out.append(eval_metrics.layer_prediction_metrics(
-          ldi_src, ldi_trg, imgs_src, imgs_trg, gt, o))
+      if fused:
+        acc.add_layer_prediction(ldi_src, ldi_trg, imgs_src, imgs_trg, gt, o)
+      else:
+        out.append(eval_metrics.layer_prediction_metrics(
+            ldi_src, ldi_trg, imgs_src, imgs_trg, gt, o))
     return out
 
   def test(self):
     self.restore()
-    dicts = []
-    for _ in range(self.opts.num_eval_iter):
-      dicts += self.eval_batch()
-    results = eval_metrics.aggregate(dicts)
+    if self.opts.device_metrics:
+      # the running sums stay on the device; one read-back after the last batch
+      acc = eval_metrics.MetricAccumulator(self.trainer.device)
+      for _ in range(self.opts.num_eval_iter):
+        self.eval_batch(acc=acc)
+      results = acc.results()
+    else:
+      dicts = []
+      for _ in range(self.opts.num_eval_iter):
+        dicts += self.eval_batch()
+      results = eval_metrics.aggregate(dicts)
     res_dir = self.opts.results_dir or os.path.join(self.opts.checkpoint_dir,
                                                     'results')
     os.makedirs(res_dir, exist_ok=True)

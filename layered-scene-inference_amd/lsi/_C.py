@@ -152,6 +152,13 @@ SIGNATURES = {
                         [_I32, _F32, _F32] + [_VP] * 5),
     'lsi_compose_depth_bwd': (ctypes.c_int, [_I32, _I64] + [_VP] * 2 +
                               [_I32, _F32, _F32, _F32] + [_VP] * 3),
+    'lsi_eval_workspace_bytes': (_SZ, []),
+    'lsi_eval_view_metrics': (ctypes.c_int, [_I32] * 8 + [_VP] * 3 + [_I64] * 4 +
+                              [_VP] * 3 + [ctypes.c_uint32, _F32] + [_VP] * 2 +
+                              [_SZ, _VP]),
+    'lsi_eval_layer_metrics': (ctypes.c_int, ([_LP] + [_VP] * 6) * 2 + [_VP] * 2 +
+                               [_SZ, _VP]),
+    'lsi_disocclusion_mask': (ctypes.c_int, [_I32] * 5 + [_VP] * 3 + [_F32, _VP, _VP]),
     'lsi_render_planes': (ctypes.c_int, [ctypes.POINTER(LsiSceneDesc)] + [_VP] * 8),
     'lsi_render_planes_bwd_workspace_bytes': (_SZ, [ctypes.POINTER(LsiSceneDesc)]),
     'lsi_render_planes_bwd': (ctypes.c_int, [ctypes.POINTER(LsiSceneDesc)] +

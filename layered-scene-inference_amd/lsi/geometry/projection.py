@@ -106,10 +106,23 @@ def inverse_projection_matrix(k_s, k_t, rot, t):
 
 
 def disocclusion_mask(disps_src, disps_trg, pixel_coords_src, src2trg_mat,
-                      thresh=1e-2):
+                      thresh=1e-2, fused=False):
   """1 where a source pixel is dis-occluded in the target view (reference
-  projection.py:109-150).  disps: B x H x W x 1; returns B x H x W x 1."""
+  projection.py:109-150).  disps: B x H x W x 1; returns B x H x W x 1.
+
+  fused=True computes the mask in one HIP launch (lsi_disocclusion_mask) when
+  `pixel_coords_src` is the pixel-centre grid (None means the grid); any other
+  coordinates take the op route below."""
   from lsi.geometry import sampling  # pylint: disable=g-import-not-at-top
+  if fused:
+    from lsi.geometry import ldi as ldi_utils  # pylint: disable=g-import-not-at-top
+    if ldi_utils._is_pixel_grid(pixel_coords_src, disps_src.unsqueeze(0)):
+      from lsi.nnutils import _hip_eval  # pylint: disable=g-import-not-at-top
+      return _hip_eval.disocclusion_mask(disps_src, disps_trg, src2trg_mat, thresh)
+  if pixel_coords_src is None:
+    pixel_coords_src = nn_helpers.pixel_coords(
+        disps_src.shape[0], disps_src.shape[1], disps_src.shape[2],
+        device=disps_src.device)
   _, h_t, w_t, _ = disps_trg.shape
   coords_src = torch.cat([pixel_coords_src, disps_src], dim=-1)
   coords_trg = nn_helpers.transform_pts(coords_src, src2trg_mat)

@@ -1,0 +1,165 @@
+"""ctypes bindings of the fused evaluation kernels (include/lsi_hip.h,
+csrc/lsi_eval.hip): the view-synthesis and per-layer metrics accumulated into a
+device array of SLOT_COUNT doubles, and the dis-occlusion mask.  For tensors on
+a ROCm device; there is no fallback: a missing library raises in lsi._C.lib().
+None of these calls synchronises with the host."""
+import ctypes
+
+import torch
+
+from lsi import _C
+
+# the header's LSI_EVAL_* slots of the accumulator
+SLOTS = {
+    'COMPOSE_SUM': 0, 'COMPOSE_NORM': 1,
+    'COMPOSE_DISOCC_SUM': 2, 'COMPOSE_DISOCC_NORM': 3,
+    'DEPTH_SUM': 4, 'DEPTH_NORM': 5,
+    'DEPTH_DISOCC_SUM': 6, 'DEPTH_DISOCC_NORM': 7,
+    'PSNR_SUM': 8, 'PSNR_COUNT': 9,
+    'FG_TEX_SUM': 10, 'FG_DISP_SUM': 11, 'FG_NORM': 12,
+    'BG_TEX_SUM': 13, 'BG_DISP_SUM': 14, 'BG_NORM': 15,
+}
+SLOT_COUNT = 16
+LSI_EVAL_DISOCC_U8, LSI_EVAL_VALID_GT = 1, 2
+
+# metric name (the keys of eval_metrics.aggregate) -> (sum slot, normaliser slot)
+METRICS = {
+    'compose_splat_loss': ('COMPOSE_SUM', 'COMPOSE_NORM'),
+    'compose_splat_loss_disocc': ('COMPOSE_DISOCC_SUM', 'COMPOSE_DISOCC_NORM'),
+    'depth_splat_loss': ('DEPTH_SUM', 'DEPTH_NORM'),
+    'depth_splat_loss_disocc': ('DEPTH_DISOCC_SUM', 'DEPTH_DISOCC_NORM'),
+    'psnr': ('PSNR_SUM', 'PSNR_COUNT'),
+    'fg_tex_error': ('FG_TEX_SUM', 'FG_NORM'),
+    'fg_disp_error': ('FG_DISP_SUM', 'FG_NORM'),
+    'bg_tex_error': ('BG_TEX_SUM', 'BG_NORM'),
+    'bg_disp_error': ('BG_DISP_SUM', 'BG_NORM'),
+}
+
+
+def workspace(dev):
+  n = int(_C.lib().lsi_eval_workspace_bytes())
+  return torch.empty((n,), dtype=torch.uint8, device=dev), n
+
+
+def _check_acc(acc, dev):
+  if (acc.device != dev or acc.dtype != torch.float64 or
+      acc.numel() != SLOT_COUNT or not acc.is_contiguous()):
+    raise RuntimeError('the accumulator is %d contiguous float64 on %s' %
+                       (SLOT_COUNT, dev))
+
+
+def _map(t, shape, what):
+  """A contiguous B x H x W (x 1) map; no copy when it already is one."""
+  if t is None:
+    return None
+  if tuple(t.shape) not in (shape, shape + (1,)):
+    raise ValueError('%s must be %s (x 1), got %s' % (what, shape, tuple(t.shape)))
+  return t.contiguous()
+
+
+def view_metrics(acc, ws, ws_bytes, recons, recons_disp, target, x_min, y_min,
+                 valid=None, disocc=None, gt_disp=None, valid_above=None):
+  """lsi_eval_view_metrics: adds the metrics of one rendered view to `acc`.
+  recons nl x B x Ht x Wt x 3, recons_disp nl x B x Ht x Wt x 1 or None, target
+  B x H x W x 3 (any strides); valid / disocc / gt_disp B x H x W (x 1) or None,
+  disocc fp32 or bool.  With valid_above, `valid` is a map and a pixel is valid
+  where it exceeds that value."""
+  dev = _C.require_device(recons, recons_disp, target, valid, gt_disp)
+  _check_acc(acc, dev)
+  nl, b, ht, wt, c = recons.shape
+  if c != 3 or tuple(target.shape[:1] + target.shape[3:]) != (b, 3):
+    raise ValueError('view_metrics: 3-channel images of one batch size')
+  _, h, w, _ = target.shape
+  if h % ht or w % wt:
+    raise ValueError('view_metrics: the target (%d x %d) is no integer multiple '
+                     'of the rendering (%d x %d)' % (h, w, ht, wt))
+  recons = recons.contiguous()
+  if recons_disp is not None:
+    if tuple(recons_disp.shape) != (nl, b, ht, wt, 1):
+      raise ValueError('view_metrics: recons_disp must be %s' % ((nl, b, ht, wt, 1),))
+    recons_disp = recons_disp.contiguous()
+  flags = 0
+  if disocc is not None:
+    if not disocc.is_cuda or disocc.device != dev:
+      raise RuntimeError('lsi HIP ops need tensors on a ROCm GPU (got device %s); '
+                         'there is no CPU fallback' % disocc.device)
+    if disocc.dtype in (torch.bool, torch.uint8):
+      flags |= LSI_EVAL_DISOCC_U8
+    elif disocc.dtype != torch.float32:
+      raise RuntimeError('the dis-occlusion mask is fp32 or bool (got %s)' %
+                         disocc.dtype)
+  valid = _map(valid, (b, h, w), 'valid_mask')
+  disocc = _map(disocc, (b, h, w), 'disocc_mask')
+  gt_disp = _map(gt_disp, (b, h, w), 'gt_disp_trg')
+  if valid_above is not None and valid is not None:
+    flags |= LSI_EVAL_VALID_GT
+  ts = target.stride()
+  rc = _C.lib().lsi_eval_view_metrics(
+      nl, b, ht, wt, h, w, int(x_min), int(y_min), _C.ptr(recons),
+      _C.ptr(recons_disp), _C.ptr(target), ts[0], ts[1], ts[2], ts[3],
+      _C.ptr(valid), _C.ptr(disocc), _C.ptr(gt_disp), flags,
+      0.0 if valid_above is None else float(valid_above), _C.ptr(acc),
+      _C.ptr(ws), ws_bytes, _C.stream_ptr(dev))
+  _C.check(rc, 'lsi_eval_view_metrics')
+
+
+def _layer_desc(tex, disp, bg_layer_disp):
+  d = _C.LsiLossDesc()
+  d.L, d.B, d.H, d.W = tex.shape[:4]
+  d.img_sl, d.img_sb, d.img_sy, d.img_sx, d.img_sc = tex.stride()
+  d.disp_sl, d.disp_sb, d.disp_sy, d.disp_sx = disp.stride()[:4]
+  d.bg_layer_disp = float(bg_layer_disp)
+  return d
+
+
+def layer_metrics(acc, ws, ws_bytes, ldi_src, ldi_trg, imgs_src, imgs_trg, gt,
+                  bg_layer_disp):
+  """lsi_eval_layer_metrics: ldi_* = [tex L x B x H x W x 3, masks, disps
+  L x B x H x W x 1] with any strides; gt as eval_metrics.layer_prediction_metrics
+  takes it.  The four *_bg entries come together or not at all."""
+  bg_keys = ('src_gt_disp_bg', 'src_gt_tex_bg', 'trg_gt_disp_bg', 'trg_gt_tex_bg')
+  n_bg = sum(k in gt for k in bg_keys)
+  if n_bg not in (0, len(bg_keys)):
+    raise ValueError('layer_metrics: gt needs all of %s or none (got %s)' %
+                     (bg_keys, sorted(k for k in bg_keys if k in gt)))
+  views = []
+  for ldi, img, side in ((ldi_src, imgs_src, 'src'), (ldi_trg, imgs_trg, 'trg')):
+    tex, disp = ldi[0], ldi[2]
+    nl, b, h, w, c = tex.shape
+    if c != 3 or tuple(disp.shape) != (nl, b, h, w, 1):
+      raise ValueError('layer_metrics: tex L x B x H x W x 3, disps L x B x H x W x 1')
+    if tuple(img.shape) != (b, h, w, 3):
+      raise ValueError('layer_metrics: images must be %s' % ((b, h, w, 3),))
+    views.append((tex, disp, img.contiguous(),
+                  _map(gt[side + '_gt_disp'], (b, h, w), side + '_gt_disp'),
+                  _map(gt.get(side + '_gt_disp_bg'), (b, h, w), side + '_gt_disp_bg'),
+                  None if n_bg == 0 else gt[side + '_gt_tex_bg'].contiguous()))
+    if n_bg and tuple(views[-1][5].shape) != (b, h, w, 3):
+      raise ValueError('layer_metrics: %s_gt_tex_bg must be %s' % (side, (b, h, w, 3)))
+  dev = _C.require_device(*[t for v in views for t in v])
+  _check_acc(acc, dev)
+  args = []
+  for v in views:
+    args += [ctypes.byref(_layer_desc(v[0], v[1], bg_layer_disp))]
+    args += [_C.ptr(t) for t in v]
+  rc = _C.lib().lsi_eval_layer_metrics(*args, _C.ptr(acc), _C.ptr(ws), ws_bytes,
+                                       _C.stream_ptr(dev))
+  _C.check(rc, 'lsi_eval_layer_metrics')
+
+
+def disocclusion_mask(disps_src, disps_trg, src2trg_mat, thresh):
+  """lsi_disocclusion_mask: disps B x H x W x 1, src2trg_mat B x 4 x 4; the source
+  points are the pixel centres.  Returns the B x Hs x Ws x 1 fp32 mask."""
+  dev = _C.require_device(disps_src, disps_trg, src2trg_mat)
+  b, hs, ws_, _ = disps_src.shape
+  _, ht, wt, _ = disps_trg.shape
+  if tuple(src2trg_mat.shape) != (b, 4, 4) or disps_trg.shape[0] != b:
+    raise ValueError('disocclusion_mask: src2trg_mat must be %s' % ((b, 4, 4),))
+  disps_src, disps_trg = disps_src.contiguous(), disps_trg.contiguous()
+  mat = src2trg_mat.contiguous()
+  mask = torch.empty((b, hs, ws_, 1), dtype=torch.float32, device=dev)
+  rc = _C.lib().lsi_disocclusion_mask(b, hs, ws_, ht, wt, _C.ptr(disps_src),
+                                      _C.ptr(disps_trg), _C.ptr(mat), float(thresh),
+                                      _C.ptr(mask), _C.stream_ptr(dev))
+  _C.check(rc, 'lsi_disocclusion_mask')
+  return mask

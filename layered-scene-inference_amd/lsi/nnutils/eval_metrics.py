@@ -7,6 +7,7 @@ variant, rendered-disparity error, and PSNR.  Metrics are returned as
 """
 import torch
 
+from lsi import _C
 from lsi.geometry import ldi as ldi_utils
 from lsi.loss import loss as loss_utils
 
@@ -111,3 +112,80 @@ def layer_prediction_metrics(ldi_src, ldi_trg, imgs_src, imgs_trg, gt, opts):
     out['bg_tex_error'] = (bg_tex, n_bg)
     out['bg_disp_error'] = (bg_disp, n_bg)
   return out
+
+
+class MetricAccumulator(object):
+  """The same metrics accumulated on the device by the fused kernels of
+  csrc/lsi_eval.hip: every add_* call is one metric launch plus a one-block
+  finishing kernel that adds to 16 running doubles, with no host
+  synchronisation and no device-to-host copy; `sums()` reads them back in one
+  copy.  `results()` is what `aggregate` gives over the op route's dicts, with
+  one difference: a view without any scored cell (an empty centre) adds nothing
+  to `psnr`, where the op route adds NaN.  The same sequence of calls gives the
+  same 16 doubles bit for bit."""
+
+  def __init__(self, device):
+    from lsi.nnutils import _hip_eval  # pylint: disable=g-import-not-at-top
+    self._hip = _hip_eval
+    self.device = torch.device(device)
+    self.acc = torch.zeros((_hip_eval.SLOT_COUNT,), dtype=torch.float64,
+                           device=self.device)
+    self._ws = None
+
+  def _workspace(self):
+    if self._ws is None:
+      self._ws = self._hip.workspace(self.acc.device)
+    return self._ws
+
+  def reset(self):
+    self.acc.zero_()
+
+  def add_rendered(self, recons, recons_disp, imgs_trg, splat_bdry_ignore,
+                   valid_mask=None, disocc_mask=None, gt_disp_trg=None,
+                   valid_above=None):
+    """Scores an existing rendering (recons nl x B x Ht x Wt x 3, recons_disp
+    nl x B x Ht x Wt x 1 or None) against imgs_trg B x H x W x 3; the masks as
+    `view_synthesis_metrics` takes them, disocc_mask fp32 or bool.  With
+    valid_above, valid_mask is a map (the ground-truth disparity, say) and a
+    pixel is valid where it exceeds that value: the caller's
+    `(map > valid_above).float()` without its two launches."""
+    _C.require_device(recons, recons_disp, imgs_trg, valid_mask, gt_disp_trg)
+    ht, wt = recons.shape[2:4]
+    ws, n = self._workspace()
+    self._hip.view_metrics(
+        self.acc, ws, n, recons, recons_disp, imgs_trg,
+        loss_utils._py2_round(wt * splat_bdry_ignore),
+        loss_utils._py2_round(ht * splat_bdry_ignore), valid=valid_mask,
+        disocc=disocc_mask, gt_disp=gt_disp_trg, valid_above=valid_above)
+
+  def add_view_synthesis(self, ldi_src, pixel_coords, k_s, k_t, rot, t, imgs_trg,
+                         opts, valid_mask=None, disocc_mask=None,
+                         gt_disp_trg=None, valid_above=None):
+    """`view_synthesis_metrics` with the arithmetic after the render fused: the
+    same forward_splat call, then `add_rendered`."""
+    recons, _, recons_disp = ldi_utils.forward_splat(
+        ldi_src, pixel_coords, k_s, k_t, rot, t, compose_layers=True,
+        compute_trg_disp=True, trg_downsampling=opts.trg_splat_downsampling,
+        zbuf_scale=opts.zbuf_scale, bg_layer_disp=opts.bg_layer_disp,
+        max_disp=opts.max_disp)
+    self.add_rendered(recons, recons_disp, imgs_trg, opts.splat_bdry_ignore,
+                      valid_mask=valid_mask, disocc_mask=disocc_mask,
+                      gt_disp_trg=gt_disp_trg, valid_above=valid_above)
+
+  def add_layer_prediction(self, ldi_src, ldi_trg, imgs_src, imgs_trg, gt, opts):
+    """`layer_prediction_metrics` in one pass over both views."""
+    _C.require_device(ldi_src[0], ldi_src[2], ldi_trg[0], ldi_trg[2], imgs_src,
+                      imgs_trg)
+    ws, n = self._workspace()
+    self._hip.layer_metrics(self.acc, ws, n, ldi_src, ldi_trg, imgs_src, imgs_trg,
+                            gt, opts.bg_layer_disp)
+
+  def sums(self):
+    """name -> (sum, norm) as Python floats, from ONE device-to-host copy."""
+    v = self.acc.tolist()
+    slot = self._hip.SLOTS
+    return {k: (v[slot[s]], v[slot[n]]) for k, (s, n) in self._hip.METRICS.items()}
+
+  def results(self):
+    """name -> sum / norm for every metric that was scored (norm > 0)."""
+    return {k: s / n for k, (s, n) in self.sums().items() if n > 0}

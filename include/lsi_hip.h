@@ -1155,6 +1155,42 @@ int lsi_fc_bwd(const LsiFcDesc* d, const void* x, const float* w, const void* dy
                const void* y, const float* z, const float* mean_rstd, void* dx, float* dw,
                float* dbeta, void* workspace, size_t workspace_bytes, lsi_stream_t stream);
 
+/*
+ * Exact AREA resize of a ragged batch of decoded uint8 images, one launch
+ * (lsi/data/kitti/data.py:area_resize of decode_png(path) * (1/255); reference
+ * lsi/data/kitti/data.py:247-266): out[m, i, k, c] is the coverage-weighted
+ * mean of image m over [i H/Ho, (i+1) H/Ho) x [k W/Wo, (k+1) W/Wo), divided by
+ * 255; H, W are the image's own, the scale may be below or above 1 on either
+ * axis.  Integer weights oy ox (in units of 1/Ho, 1/Wo) and a uint32 sum, then
+ * one conversion and one fp32 multiply by fl(1 / (255 H W)): independent of
+ * the summation order, bitwise reproducible, within 1.5 ulp of the exact
+ * rational, exactly 0 where the covered input is 0.
+ *   packed    device, uint8, 16-byte aligned, packed_bytes a multiple of 16
+ *             (the producer pads); image m is H x W x C interleaved at
+ *             packed + offset, rows W C bytes apart (any alignment).  No byte
+ *             outside [0, packed_bytes) is read.
+ *   desc_dev  the n descriptors on the device (8-byte aligned), read by the
+ *             kernel; desc_host the same n descriptors in host memory, checked
+ *             here before the launch (the two must agree)
+ *   out       device, float32 [n, Ho, Wo, Co], written fully
+ * LSI_ENULL for a NULL pointer; LSI_EINVAL for n outside [1, 65535], Co not 1
+ * or 3, a descriptor with C != Co, H or W <= 0, H W > LSI_IMAGE_MAX_PIXELS
+ * (255 H W must stay below 2^32), (Ho + 1)(H + 1) or (Wo + 1)(W + 1) >= 2^31,
+ * an offset that is negative or not a multiple of 16, offset + H W C >
+ * packed_bytes, or a misaligned pointer -- all before any launch.  No
+ * workspace, no allocation, no synchronisation, no state.
+ */
+#define LSI_IMAGE_MAX_PIXELS 16843009
+typedef struct LsiImageDesc {
+  int64_t offset;         /* bytes from `packed`, a multiple of 16           */
+  int32_t H, W, C;        /* the image's own size; C == Co                   */
+  int32_t reserved;       /* 0                                               */
+} LsiImageDesc;
+int lsi_area_resize_u8(int32_t n, const LsiImageDesc* desc_host,
+                       const LsiImageDesc* desc_dev, const uint8_t* packed,
+                       size_t packed_bytes, int32_t Ho, int32_t Wo, int32_t Co,
+                       float* out, lsi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,199 @@
+// Exact AREA resize of a ragged batch of uint8 images (gfx950): the arithmetic
+// of lsi/data/kitti/data.py:area_resize applied to decode_png(path) * (1/255)
+// (reference lsi/data/kitti/data.py:247-266, tf.image.resize_images(AREA)), for
+// n images of their own H x W in ONE launch.
+//
+// Integers: in units of 1/Ho the overlap of output row i with input row y is
+// oy = min((i+1) H, (y+1) Ho) - max(i H, y Ho), columns alike with W, Wo, and the
+// normalised weight is oy ox / (H W) exactly.  sum oy ox u8 <= 255 H W < 2^32 is
+// accumulated in uint32 -- no rounding, any order -- and finished by one
+// conversion and one fp32 multiply by fl(1 / (255 H W)): within 1.5 ulp of the
+// exact rational, bitwise reproducible, 0 where the covered input is 0.
+//
+// Bound: HBM streaming (every input byte once per tile that covers it, 4 output
+// bytes per input byte at most); about 30 MB for 8 KITTI images, so the fixed
+// costs count: one launch, 256 threads per tile of 8 output rows x 32 RGB pixels
+// (12 bytes per thread, the lanes of a row contiguous) or x 128 one-channel
+// pixels (one float4 per thread); a pixel's column weight is formed once for
+// its channels.
+// Loads: the input rows of a tile start at any byte address (W C = 183 is legal).
+// They are staged through LDS in chunks of CHUNK_ROWS rows x at most
+// CHUNK_BYTES bytes with aligned 16-byte loads: a row is read from its address
+// rounded down to 16 and its phase (0..15) is kept in LDS, so the taps read
+// lds[row][phase + byte].  The buffer is 16-byte aligned and a multiple of 16
+// bytes long, so an aligned 16-byte load that holds one valid byte lies inside
+// it.  The tap loops run over whatever the ratio gives (1-2 taps when
+// upscaling, 7 x 7 for a factor 5); tiles whose input exceeds one chunk loop
+// over chunks with the sums kept in registers.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/lsi_hip.h"
+
+namespace {
+
+constexpr int TILE_ROWS = 8;     // output rows per workgroup
+constexpr int TILE_COLS = 32;    // threads along a row
+constexpr int THREADS = TILE_ROWS * TILE_COLS;
+constexpr int CHUNK_ROWS = 16;
+constexpr int PITCH = 256;                 // LDS bytes per staged row
+constexpr int CHUNK_BYTES = PITCH - 16;    // payload: the phase takes up to 15
+constexpr int ROW_VECS = PITCH / 16;
+
+// pixels per thread: one RGB pixel (a 12-byte store, lanes contiguous) or four
+// one-channel pixels (a float4)
+__host__ __device__ constexpr int pixels_per_thread(int C) { return C == 1 ? 4 : 1; }
+
+struct ImageArgs {
+  int n, Ho, Wo;
+  int vec_store;  // C = 1: Wo is a multiple of 4 and out is 16-byte aligned
+  const LsiImageDesc* desc;
+  const uint8_t* packed;
+  float* out;
+};
+
+__device__ __forceinline__ int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+template <int C>
+__global__ __launch_bounds__(THREADS) void area_resize_u8_kernel(ImageArgs a) {
+  constexpr int P = pixels_per_thread(C);
+  constexpr int TILE_PX = TILE_COLS * P;
+  constexpr int CHUNK_COLS = CHUNK_BYTES / C;
+  __shared__ __attribute__((aligned(16))) uint8_t lds[CHUNK_ROWS * PITCH];
+  const LsiImageDesc d = a.desc[blockIdx.z];
+  const int H = d.H, W = d.W, Ho = a.Ho, Wo = a.Wo;
+  const uint8_t* src = a.packed + d.offset;  // 16-byte aligned (validated)
+
+  // the tile: output rows [i0, i1), output pixels [k0, k1) of each row
+  const int i0 = blockIdx.y * TILE_ROWS, i1 = min(i0 + TILE_ROWS, Ho);
+  const int k0 = blockIdx.x * TILE_PX, k1 = min(k0 + TILE_PX, Wo);
+  // ... and the input rows / columns it covers (products < 2^31: validated)
+  const int ty0 = (i0 * H) / Ho, ty1 = ceil_div(i1 * H, Ho);
+  const int tx0 = (k0 * W) / Wo, tx1 = ceil_div(k1 * W, Wo);
+
+  // this thread: output row i, pixels [kb, kb + P)
+  const int i = i0 + (int)threadIdx.x / TILE_COLS;
+  const int kb = k0 + P * ((int)threadIdx.x % TILE_COLS);
+  const bool row_ok = i < i1;
+  int xs[P], xe[P];
+  uint32_t acc[P * C];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const bool ok = row_ok && kb + p < k1;
+    xs[p] = ok ? ((kb + p) * W) / Wo : 0;
+    xe[p] = ok ? ceil_div((kb + p + 1) * W, Wo) : 0;  // empty range: no taps
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[p * C + c] = 0u;
+  }
+  const int ys = row_ok ? (i * H) / Ho : 0;
+  const int ye = row_ok ? ceil_div((i + 1) * H, Ho) : 0;
+
+  for (int cy = ty0; cy < ty1; cy += CHUNK_ROWS) {
+    const int rows = min(CHUNK_ROWS, ty1 - cy);
+    for (int cx = tx0; cx < tx1; cx += CHUNK_COLS) {
+      const int ncols = min(CHUNK_COLS, tx1 - cx);
+      const int nbytes = ncols * C;
+      __syncthreads();  // the previous chunk has been read
+      for (int s = threadIdx.x; s < rows * ROW_VECS; s += THREADS) {
+        const int r = s / ROW_VECS, q = s - r * ROW_VECS;
+        const int first = ((cy + r) * W + cx) * C;  // byte offset in the image
+        const int phase = first & 15;
+        if (q * 16 < phase + nbytes) {
+          const uint4 v =
+              *reinterpret_cast<const uint4*>(src + (first - phase) + q * 16);
+          *reinterpret_cast<uint4*>(lds + r * PITCH + q * 16) = v;
+        }
+      }
+      __syncthreads();
+      const int y_lo = max(ys, cy), y_hi = min(ye, cy + rows);
+      for (int y = y_lo; y < y_hi; ++y) {
+        const uint32_t oy = (uint32_t)(min((i + 1) * H, (y + 1) * Ho) - max(i * H, y * Ho));
+        const uint8_t* row = lds + (y - cy) * PITCH + (((y * W + cx) * C) & 15);
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+          const int k = kb + p;
+          const int x_lo = max(xs[p], cx), x_hi = min(xe[p], cx + ncols);
+          uint32_t sx[C];
+#pragma unroll
+          for (int c = 0; c < C; ++c) sx[c] = 0u;
+          for (int x = x_lo; x < x_hi; ++x) {
+            const uint32_t ox =
+                (uint32_t)(min((k + 1) * W, (x + 1) * Wo) - max(k * W, x * Wo));
+#pragma unroll
+            for (int c = 0; c < C; ++c) sx[c] += ox * row[(x - cx) * C + c];
+          }
+#pragma unroll
+          for (int c = 0; c < C; ++c) acc[p * C + c] += oy * sx[c];
+        }
+      }
+    }
+  }
+
+  if (!row_ok || kb >= k1) return;
+  const float scale = (float)(1.0 / (255.0 * (double)H * (double)W));
+  float* o = a.out + (((size_t)blockIdx.z * Ho + i) * Wo + kb) * C;
+  if constexpr (C == 3) {  // 12 bytes per lane, the lanes of a row contiguous
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = (float)acc[c] * scale;
+  } else {
+    if (a.vec_store) {  // kb + 4 <= k1: both are multiples of 4
+      float4 v;
+      v.x = (float)acc[0] * scale;
+      v.y = (float)acc[1] * scale;
+      v.z = (float)acc[2] * scale;
+      v.w = (float)acc[3] * scale;
+      *reinterpret_cast<float4*>(o) = v;
+    } else {
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+        if (kb + p < k1) o[p] = (float)acc[p] * scale;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsi_area_resize_u8(int32_t n, const LsiImageDesc* desc_host,
+                       const LsiImageDesc* desc_dev, const uint8_t* packed,
+                       size_t packed_bytes, int32_t Ho, int32_t Wo, int32_t Co,
+                       float* out, lsi_stream_t stream) {
+  if (!desc_host || !desc_dev || !packed || !out) return LSI_ENULL;
+  if (n <= 0 || n > 65535 || Ho <= 0 || Wo <= 0 || (Co != 1 && Co != 3))
+    return LSI_EINVAL;
+  if (((uintptr_t)packed & 15) || (packed_bytes & 15) || ((uintptr_t)out & 3) ||
+      ((uintptr_t)desc_dev & 7))
+    return LSI_EINVAL;
+  if ((int64_t)Wo * Co > INT32_MAX - 4 * THREADS) return LSI_EINVAL;
+  for (int32_t m = 0; m < n; ++m) {
+    const LsiImageDesc& d = desc_host[m];
+    if (d.H <= 0 || d.W <= 0 || d.C != Co) return LSI_EINVAL;
+    // the uint32 accumulator: 255 H W < 2^32
+    if ((int64_t)d.H * d.W > LSI_IMAGE_MAX_PIXELS) return LSI_EINVAL;
+    // the kernel's int32 products (i + 1) H, (y + 1) Ho, (k + 1) W, (x + 1) Wo
+    if ((int64_t)(Ho + 1) * (d.H + 1) > INT32_MAX ||
+        (int64_t)(Wo + 1) * (d.W + 1) > INT32_MAX)
+      return LSI_EINVAL;
+    const int64_t bytes = (int64_t)d.H * d.W * d.C;
+    if (d.offset < 0 || (d.offset & 15) || (uint64_t)d.offset > packed_bytes ||
+        (uint64_t)bytes > packed_bytes - (uint64_t)d.offset)
+      return LSI_EINVAL;
+  }
+  ImageArgs a;
+  a.n = n; a.Ho = Ho; a.Wo = Wo;
+  a.vec_store = (Wo % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
+  a.desc = desc_dev; a.packed = packed; a.out = out;
+  const int tile_px = TILE_COLS * pixels_per_thread(Co);
+  const dim3 grid((Wo + tile_px - 1) / tile_px, (Ho + TILE_ROWS - 1) / TILE_ROWS, n);
+  if (grid.y > 65535u) return LSI_EINVAL;
+  if (Co == 1)
+    hipLaunchKernelGGL(area_resize_u8_kernel<1>, grid, dim3(THREADS), 0,
+                       (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(area_resize_u8_kernel<3>, grid, dim3(THREADS), 0,
+                       (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+}
+
+}  // extern "C"

@@ -58,6 +58,14 @@ def build_parser():
     help='no KITTI files: procedural stereo pairs seen through the KITTI camera '
     'model and constants (throughput runs, tests).  Without this switch a '
     'missing --kitti_data_root is an error')
+  a('--data_workers', type=int, default=0,
+    help='KITTI files: threads that decode PNGs ahead of the step '
+    '(lsi/data/kitti/pipeline.py; clamped to [1, 16] and divided by the world '
+    'size).  0 = the synchronous loader')
+  a('--kitti_resize', default='host', choices=['host', 'device'],
+    help="KITTI files: the AREA resize in NumPy ('host') or as one HIP launch "
+    "per batch on the decoded uint8 pixels ('device': csrc/lsi_image.hip; "
+    'needs a ROCm device)')
   a('--self_cons_wt', type=float, default=1.0)
   a('--l0_self_cons', type=_bool, default=False)
   a('--indep_splat_wt', type=float, default=1.0)
@@ -246,6 +254,12 @@ class KittiBatches(object):
     return tuple(torch.as_tensor(a, dtype=torch.float32)
                  for a in self.loader.forward(bs))
 
+  def close(self):
+    """Stops a prefetching loader's workers (nothing to do otherwise)."""
+    close = getattr(self.loader, 'close', None)
+    if close is not None:
+      close()
+
 
 class Trainer(train_utils.Trainer):
   """LDI prediction trainer (reference ldi_enc_dec.py:126-410)."""
@@ -273,7 +287,20 @@ class Trainer(train_utils.Trainer):
             '--dataset=kitti: no directory %r (--kitti_data_root); pass '
             '--kitti_procedural=true for procedural pairs with KITTI cameras'
             % opts.kitti_data_root)
-      self.data_loader = KittiBatches(kitti_data.DataLoader(opts), self.rank)
+      loader = kitti_data.DataLoader(opts)
+      workers = int(getattr(opts, 'data_workers', 0))
+      resize = getattr(opts, 'kitti_resize', 'host')
+      if workers != 0 or resize != 'host':
+        if resize == 'device' and self.device.type != 'cuda':
+          raise ValueError(
+              '--kitti_resize device runs the AREA resize as a HIP kernel: it '
+              'needs a ROCm device (this run is on %s); use --kitti_resize host'
+              % self.device)
+        from lsi.data.kitti import pipeline  # pylint: disable=g-import-not-at-top
+        loader = pipeline.PrefetchLoader(
+            loader, workers=workers, resize=resize, device=self.device,
+            world_size=self.world)
+      self.data_loader = KittiBatches(loader, self.rank)
     else:
       self.data_loader = SyntheticPairs(opts, self.device, 1234 + self.rank)
     bs = self.opts.batch_size
@@ -480,7 +507,12 @@ def main(argv=None):
   opts = apply_dataset_overrides(build_parser().parse_args(argv))
   trainer = Trainer(opts)
   trainer.setup()
-  trainer.train()
+  try:
+    trainer.train()
+  finally:
+    close = getattr(trainer.data_loader, 'close', None)
+    if close is not None:
+      close()  # a prefetching loader's decode threads
   if trainer.dist is not None:
     trainer.dist.destroy_process_group()
   return trainer

@@ -186,7 +186,12 @@ def main(argv=None):
     opts.debug_synth_texture = False
     opts.synth_dl_eval_data = True
   tester = Tester(opts)
-  results = tester.test()
+  try:
+    results = tester.test()
+  finally:
+    close = getattr(getattr(tester.trainer, 'data_loader', None), 'close', None)
+    if close is not None:
+      close()  # a prefetching loader's decode threads (--data_workers)
   if tester.trainer.rank == 0:
     print(json.dumps({'restored': tester.restored, 'results': results}))
 

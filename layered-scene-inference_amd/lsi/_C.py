@@ -26,6 +26,7 @@ LSI_PATH_TILE = 4
 LSI_SCENE_IMG, LSI_SCENE_DISP, LSI_SCENE_IMG_ROOM, LSI_SCENE_DISP_ROOM = 1, 2, 4, 8
 LSI_SCENE_MAX_PLANES = 16
 LSI_FC_BN, LSI_FC_X_F32, LSI_FC_OUT_F32 = 1, 2, 4
+LSI_IMAGE_MAX_PIXELS = 16843009
 PATH_NAMES = {1: 'atomic', 2: 'rowband', 3: 'stream', 4: 'tile'}
 
 _c_f = ctypes.POINTER(ctypes.c_float)
@@ -95,6 +96,11 @@ class LsiConvIO(ctypes.Structure):
                                               'bn_workspace', 'workspace')] +
               [('workspace_bytes', ctypes.c_size_t), ('c1', ctypes.c_int32),
                ('groups', ctypes.c_int32)])
+
+
+class LsiImageDesc(ctypes.Structure):
+  _fields_ = ([('offset', ctypes.c_int64)] +
+              [(n, ctypes.c_int32) for n in ('H', 'W', 'C', 'reserved')])
 
 
 # name -> (restype, argtypes); every symbol include/lsi_hip.h declares.
@@ -205,6 +211,8 @@ SIGNATURES = {
     'lsi_fc_workspace_bytes': (_SZ, [ctypes.POINTER(LsiFcDesc)]),
     'lsi_fc_fwd': (ctypes.c_int, [ctypes.POINTER(LsiFcDesc)] + [_VP] * 7 + [_SZ, _VP]),
     'lsi_fc_bwd': (ctypes.c_int, [ctypes.POINTER(LsiFcDesc)] + [_VP] * 10 + [_SZ, _VP]),
+    'lsi_area_resize_u8': (ctypes.c_int, [_I32, _VP, _VP, _VP, _SZ] + [_I32] * 3 +
+                           [_VP, _VP]),
 }
 
 _lib = None

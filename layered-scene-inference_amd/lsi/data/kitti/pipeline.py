@@ -1,0 +1,358 @@
+"""Prefetching KITTI loader: PNG decode on a pool of threads running ahead of
+the step, the AREA resize on the host (in the worker) or on the device (one
+launch of csrc/lsi_image.hip per output tensor of a batch).
+
+`PrefetchLoader` wraps data.DataLoader and returns what its forward() returns,
+for the same samples in the same order: the indices of every batch -- prefetched
+ones included -- are drawn from the wrapped loader's own RNG by the consuming
+thread, in the sequence the synchronous loader draws them.
+
+  workers   threads that decode (Pillow releases the GIL while it inflates and
+            unfilters a PNG), clamped to [1, 16] and divided by the world size:
+            the ranks of one command stay within 16 threads together.  Never
+            sized from the machine's CPU count.
+  resize    'host':   data._load_image in the worker; values bit for bit those
+                      of the synchronous loader.
+            'device': the worker writes the decoded uint8 pixels and one
+                      descriptor per image straight into a pinned staging
+                      buffer; forward() issues one non-blocking upload and the
+                      resize launches on the current stream and returns device
+                      tensors for images and disparities, NumPy arrays for the
+                      cameras (data.pair_cameras, untouched).
+  prefetch_depth  batches decoded ahead of the one being returned.
+
+A staging buffer goes back to the pool only when an event recorded behind its
+upload has completed.  A decode error is raised from the forward() that owns the
+sample and names the file.  close() stops the workers; a collected loader or an
+exiting interpreter does not wait on more than the decodes already running.
+"""
+import collections
+import threading
+import time
+import weakref
+from concurrent import futures
+
+import numpy as np
+
+from lsi.data.kitti import data as kitti_data
+
+MAX_THREADS = 16
+DESC_DTYPE = np.dtype([('offset', '<i8'), ('H', '<i4'), ('W', '<i4'),
+                       ('C', '<i4'), ('reserved', '<i4')])  # _C.LsiImageDesc
+
+
+def pool_size(workers, world_size=1):
+  """Threads of one rank: the option clamped to [1, 16], shared by the ranks."""
+  return max(1, min(MAX_THREADS, int(workers)) // max(1, int(world_size)))
+
+
+def _round16(n):
+  return (int(n) + 15) // 16 * 16
+
+
+def decode_u8(path, nc):
+  """data.decode_png's pixels as uint8, first nc channels: H x W x nc.  16-bit
+  PNGs keep their high byte."""
+  from PIL import Image  # pylint: disable=g-import-not-at-top
+  with Image.open(path) as im:
+    if im.mode in ('I;16', 'I;16B', 'I;16L', 'I'):
+      arr = (np.asarray(im).astype(np.int64) >> 8).astype(np.uint8)
+    elif im.mode in ('L', 'P', '1', 'LA'):
+      arr = np.asarray(im.convert('L'), np.uint8)
+    else:
+      arr = np.asarray(im.convert('RGB'), np.uint8)
+  if arr.ndim == 2:
+    arr = arr[:, :, None]
+  if arr.shape[2] < nc:
+    raise ValueError('%s has %d channels, %d needed' % (path, arr.shape[2], nc))
+  return arr[:, :, :nc]
+
+
+def area_resize_u8(packed, desc_host, desc_dev, n, h, w, nc, out=None):
+  """lsi_area_resize_u8 on the current stream: `packed` a uint8 device tensor
+  (16-byte aligned, a multiple of 16 long), desc_host a DESC_DTYPE array of n
+  records, desc_dev the address of their device copy.  Returns float32
+  [n, h, w, nc] on packed's device."""
+  import torch  # pylint: disable=g-import-not-at-top
+  from lsi import _C  # pylint: disable=g-import-not-at-top
+  if not packed.is_cuda:
+    raise RuntimeError('the device AREA resize needs a ROCm GPU (got device %s); '
+                       'there is no CPU fallback' % packed.device)
+  if packed.dtype != torch.uint8 or not packed.is_contiguous():
+    raise RuntimeError('packed must be a contiguous uint8 tensor')
+  desc_host = np.ascontiguousarray(desc_host, DESC_DTYPE)
+  if desc_host.shape != (n,):
+    raise ValueError('%d descriptors for %d images' % (desc_host.size, n))
+  if out is None:
+    out = torch.empty((n, h, w, nc), dtype=torch.float32, device=packed.device)
+  _C.check(_C.lib().lsi_area_resize_u8(
+      n, desc_host.ctypes.data, int(desc_dev), packed.data_ptr(), packed.numel(),
+      h, w, nc, out.data_ptr(), _C.stream_ptr(packed.device)),
+           'lsi_area_resize_u8')
+  return out
+
+
+class _Staging(object):
+  """One pinned buffer: [descriptors | pixel bytes], filled by the workers of
+  one batch.  alloc() hands out 16-byte aligned ranges; a range that does not
+  fit is refused and the image travels as its own array (the batch is then
+  re-packed into a larger buffer)."""
+
+  def __init__(self, n_desc, capacity):
+    import torch  # pylint: disable=g-import-not-at-top
+    self.header = _round16(n_desc * DESC_DTYPE.itemsize)
+    self.capacity = _round16(capacity)
+    self.tensor = torch.empty(self.header + self.capacity + 16, dtype=torch.uint8,
+                              pin_memory=True)
+    self.bytes = self.tensor.numpy()
+    self.desc = self.bytes[:n_desc * DESC_DTYPE.itemsize].view(DESC_DTYPE)
+    self.lock = threading.Lock()
+    self.reset()
+
+  def reset(self):
+    self.used = self.header
+    self.wanted = self.header
+
+  def alloc(self, nbytes):
+    nbytes = _round16(nbytes)
+    with self.lock:
+      self.wanted += nbytes
+      if self.used + nbytes > self.header + self.capacity:
+        return None
+      off = self.used
+      self.used += nbytes
+      return off
+
+
+def _host_task(stop, path, h, w, nc):
+  if stop.is_set():
+    raise RuntimeError('the loader was closed')
+  return kitti_data._load_image(path, h, w, nc)  # pylint: disable=protected-access
+
+
+def _device_task(stop, path, nc, staging, slot):
+  """Decodes `path` into `staging` and fills descriptor `slot`.  Returns
+  (original shape, None) or, when the buffer is full, (shape, pixel array)."""
+  if stop.is_set():
+    raise RuntimeError('the loader was closed')
+  arr = decode_u8(path, nc)
+  h, w = arr.shape[:2]
+  if h * w > 16843009:
+    raise ValueError('%s: %d x %d pixels exceed the resize kernel\'s bound' %
+                     (path, h, w))
+  off = staging.alloc(arr.size)
+  if off is None:
+    return (h, w, nc), np.ascontiguousarray(arr)
+  staging.bytes[off:off + arr.size].reshape(arr.shape)[...] = arr
+  staging.desc[slot] = (off, h, w, nc, 0)
+  return (h, w, nc), None
+
+
+def _named(path, err):
+  """`err` if it names the file, else an error of its type's family that does."""
+  if path in str(err):
+    return err
+  new = RuntimeError('cannot decode %s: %s: %s' % (path, type(err).__name__, err))
+  new.__cause__ = err
+  return new
+
+
+def _shutdown(stop, pool):
+  stop.set()
+  pool.shutdown(wait=False, cancel_futures=True)
+
+
+class PrefetchLoader(object):
+  """data.DataLoader with its decodes running ahead on threads (module doc)."""
+
+  def __init__(self, loader, workers=4, resize='host', prefetch_depth=2,
+               device=None, world_size=1):
+    if resize not in ('host', 'device'):
+      raise ValueError("resize must be 'host' or 'device', got %r" % (resize,))
+    self.loader = loader
+    self.resize = resize
+    self.depth = max(1, int(prefetch_depth))
+    self.device = device
+    if resize == 'device':
+      import torch  # pylint: disable=g-import-not-at-top
+      dev = torch.device(device if device is not None else 'cuda')
+      if dev.type != 'cuda' or not torch.cuda.is_available():
+        raise RuntimeError(
+            "resize='device' runs the AREA resize as a HIP kernel and needs a "
+            'ROCm GPU (got device %s); use resize=\'host\' on a CPU run' % dev)
+      self.device = dev
+    self.n_threads = pool_size(workers, world_size)
+    self._stop = threading.Event()
+    self._pool = futures.ThreadPoolExecutor(self.n_threads,
+                                            thread_name_prefix='kitti-decode')
+    self._finalizer = weakref.finalize(self, _shutdown, self._stop, self._pool)
+    self._pending = collections.deque()   # scheduled batches, oldest first
+    self._free, self._uploading = [], []  # staging buffers; (event, staging)
+    self._capacity = 0
+    self._bs = None
+    self.src_image_names = []
+
+  # the wrapped loader's state, where KittiBatches and callers look for it
+  @property
+  def _rng(self):
+    return self.loader._rng  # pylint: disable=protected-access
+
+  @_rng.setter
+  def _rng(self, rng):
+    if self._pending:
+      raise RuntimeError('the RNG must be set before the first forward()')
+    self.loader._rng = rng  # pylint: disable=protected-access
+
+  @property
+  def output_disparities(self):
+    return self.loader.output_disparities
+
+  def __getattr__(self, name):  # file lists, h, w, opts ... of the wrapped loader
+    if name == 'loader':
+      raise AttributeError(name)
+    return getattr(self.loader, name)
+
+  # -- staging buffers ----------------------------------------------------------
+  def _acquire(self, n_desc, first_path):
+    # a buffer is free once the event behind its upload has completed
+    still = []
+    for ev, st in self._uploading:
+      if ev.query():
+        self._free.append(st)
+      else:
+        still.append((ev, st))
+    self._uploading = still
+    if not self._free and len(self._uploading) > self.depth + 1:
+      # the device is far behind: wait for the oldest upload, do not grow
+      ev, st = self._uploading.pop(0)
+      ev.synchronize()
+      self._free.append(st)
+    while self._free:
+      st = self._free.pop()  # (one of another size or batch layout is dropped)
+      if st.capacity >= self._capacity and st.desc.shape[0] == n_desc:
+        st.reset()
+        return st
+    if not self._capacity:
+      # a first guess from one file's header; a batch that does not fit is
+      # re-packed and the next buffers are made larger
+      from PIL import Image  # pylint: disable=g-import-not-at-top
+      try:
+        with Image.open(first_path) as im:
+          self._capacity = _round16(im.size[0] * im.size[1] * 3) * n_desc
+      except Exception:  # pylint: disable=broad-except
+        self._capacity = 1 << 20  # (the decode task reports the file)
+    return _Staging(n_desc, self._capacity)
+
+  # -- scheduling -------------------------------------------------------------
+  def _schedule(self, bs):
+    ld = self.loader
+    if ld.cam_calibration is None:
+      ld.preload_calib_files()
+    ids = [ld._next_index() for _ in range(bs)]  # pylint: disable=protected-access
+    lists = [(ld.img_list_src, 3), (ld.img_list_trg, 3)]
+    if ld.output_disparities:
+      lists += [(ld.img_list_disp_src, 1), (ld.img_list_disp_trg, 1)]
+    # descriptor / result order: per list, the bs samples
+    paths = [(lst[i], nc) for lst, nc in lists for i in ids]
+    staging = None
+    if self.resize == 'device':
+      staging = self._acquire(len(paths), paths[0][0])
+      futs = [self._pool.submit(_device_task, self._stop, p, nc, staging, slot)
+              for slot, (p, nc) in enumerate(paths)]
+    else:
+      futs = [self._pool.submit(_host_task, self._stop, p, ld.h, ld.w, nc)
+              for p, nc in paths]
+    self._pending.append((ids, paths, futs, staging))
+
+  def forward(self, bs):
+    """The next batch of the wrapped loader's sequence (module doc)."""
+    if self._stop.is_set():
+      raise RuntimeError('the loader was closed')
+    if self._bs is not None and bs != self._bs and self._pending:
+      raise ValueError('batches of %d are already being prefetched; got bs=%d' %
+                       (self._bs, bs))
+    self._bs = bs
+    while len(self._pending) < self.depth + 1:
+      self._schedule(bs)
+    ids, paths, futs, staging = self._pending.popleft()
+    ld = self.loader
+    results, error = [], None
+    for (path, _), fut in zip(paths, futs):  # every task of the batch ends here
+      try:
+        results.append(fut.result())
+      except Exception as e:  # pylint: disable=broad-except
+        results.append(None)
+        if error is None:
+          error = _named(path, e)
+    self.src_image_names = [ld.img_list_src[i] for i in ids]
+    ld.src_image_names = self.src_image_names
+    if error is not None:
+      if staging is not None:
+        self._free.append(staging)  # never uploaded: free at once
+      raise error
+    shapes = [r[0] if self.resize == 'device' else r[1] for r in results]
+    cams = [kitti_data.pair_cameras(ld.cam_calibration[ld.seq_id_list[i]],
+                                    shapes[j], shapes[bs + j], ld.h, ld.w)
+            for j, i in enumerate(ids)]
+    out_cams = [np.stack([c[k] for c in cams]) for k in range(4)]
+    if self.resize == 'host':
+      imgs = [np.stack([r[0] for r in results[g * bs:(g + 1) * bs]])
+              for g in range(len(paths) // bs)]
+      return imgs[:2] + out_cams + imgs[2:]
+    imgs = self._upload_and_resize(staging, results, bs)
+    return imgs[:2] + out_cams + imgs[2:]
+
+  def _upload_and_resize(self, staging, results, bs):
+    import torch  # pylint: disable=g-import-not-at-top
+    ld = self.loader
+    spilled = [(slot, r[1]) for slot, r in enumerate(results) if r[1] is not None]
+    if spilled:
+      # the buffer was too small: a larger one takes the whole batch (and sets
+      # the size of the buffers made from now on)
+      self._capacity = _round16(staging.wanted - staging.header) * 5 // 4
+      big = _Staging(staging.desc.shape[0], self._capacity)
+      n_fit = staging.used
+      big.bytes[big.header:n_fit] = staging.bytes[staging.header:n_fit]
+      big.desc[...] = staging.desc
+      big.used = n_fit
+      for slot, arr in spilled:
+        off = big.alloc(arr.size)
+        big.bytes[off:off + arr.size].reshape(arr.shape)[...] = arr
+        big.desc[slot] = (off, arr.shape[0], arr.shape[1], arr.shape[2], 0)
+      staging = big
+    used = staging.used + 16  # the pad behind the last image
+    with torch.cuda.device(self.device):
+      packed = torch.empty(used, dtype=torch.uint8, device=self.device)
+      packed.copy_(staging.tensor[:used], non_blocking=True)
+      event = torch.cuda.Event()
+      event.record()
+      self._uploading.append((event, staging))
+      out = []
+      for g, nc in enumerate((3, 1) if ld.output_disparities else (3,)):
+        n = 2 * bs
+        first = g * n
+        both = area_resize_u8(
+            packed, staging.desc[first:first + n],
+            packed.data_ptr() + first * DESC_DTYPE.itemsize, n, ld.h, ld.w, nc)
+        out += [both[:bs], both[bs:]]
+    return out
+
+  # -- shutdown ---------------------------------------------------------------
+  def close(self):
+    """Stops the workers: queued decodes are dropped, running ones finish."""
+    self._finalizer()
+    self._pending.clear()
+    # (a running decode takes milliseconds; never wait long for one)
+    deadline = time.monotonic() + 0.5
+    for t in list(getattr(self._pool, '_threads', ())):
+      t.join(max(0.0, deadline - time.monotonic()))
+
+  def workers_alive(self):
+    return sum(t.is_alive() for t in list(getattr(self._pool, '_threads', ())))
+
+  def __enter__(self):
+    return self
+
+  def __exit__(self, *exc):
+    self.close()
+    return False

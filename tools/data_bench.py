@@ -1,0 +1,247 @@
+"""Feed rate of the KITTI loaders against the training step they feed.
+
+Writes a KITTI-shaped raw_city tree of procedural PNGs (ragged sizes around
+375 x 1242, one per sequence; nothing is downloaded) and reports, for batch 4
+at 256 x 768 on this host, in this run:
+  * the synchronous loader (data.DataLoader inside KittiBatches): the baseline;
+  * pipeline.PrefetchLoader, resize on the host, at 2, 4, 8 and 16 threads;
+  * the same with the resize on the device (csrc/lsi_image.hip);
+  * the HIP-event time of the resize launch alone and the bytes it moves;
+  * where one image's host time goes (decode / resize);
+  * the 2- and 4-layer training step on procedural pairs (tools/train_bench.py's
+    measurement), and the 2-layer step fed from the tree by both loaders, eager
+    and as a captured HIP graph.
+  python tools/data_bench.py [--out FILE] [--batches N] [--skip_steps] [--kernel_only]
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+import types
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'layered-scene-inference_amd'))
+
+from lsi.data.kitti import data as kitti_data  # noqa: E402
+from lsi.data.kitti import pipeline  # noqa: E402
+
+SIZES = [(375, 1242), (370, 1226), (374, 1238), (376, 1241)]  # KITTI raw dates
+PAIRS_PER_SEQ = 6
+H, W, BS = 256, 768, 4
+
+
+def procedural_png(path, h, w, seed):
+  """A smooth random texture plus sensor-like noise: compresses to about two
+  thirds of its raw size, as a photograph does."""
+  from PIL import Image
+  rs = np.random.RandomState(seed)
+  lo = rs.rand(h // 16 + 2, w // 16 + 2, 3)
+  yy = np.linspace(0, lo.shape[0] - 1.001, h)
+  xx = np.linspace(0, lo.shape[1] - 1.001, w)
+  y0, x0 = yy.astype(int), xx.astype(int)
+  fy, fx = (yy - y0)[:, None, None], (xx - x0)[None, :, None]
+  img = ((lo[y0][:, x0] * (1 - fx) + lo[y0][:, x0 + 1] * fx) * (1 - fy) +
+         (lo[y0 + 1][:, x0] * (1 - fx) + lo[y0 + 1][:, x0 + 1] * fx) * fy)
+  img = img * 255 + rs.randint(-6, 7, (h, w, 3))
+  os.makedirs(os.path.dirname(path), exist_ok=True)
+  Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(path)
+
+
+def write_tree(root):
+  opts = loader_opts(root)
+  seqs = kitti_data.DataLoader(opts).split_sequences()[:len(SIZES)]
+  top = os.path.join(root, 'kitti_raw')
+  n_bytes = 0
+  for s, (seq, (h, w)) in enumerate(zip(seqs, SIZES)):
+    date = seq[:10]
+    for n in range(PAIRS_PER_SEQ):
+      for cam in ('image_02', 'image_03'):
+        path = os.path.join(top, date, seq + '_sync', cam, 'data', '%010d.png' % n)
+        procedural_png(path, h, w, 1000 * s + 2 * n + (cam == 'image_03'))
+        n_bytes += os.path.getsize(path)
+    with open(os.path.join(top, date, 'calib_cam_to_cam.txt'), 'w') as f:
+      p = '721.5 0 609.6 %f 0 721.5 172.9 0 0 0 1 0'
+      f.write('P_rect_02: %s\nP_rect_03: %s\n' % (p % 44.86, p % -339.5))
+  return n_bytes / (2.0 * PAIRS_PER_SEQ * len(SIZES))
+
+
+def loader_opts(root):
+  return types.SimpleNamespace(
+      batch_size=BS, kitti_data_root=root, kitti_dataset_variant='raw_city',
+      data_split='train', img_height=H, img_width=W, kitti_dl_disparities=False)
+
+
+def time_loader(make, batches, warm=2):
+  """ms per batch of forward(BS), the device idle at the end of the clock."""
+  ld = make()
+  try:
+    for _ in range(warm):
+      ld.forward(BS)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(batches):
+      out = ld.forward(BS)
+    torch.cuda.synchronize()
+    del out
+    return (time.perf_counter() - t0) * 1e3 / batches
+  finally:
+    close = getattr(ld, 'close', None)
+    if close is not None:
+      close()
+
+
+def time_kernel(root, reps=20):
+  """HIP-event time of one lsi_area_resize_u8 launch on 8 images of the tree."""
+  ld = kitti_data.DataLoader(loader_opts(root))
+  paths = [p for i in range(0, len(ld.img_list_src), PAIRS_PER_SEQ)
+           for p in (ld.img_list_src[i], ld.img_list_trg[i])][:2 * BS]
+  st = pipeline._Staging(len(paths), sum(
+      pipeline._round16(h * w * 3) for h, w in SIZES) * 2)
+  stop = __import__('threading').Event()
+  for slot, p in enumerate(paths):
+    pipeline._device_task(stop, p, 3, st, slot)
+  used = st.used + 16
+  packed = torch.empty(used, dtype=torch.uint8, device='cuda')
+  packed.copy_(st.tensor[:used])
+  out = torch.empty((len(paths), H, W, 3), device='cuda')
+  run = lambda: pipeline.area_resize_u8(packed, st.desc, packed.data_ptr(),
+                                        len(paths), H, W, 3, out=out)
+  for _ in range(3):
+    run()
+  torch.cuda.synchronize()
+  times = []
+  for _ in range(reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    run()
+    e1.record()
+    e1.synchronize()
+    times.append(e0.elapsed_time(e1) * 1e3)
+  moved = int(st.desc['H'].astype(np.int64) @ st.desc['W'] * 3) + out.numel() * 4
+  return float(np.median(times)), float(min(times)), moved, used
+
+
+def time_host_parts(root, reps=8):
+  ld = kitti_data.DataLoader(loader_opts(root))
+  paths = ld.img_list_src[:reps]
+  t0 = time.perf_counter()
+  arrs = [pipeline.decode_u8(p, 3) for p in paths]
+  t1 = time.perf_counter()
+  for a in arrs:
+    kitti_data.area_resize(a.astype(np.float32) * np.float32(1.0 / 255), H, W)
+  t2 = time.perf_counter()
+  for p in paths:
+    kitti_data._load_image(p, H, W)
+  t3 = time.perf_counter()
+  return ((t1 - t0) * 1e3 / reps, (t2 - t1) * 1e3 / reps, (t3 - t2) * 1e3 / reps)
+
+
+def time_step(extra, steps=20, warm=6):
+  import ldi_enc_dec as script
+  base = ['--dataset', 'kitti', '--batch_size', str(BS), '--img_height', str(H),
+          '--img_width', str(W), '--checkpoint_dir',
+          os.path.join(tempfile.gettempdir(), 'lsi_data_bench_ckpt'),
+          '--save_latest_freq', '1000000', '--checkpoint_freq', '1000000',
+          '--log_freq', '1000000']
+  opts = script.apply_dataset_overrides(script.build_parser().parse_args(base + extra))
+  tr = script.Trainer(opts)
+  tr.setup()
+  try:
+    for _ in range(warm):
+      tr.train_step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+      tr.train_step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+  finally:
+    close = getattr(tr.data_loader, 'close', None)
+    if close is not None:
+      close()
+
+
+def main():
+  ap = argparse.ArgumentParser(description=__doc__)
+  ap.add_argument('--out', default='')
+  ap.add_argument('--batches', type=int, default=12)
+  ap.add_argument('--skip_steps', action='store_true')
+  ap.add_argument('--kernel_only', action='store_true',
+                  help='only the resize launch (for a rocprofv3 --kernel-trace run)')
+  args = ap.parse_args()
+  assert torch.cuda.is_available(), 'data_bench needs a ROCm device'
+  lines, rec = [], {}
+
+  def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+  with tempfile.TemporaryDirectory(prefix='lsi_kitti_tree_') as root:
+    png = write_tree(root)
+    say('tree: %d sequences x %d pairs, sizes %s, mean PNG %.0f kB; batch %d -> %d x %d'
+        % (len(SIZES), PAIRS_PER_SEQ, SIZES, png / 1e3, BS, H, W))
+    if args.kernel_only:
+      med, best, moved, _ = time_kernel(root, reps=50)
+      say('resize launch alone: median %.1f us, min %.1f us by HIP events, %.1f MB'
+          % (med, best, moved / 1e6))
+      return
+    dec, rsz, whole = time_host_parts(root)
+    say('one image on one thread: decode %.1f ms, host AREA resize %.1f ms, '
+        '_load_image %.1f ms' % (dec, rsz, whole))
+    rec['image_ms'] = {'decode': dec, 'host_resize': rsz, 'load_image': whole}
+    med, best, moved, up = time_kernel(root)
+    say('resize launch alone (8 RGB images -> 8 x %d x %d x 3 fp32): median %.1f us, '
+        'min %.1f us, %.1f MB moved (%.0f GB/s at the median); upload %.1f MB'
+        % (H, W, med, best, moved / 1e6, moved / med / 1e3, up / 1e6))
+    rec['resize_kernel'] = {'median_us': med, 'min_us': best, 'bytes': moved,
+                            'upload_bytes': up}
+    import ldi_enc_dec as script
+    sync = time_loader(lambda: script.KittiBatches(
+        kitti_data.DataLoader(loader_opts(root))), args.batches)
+    say('%-34s %8.1f ms/batch %7.2f batches/s' % ('synchronous loader (baseline)',
+                                                 sync, 1e3 / sync))
+    rec['loaders_ms_per_batch'] = {'sync': sync}
+    for resize in ('host', 'device'):
+      for n in (2, 4, 8, 16):
+        ms = time_loader(lambda: script.KittiBatches(pipeline.PrefetchLoader(
+            kitti_data.DataLoader(loader_opts(root)), workers=n, resize=resize,
+            device=torch.device('cuda', 0))), args.batches)
+        say('%-34s %8.1f ms/batch %7.2f batches/s  x%.1f' % (
+            '%2d threads, resize on the %s' % (n, resize), ms, 1e3 / ms, sync / ms))
+        rec['loaders_ms_per_batch']['%s_%d' % (resize, n)] = ms
+    if not args.skip_steps:
+      rec['step_ms'] = {}
+      for nl in (2, 4):
+        ms = time_step(['--kitti_procedural', 'true', '--n_layers', str(nl)])
+        say('training step, %d layers, procedural pairs: %.1f ms (%.2f steps/s)'
+            % (nl, ms, 1e3 / ms))
+        rec['step_ms']['L%d' % nl] = ms
+      tree = ['--kitti_dataset_variant', 'raw_city', '--kitti_data_root', root,
+              '--n_layers', '2']
+      dev = lambda n: ['--data_workers', str(n), '--kitti_resize', 'device']
+      graph = ['--hip_graph', 'true']
+      for key, name, extra in (
+          ('L2_tree_sync', 'tree, synchronous loader', tree),
+          ('L2_tree_device_8', 'tree, 8 threads + device resize', tree + dev(8)),
+          ('L2_tree_device_16', 'tree, 16 threads + device resize', tree + dev(16)),
+          ('L2_graph', 'procedural pairs, --hip_graph', graph + [
+              '--kitti_procedural', 'true', '--n_layers', '2']),
+          ('L2_graph_tree_device_16', 'tree, 16 threads + device resize, --hip_graph',
+           tree + dev(16) + graph)):
+        ms = time_step(extra, steps=12, warm=6)
+        say('training step, 2 layers, %s: %.1f ms' % (name, ms))
+        rec['step_ms'][key] = ms
+  say(json.dumps(rec))
+  if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+      f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+  main()

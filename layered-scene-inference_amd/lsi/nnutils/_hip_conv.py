@@ -46,15 +46,11 @@ def _launch(x, weight, cout, mode, bias=None):
   itself -- no packing or casting launches."""
   n, _, h, w = x.shape
   dev = x.device
-  weight = weight.detach()
-  if weight.dtype != torch.float32 or not weight.is_contiguous():
-    weight = weight.float().contiguous()
+  weight = _f32(weight)
   if mode == 1:
-    out = torch.empty((n, 4, h, w), dtype=torch.float32, device=dev,
-                      memory_format=torch.channels_last)
+    out = _empty_cl(n, 4, h, w, dev, torch.float32)
   else:
-    out = torch.empty((n, cout, h, w), dtype=torch.bfloat16, device=dev,
-                      memory_format=torch.channels_last)
+    out = _empty_cl(n, cout, h, w, dev, torch.bfloat16)
   rc = _C.lib().lsi_conv3x3_c32_fwd(n, h, w, cout, mode, _C.ptr(x), _C.ptr(weight),
                                     _C.ptr(bias), 1.0, _C.ptr(out),
                                     _C.stream_ptr(dev))
@@ -172,7 +168,6 @@ class _Conv3x3C32(torch.autograd.Function):
 
 
 # ---- weight gradient on the matrix cores (csrc/lsi_conv_wgrad.hip) ---------------
-import os
 WGRAD_MIN_PIXELS = int(os.environ.get('LSI_WGRAD_MIN_PIXELS', '200000'))  # below: aten (tools/time_wgrad.py)
 _WGRAD_WS = {}
 
@@ -281,17 +276,13 @@ class _Conv3x3C32Sigmoid(torch.autograd.Function):
       # kernel)
       g = g.contiguous(memory_format=torch.channels_last)
       dev = x.device
-      gx = (torch.empty((n, 32, h, w), dtype=torch.bfloat16, device=dev,
-                        memory_format=torch.channels_last)
-            if ctx.needs_input_grad[0] else None)
+      gx = _empty_cl(n, 32, h, w, dev, torch.bfloat16) if ctx.needs_input_grad[0] else None
       want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
       gwb = ws = None
       if want_w:
         gwb = torch.empty((cout * 288 + cout,), dtype=torch.float32, device=dev)
         ws = _pred_workspace(dev, n, h, w)
-      wt = weight.detach()
-      if wt.dtype != torch.float32 or not wt.is_contiguous():
-        wt = wt.float().contiguous()
+      wt = _f32(weight)
       rc = _C.lib().lsi_conv3x3_pred_bwd(n, h, w, cout, _C.ptr(g), _C.ptr(y), _C.ptr(x),
                                          _C.ptr(wt), _C.ptr(gx), _C.ptr(gwb),
                                          _C.ptr(ws), 0 if ws is None else ws.numel() * 4,
@@ -322,50 +313,119 @@ def conv3x3_c32_sigmoid(x, weight, bias):
   return _Conv3x3C32Sigmoid.apply(x, weight, bias)
 
 
-# ---- every other convolution: the implicit-GEMM kernel (csrc/lsi_conv_igemm.hip) ----
+# ---- every other convolution: the implicit-GEMM kernels -----------------------------
+# (bf16: csrc/lsi_conv_igemm.hip, lsi_conv_wgrad_igemm.hip; exact fp32:
+# csrc/lsi_conv_f32.hip)
 import ctypes
+import dataclasses
 
 IGEMM_MIN_PIXELS = int(os.environ.get('LSI_IGEMM_MIN_PIXELS', '0'))
 
 
+@dataclasses.dataclass(frozen=True, eq=False)
+class _Precision(object):
+  """One precision of the implicit-GEMM family.  The two take the same
+  LsiConvDesc, LsiConvIO and argument lists; what differs is here, or where the
+  code says `p is BF16`."""
+  dtype: torch.dtype       # of the activations and of the packed weights
+  esz: int
+  supported: str           # the C entries, by name
+  run: str
+  run_bytes: str
+  wgrad: str
+  wgrad_bytes: str
+  packed_bytes: str
+  pack: str
+  pack_job: str
+  pack_many: str
+  bn_sums: bool            # the epilogue can leave batch-norm sums (bn_groups)
+  counts: bool             # every launch counts into USED_F32
+
+
+BF16 = _Precision(torch.bfloat16, 2, 'lsi_conv2d_supported', 'lsi_conv2d_run',
+                  'lsi_conv2d_workspace_bytes', 'lsi_conv2d_wgrad_cat',
+                  'lsi_conv2d_wgrad_workspace_bytes', 'lsi_conv2d_packed_bytes',
+                  'lsi_conv2d_pack', 'lsi_conv2d_pack_job', 'lsi_conv2d_pack_many', True, False)
+# Exact fp32 (v_mfma_f32_16x16x4_f32, deterministic folds) on fp32 channels-last
+# activations -- the reference's own arithmetic (--bf16 false) -- opted into with
+# nets.F32_CONV (LSI_F32_CONV=1, the trainer's --fp32_convs own).  The batch norm
+# behind these kernels stays on the two-pass kernels (no sums in the epilogue); the
+# weight gradients the kernel does not take (partial sums over the workspace cap:
+# the bottleneck layers) go to aten.
+F32 = _Precision(torch.float32, 4, 'lsi_conv2d_f32_supported', 'lsi_conv2d_f32_run',
+                 'lsi_conv2d_f32_workspace_bytes', 'lsi_conv2d_wgrad_f32',
+                 'lsi_conv2d_wgrad_f32_workspace_bytes', 'lsi_conv2d_f32_packed_bytes',
+                 'lsi_conv2d_f32_pack', 'lsi_conv2d_f32_pack_job', 'lsi_conv2d_f32_pack_many',
+                 False, True)
+_PRECISIONS = {torch.bfloat16: BF16, torch.float32: F32}
+USED_F32 = [0]   # kernel launches of the fp32 precision (tests check that it ran)
+
+# what the library says about a geometry, asked once: (precision, geometry) -> answer
+_DESC_OK = {}
+_RUN_BYTES = {}      # (precision, mode, geometry)
+_WGRAD_BYTES = {}
+
+
 def _conv_desc(n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l):
+  """The LsiConvDesc, and on it the same numbers as a tuple: `geometry`, the
+  descriptor as a cache key (reading the twelve fields back costs more than the
+  look-up it is for)."""
   d = _C.LsiConvDesc()
-  (d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout, d.KH, d.KW, d.stride, d.pad_t,
-   d.pad_l) = (n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l)
+  d.geometry = (d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout, d.KH, d.KW, d.stride, d.pad_t,
+                d.pad_l) = (n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l)
   return d
 
 
-def _cl_bf16(t):
-  return (t.is_cuda and t.dim() == 4 and t.dtype == torch.bfloat16 and
+def same_geometry(h, w, k, stride):
+  """TF 'SAME' for an h x w map: (oh, ow, pad_t, pad_l) -- the output size and the
+  padding before (asymmetric for stride 2: the extra pixel goes after)."""
+  oh, ow = -(-h // stride), -(-w // stride)
+  return (oh, ow, max((oh - 1) * stride + k - h, 0) // 2,
+          max((ow - 1) * stride + k - w, 0) // 2)
+
+
+def _cl(t, dtype):
+  return (t.is_cuda and t.dim() == 4 and t.dtype == dtype and
           t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0)
 
 
-_DESC_OK = {}
+def _empty_cl(n, c, h, w, dev, dtype):
+  return torch.empty((n, c, h, w), dtype=dtype, device=dev, memory_format=torch.channels_last)
 
 
-def _desc_supported(n, h, w, cin, oh, ow, cout, k, stride, pad):
-  """lsi_conv2d_supported for the geometry (the library's own word: channel
-  multiples, kernel size, the 2^31-element bound of its int32 offsets), cached."""
-  key = (n, h, w, cin, oh, ow, cout, k, stride, pad)
-  ok = _DESC_OK.get(key)
+def _desc_supported(p, geo):
+  """lsi_conv2d[_f32]_supported for the geometry (the library's own word: channel
+  multiples, kernel size, the 2^31-element bound of its int32 offsets), cached.
+  Cout a multiple of 32: the data gradient takes it as its input channels (the
+  fp32 forward alone would take 16)."""
+  ok = _DESC_OK.get((p, geo))
   if ok is None:
-    d = _conv_desc(n, h, w, cin, oh, ow, cout, k, k, stride, pad, pad)
-    ok = _DESC_OK[key] = bool(_C.lib().lsi_conv2d_supported(ctypes.byref(d)))
+    d = _conv_desc(*geo)
+    ok = _DESC_OK[(p, geo)] = (bool(getattr(_C.lib(), p.supported)(ctypes.byref(d))) and
+                               geo[6] % 32 == 0)
   return ok
+
+
+def _conv_supported(p, x, cin, cout, k, stride, min_pixels=0):
+  if not (_cl(x, p.dtype) and x.shape[1] == cin and 1 <= k <= 7 and stride in (1, 2) and
+          x.shape[0] * x.shape[2] * x.shape[3] >= min_pixels):
+    return False
+  n, _, h, w = x.shape
+  oh, ow, pad_t, pad_l = same_geometry(h, w, k, stride)   # (what SlimConv2d passes)
+  return _desc_supported(p, (n, h, w, cin, oh, ow, cout, k, k, stride, pad_t, pad_l))
 
 
 def igemm_supported(x, cin, cout, k, stride):
   """bf16 channels-last GPU activations, channel counts that are multiples of
   32, kernels up to 7 x 7, stride 1 or 2, fewer than 2^31 elements per tensor
   (lsi_conv2d_supported)."""
-  if not (_cl_bf16(x) and x.shape[1] == cin and 1 <= k <= 7 and stride in (1, 2) and
-          x.shape[0] * x.shape[2] * x.shape[3] >= IGEMM_MIN_PIXELS):
-    return False
-  n, _, h, w = x.shape
-  oh, ow = -(-h // stride), -(-w // stride)
-  # (TF SAME: the pad before; what SlimConv2d passes)
-  pad = max((oh - 1) * stride + k - h, 0) // 2
-  return _desc_supported(n, h, w, cin, oh, ow, cout, k, stride, pad)
+  return _conv_supported(BF16, x, cin, cout, k, stride, IGEMM_MIN_PIXELS)
+
+
+def f32_supported(x, cin, cout, k, stride):
+  """The same for fp32 channels-last 16-byte aligned GPU activations
+  (lsi_conv2d_f32_supported)."""
+  return _conv_supported(F32, x, cin, cout, k, stride)
 
 
 def _f32(weight):
@@ -439,15 +499,6 @@ def _after_optimizer_step(optimizer, args, kwargs):
     repack_all(_owned=owned)
 
 
-# the pack entries per pack dtype: (packed_bytes, pack, pack_job, pack_many)
-_PACK_FNS = {
-    torch.bfloat16: ('lsi_conv2d_packed_bytes', 'lsi_conv2d_pack', 'lsi_conv2d_pack_job',
-                     'lsi_conv2d_pack_many'),
-    torch.float32: ('lsi_conv2d_f32_packed_bytes', 'lsi_conv2d_f32_pack',
-                    'lsi_conv2d_f32_pack_job', 'lsi_conv2d_f32_pack_many'),
-}
-
-
 def _packed(desc, mode, weight, training=False, dtype=torch.bfloat16):
   """The layer's weights in the kernel's operand order (lsi_conv2d_pack; with
   dtype=torch.float32 lsi_conv2d_f32_pack: the fp32 kernels' pack, cached
@@ -492,18 +543,18 @@ def _packed(desc, mode, weight, training=False, dtype=torch.bfloat16):
       return hit.buf
   lib = _C.lib()
   dev = weight.device
-  fns = _PACK_FNS[dtype]
-  esz = 2 if dtype == torch.bfloat16 else 4
-  nbytes = getattr(lib, fns[0])(ctypes.byref(desc))
+  p = _PRECISIONS[dtype]
+  esz = p.esz
+  nbytes = getattr(lib, p.packed_bytes)(ctypes.byref(desc))
   if (hit is not None and hit.wref() is weight and hit.buf.device == dev and
       hit.buf.numel() * esz == nbytes and hit.geo == geo):
     buf = hit.buf          # (same place: a captured graph or a job table keeps its address)
   else:
     buf = torch.empty((nbytes // esz,), dtype=dtype, device=dev)
   src, cl = _pack_source(weight)
-  rc = getattr(lib, fns[1])(ctypes.byref(desc), mode | cl, _C.ptr(src), _C.ptr(buf),
+  rc = getattr(lib, p.pack)(ctypes.byref(desc), mode | cl, _C.ptr(src), _C.ptr(buf),
                             nbytes, _C.stream_ptr(dev))
-  _C.check(rc, fns[1])
+  _C.check(rc, p.pack)
   e = _Pack()
   e.wref = weakref.ref(weight, lambda _r, k=key: _PACKED.pop(k, None))
   e.version = weight._version
@@ -519,7 +570,7 @@ def _verify_pack(e, weight):
   """LSI_PACK_CHECK: the trusted pack against a fresh one (synchronises)."""
   src, cl = _pack_source(weight)
   fresh = torch.empty_like(e.buf)
-  pack = _PACK_FNS[e.dtype][1]
+  pack = _PRECISIONS[e.dtype].pack
   rc = getattr(_C.lib(), pack)(ctypes.byref(e.desc), e.mode | cl, _C.ptr(src), _C.ptr(fresh),
                                fresh.numel() * fresh.element_size(), _C.stream_ptr(weight.device))
   _C.check(rc, pack)
@@ -564,7 +615,7 @@ def repack_all(device=None, _owned=None):
     by_dev.setdefault((w.device.index, e.dtype), []).append((e, w))
   n = 0
   for (idx, dtype), items in by_dev.items():
-    fns = _PACK_FNS[dtype]
+    p = _PRECISIONS[dtype]
     key = tuple((w.data_ptr(), e.buf.data_ptr(), e.mode) for e, w in items)
     # (every table ever built stays alive under its key: a captured graph has
     # its device address baked in)
@@ -575,10 +626,10 @@ def repack_all(device=None, _owned=None):
       nb = ctypes.c_int32(0)
       blocks = 0
       for j, (e, w) in enumerate(items):
-        rc = getattr(lib, fns[2])(ctypes.byref(e.desc), e.mode | _pack_layout(w), w.data_ptr(),
+        rc = getattr(lib, p.pack_job)(ctypes.byref(e.desc), e.mode | _pack_layout(w), w.data_ptr(),
                                   e.buf.data_ptr(), e.buf.numel() * e.buf.element_size(),
                                   ctypes.byref(jobs[j]), ctypes.byref(nb))
-        _C.check(rc, fns[2])
+        _C.check(rc, p.pack_job)
         jobs[j].block0 = blocks
         blocks += nb.value
       host = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8)
@@ -586,8 +637,8 @@ def repack_all(device=None, _owned=None):
       tabs[key] = tab
     dev = items[0][1].device
     with torch.cuda.device(dev):
-      rc = getattr(lib, fns[3])(tab[1].data_ptr(), tab[2], tab[3], _C.stream_ptr(dev))
-    _C.check(rc, fns[3])
+      rc = getattr(lib, p.pack_many)(tab[1].data_ptr(), tab[2], tab[3], _C.stream_ptr(dev))
+    _C.check(rc, p.pack_many)
     for e, w in items:
       e.version = w._version
       if _owned is not None:
@@ -597,292 +648,348 @@ def repack_all(device=None, _owned=None):
 
 
 SPLITK = os.environ.get('LSI_IGEMM_SPLITK', '1') != '0'
-_RUN_BYTES = {}
 
 
-def _run_workspace(desc, mode, dev):
-  """(pointer, bytes) of the workspace lsi_conv2d_run splits the contraction
-  over the input channels in (the bottleneck maps); (0, 0) where it does not
-  split.  The buffer is the weight gradients' (per device and stream: the calls
-  that share it are ordered on that stream)."""
-  if not SPLITK:
-    return 0, 0
-  key = (mode, desc.N, desc.H, desc.W, desc.Cin, desc.OH, desc.OW, desc.Cout, desc.KH,
-         desc.KW, desc.stride, desc.pad_t, desc.pad_l)
-  n = _RUN_BYTES.get(key)
-  if n is None:
-    n = _RUN_BYTES[key] = int(_C.lib().lsi_conv2d_workspace_bytes(ctypes.byref(desc), mode))
-  if not n:
-    return 0, 0
-  ws = _wgrad_workspace(dev, n)
-  return ws.data_ptr(), ws.numel() * 4
-
-
-def _run(desc, mode, packed, dev, x=0, x2=0, out=0, out2=0, c1=0, bn_ws=0, groups=0):
-  """lsi_conv2d_run: forward (mode 0) / data gradient (mode 1) of the
-  descriptor's convolution with every option of the C ABI (two input tensors,
-  two gradient tensors, batch-norm sums, the split over the input channels)."""
-  io = _C.LsiConvIO()
-  io.x, io.x2, io.packed, io.out, io.out2 = x, x2 or None, packed, out, out2 or None
-  io.bn_workspace = bn_ws or None
-  io.c1, io.groups = int(c1), int(groups)
-  wp, wb = _run_workspace(desc, mode, dev)
-  io.workspace, io.workspace_bytes = wp or None, wb
-  rc = _C.lib().lsi_conv2d_run(ctypes.byref(desc), mode, ctypes.byref(io), _C.stream_ptr(dev))
-  if rc:
-    _C.check(rc, 'lsi_conv2d_run(mode %d)' % mode)
-
-
-def _igemm(entry, desc, src, weight, out, bn_groups=0, training=False):
-  """bn_groups > 0: the kernel also adds the batch-norm sums of `out` to the
-  workspace (as lsi_conv2d_*_bnstats) for the lsi_bn_relu_norm that has to follow."""
-  mode = 1 if entry == 'lsi_conv2d_bwd_data' else 0
-  if training:          # (a forward call of a layer: see _SIDE_CB)
+def _run(p, desc, mode, weight, src, out, x2=None, out2=None, c1=0, bn_groups=0,
+         training=False):
+  """lsi_conv2d[_f32]_run: forward (mode 0) / data gradient (mode 1) of the
+  descriptor's convolution with the precision's pack of `weight` and every option
+  of the C ABI -- the input as two tensors (x2, c1: the channels of the first),
+  the gradient into two tensors (out2), the split of the contraction over the
+  input channels where the library asks for a workspace (the bottleneck maps;
+  the buffer is the weight gradients': per device and stream, the calls that
+  share it are ordered on that stream) and, bf16 only, the batch-norm sums of
+  `out` added to _hip_bn's workspace for the lsi_bn_relu_norm that has to follow
+  (bn_groups > 0).  training: a forward call of a layer (see _SIDE_CB, _packed)."""
+  if bn_groups and not p.bn_sums:
+    raise ValueError('the %s convolutions leave no batch-norm sums (bn_groups=%d)'
+                     % (p.dtype, bn_groups))
+  if training:
     _FWD_SEQ[0] += 1
-  packed = _packed(desc, mode, weight, training)
+  packed = _packed(desc, mode, weight, training, p.dtype)
   dev = src.device
-  bn_ws = 0
+  io = _C.LsiConvIO()
+  io.x, io.packed, io.out, io.c1 = src.data_ptr(), packed.data_ptr(), out.data_ptr(), c1
+  if x2 is not None:
+    io.x2 = x2.data_ptr()
+  if out2 is not None:
+    io.out2 = out2.data_ptr()
   if bn_groups:
     from lsi.nnutils import _hip_bn  # pylint: disable=g-import-not-at-top
-    bn_ws = _hip_bn.stats_workspace(tuple(out.shape), dev, 1, bn_groups).data_ptr()
-  _run(desc, mode, packed.data_ptr(), dev, x=src.data_ptr(), out=out.data_ptr(), bn_ws=bn_ws,
-       groups=bn_groups)
+    io.bn_workspace = _hip_bn.stats_workspace(tuple(out.shape), dev, 1, bn_groups).data_ptr()
+    io.groups = bn_groups
+  lib = _C.lib()
+  if SPLITK:
+    key = (p, mode, desc.geometry)
+    nb = _RUN_BYTES.get(key)
+    if nb is None:
+      nb = _RUN_BYTES[key] = int(getattr(lib, p.run_bytes)(ctypes.byref(desc), mode))
+    if nb:
+      ws = _wgrad_workspace(dev, nb)
+      io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+  rc = getattr(lib, p.run)(ctypes.byref(desc), mode, ctypes.byref(io), _C.stream_ptr(dev))
+  if rc:
+    _C.check(rc, '%s(mode %d)' % (p.run, mode))
+  if p.counts:
+    USED_F32[0] += 1
   return out
 
 
-def _empty_cl(n, c, h, w, dev):
-  return torch.empty((n, c, h, w), dtype=torch.bfloat16, device=dev,
-                     memory_format=torch.channels_last)
-
-
+# bf16 only: LSI_IGEMM_WGRAD=0 sends every weight gradient but the row-ring
+# kernel's to the library, LSI_IGEMM_WGRAD_MIN_PIXELS those of small maps
 OWN_WGRAD = os.environ.get('LSI_IGEMM_WGRAD', '1') != '0'
 IGEMM_WGRAD_MIN_PIXELS = int(os.environ.get('LSI_IGEMM_WGRAD_MIN_PIXELS', '0'))
-_WGRAD_BYTES = {}
 
 
-def _igemm_wgrad_bytes(d):
-  """lsi_conv2d_wgrad_workspace_bytes per geometry (0: the library takes it)."""
-  key = (d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout, d.KH, d.KW, d.stride, d.pad_t, d.pad_l)
+def wgrad_bytes(p, d):
+  """lsi_conv2d_wgrad[_f32]_workspace_bytes per geometry (0: the library takes it)."""
+  key = (p, d.geometry)
   n = _WGRAD_BYTES.get(key)
   if n is None:
-    n = int(_C.lib().lsi_conv2d_wgrad_workspace_bytes(ctypes.byref(d)))
-    # (every map size since the transposing fold -- the bottleneck layers' 2 x 6
-    # ... 8 x 24 maps, too: 32 - 66 us against the library's 25 - 92,
+    n = int(getattr(_C.lib(), p.wgrad_bytes)(ctypes.byref(d)))
+    # (bf16: every map size since the transposing fold -- the bottleneck layers'
+    # 2 x 6 ... 8 x 24 maps, too: 32 - 66 us against the library's 25 - 92,
     # tools/conv_bench.py; LSI_IGEMM_WGRAD_MIN_PIXELS sends small maps back)
-    if d.N * d.OH * d.OW < IGEMM_WGRAD_MIN_PIXELS:
+    if p is BF16 and d.N * d.OH * d.OW < IGEMM_WGRAD_MIN_PIXELS:
       n = 0
     _WGRAD_BYTES[key] = n
   return n
 
 
-def _igemm_wgrad(d, x, gy, weight, x2=None):
-  """lsi_conv2d_wgrad[_cat]: x (and x2: the input as two tensors) = the
-  descriptor's input, gy its output gradient.  The gradient comes out in the
-  parameter's own memory layout (contiguous or channels-last strides), so that
-  autograd's accumulation takes it as it is instead of cloning it into that
-  layout (one copy kernel per parameter and step)."""
-  dev = x.device
-  nbytes = _igemm_wgrad_bytes(d)
-  ws = _wgrad_workspace(dev, nbytes)
+def f32_wgrad_bytes(d):
+  return wgrad_bytes(F32, d)
+
+
+def _grad_like(weight):
+  """(an fp32 buffer in the parameter's own memory layout -- contiguous or
+  channels-last strides -- and that layout's bit): autograd's accumulation takes
+  such a gradient as it is instead of cloning it into the layout (one copy kernel
+  per parameter and step)."""
   cl = 2 if (weight.dim() == 4 and not weight.is_contiguous() and
              weight.is_contiguous(memory_format=torch.channels_last)) else 0
-  gw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=dev,
-                   memory_format=torch.channels_last if cl else torch.contiguous_format)
-  rc = _C.lib().lsi_conv2d_wgrad_cat(
+  return torch.empty(tuple(weight.shape), dtype=torch.float32, device=weight.device,
+                     memory_format=torch.channels_last if cl else torch.contiguous_format), cl
+
+
+def _wgrad(p, d, x, gy, weight, x2=None):
+  """lsi_conv2d_wgrad_cat / lsi_conv2d_wgrad_f32: x (and x2: the input as two
+  tensors) = the descriptor's input, gy its output gradient."""
+  dev = x.device
+  ws = _wgrad_workspace(dev, wgrad_bytes(p, d))
+  gw, cl = _grad_like(weight)
+  rc = getattr(_C.lib(), p.wgrad)(
       ctypes.byref(d), x.data_ptr(), x2.data_ptr() if x2 is not None else 0,
       x.shape[1] if x2 is not None else 0, gy.data_ptr(), gw.data_ptr(), cl, ws.data_ptr(),
       ws.numel() * 4, _C.stream_ptr(dev))
   if rc:
-    _C.check(rc, 'lsi_conv2d_wgrad_cat')
+    _C.check(rc, p.wgrad)
+  if p.counts:
+    USED_F32[0] += 1
   return gw if weight.dtype == torch.float32 else gw.to(weight.dtype)
 
 
-class _Conv2dIgemm(torch.autograd.Function):
+# (the names the tests call the two precisions' weight gradients by)
+def _igemm_wgrad_bytes(d):
+  return wgrad_bytes(BF16, d)
+
+
+def _igemm_wgrad(d, x, gy, weight, x2=None):
+  return _wgrad(BF16, d, x, gy, weight, x2)
+
+
+def _f32_wgrad(d, x, gy, weight, x2=None):
+  return _wgrad(F32, d, x, gy, weight, x2)
+
+
+def _aten_wgrad(d, x, g, weight, transposed=False):
+  """dL/dW on aten (MIOpen): explicit padding where TF SAME is asymmetric (stride
+  2: one more pixel after)."""
+  if transposed:
+    return torch.ops.aten.convolution_backward(
+        g, x, weight.to(g.dtype), None, [d.stride, d.stride], [d.pad_t, d.pad_l], [1, 1], True,
+        [0, 0], 1, [False, True, False])[1].to(weight.dtype)
+  pb = max((d.OH - 1) * d.stride + d.KH - d.H - d.pad_t, 0)
+  pr = max((d.OW - 1) * d.stride + d.KW - d.W - d.pad_l, 0)
+  if pb == d.pad_t and pr == d.pad_l:
+    xp, pad = x, [d.pad_t, d.pad_l]
+  else:
+    xp, pad = torch.nn.functional.pad(x, (d.pad_l, pr, d.pad_t, pb)), [0, 0]
+  return torch.ops.aten.convolution_backward(
+      g, xp, weight.to(g.dtype), None, [d.stride, d.stride], pad, [1, 1], False,
+      [0, 0], 1, [False, True, False])[1].to(weight.dtype)
+
+
+def _weight_gradient(p, d, x, gy, weight, x2=None, transposed=False):
+  """dL/dW of the descriptor's convolution (x, x2: its input; gy: its output
+  gradient) on the precision's kernel where it takes the geometry, else on aten
+  -- of the concatenated input, which only fp32 layers reach: nets.py asks
+  wgrad_bytes before it hands a bf16 skip connection over.  transposed: the layer
+  is the descriptor's data gradient, so the tensors arrive with their roles
+  swapped (x = the layer's output gradient, gy = its input)."""
+  if (OWN_WGRAD or p is not BF16) and wgrad_bytes(p, d) > 0:
+    return _wgrad(p, d, x, gy, weight, x2)
+  if transposed:
+    return _aten_wgrad(d, gy, x, weight, True)
+  return _aten_wgrad(d, x if x2 is None else torch.cat([x, x2], 1), gy, weight)
+
+
+def _cl_f32_copy(t):
+  """t as an fp32 channels-last 16-byte aligned tensor (a copy only if needed)."""
+  t = t.float().contiguous(memory_format=torch.channels_last)
+  if t.data_ptr() % 16:
+    t = t.clone(memory_format=torch.channels_last)
+  return t
+
+
+def _incoming(p, g):
+  """The gradient autograd hands over as the kernels read it: channels-last in the
+  precision's dtype; fp32 is also cloned where it is not 16-byte aligned."""
+  if p is F32:
+    return _cl_f32_copy(g)
+  if g.dtype != torch.bfloat16:
+    g = g.to(torch.bfloat16)
+  return g.contiguous(memory_format=torch.channels_last)
+
+
+class _Conv2d(torch.autograd.Function):
   """slim.conv2d without bias (reference nets.py: the arg_scope's conv2d) --
-  forward and data gradient on lsi_conv2d_fwd / lsi_conv2d_bwd_data, the weight
-  gradient on lsi_conv3x3_wgrad (3 x 3 stride 1 at >= 200 k pixels: the row-ring
-  kernel) or lsi_conv2d_wgrad_cat (every other shape the library takes:
-  lsi_conv2d_wgrad_workspace_bytes > 0); aten (MIOpen) only for what is left."""
+  forward and data gradient on lsi_conv2d[_f32]_run; the weight gradient, bf16
+  only, on lsi_conv3x3_wgrad (3 x 3 stride 1 at >= 200 k pixels: the row-ring
+  kernel), else on lsi_conv2d_wgrad_cat / lsi_conv2d_wgrad_f32 (every shape they
+  take: workspace bytes > 0); aten (MIOpen) only for what is left."""
 
   @staticmethod
-  def forward(ctx, x, weight, stride, pad_t, pad_l, oh, ow, bn_groups=0):
+  def forward(ctx, p, x, weight, stride, pad_t, pad_l, oh, ow, bn_groups):
     n, cin, h, w = x.shape
     cout, _, kh, kw = weight.shape
     desc = _conv_desc(n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l)
-    ctx.desc = desc
+    ctx.p, ctx.desc = p, desc
     ctx.save_for_backward(x, weight)
-    return _igemm('lsi_conv2d_fwd', desc, x, weight, _empty_cl(n, cout, oh, ow, x.device),
-                  bn_groups, True)
+    return _run(p, desc, 0, weight, x, _empty_cl(n, cout, oh, ow, x.device, p.dtype),
+                bn_groups=bn_groups, training=True)
 
   @staticmethod
   def backward(ctx, g):
     x, weight = ctx.saved_tensors
-    d = ctx.desc
-    if g.dtype != torch.bfloat16:
-      g = g.to(torch.bfloat16)
-    g = g.contiguous(memory_format=torch.channels_last)
+    p, d = ctx.p, ctx.desc
+    g = _incoming(p, g)
     gx = gw = None
-    if ctx.needs_input_grad[1]:   # (first: it may go to the side stream)
+    if ctx.needs_input_grad[2]:   # (first: it may go to the side stream)
       def wgrad():
-        if (d.KH == 3 and d.KW == 3 and d.stride == 1 and d.pad_t == 1 and d.pad_l == 1 and
-            wgrad_supported(x, d.Cin, d.Cout, 3, 1)):
+        if (p is BF16 and d.KH == 3 and d.KW == 3 and d.stride == 1 and d.pad_t == 1 and
+            d.pad_l == 1 and wgrad_supported(x, d.Cin, d.Cout, 3, 1)):
           return _weight_grad(x, g, weight)    # (the row-ring kernel: full / half resolution)
-        if OWN_WGRAD and _igemm_wgrad_bytes(d) > 0:
-          return _igemm_wgrad(d, x, g, weight)
-        # explicit padding: TF SAME is asymmetric for stride 2 (one more after)
-        pb = max((d.OH - 1) * d.stride + d.KH - d.H - d.pad_t, 0)
-        pr = max((d.OW - 1) * d.stride + d.KW - d.W - d.pad_l, 0)
-        if pb == d.pad_t and pr == d.pad_l:
-          xp, pad = x, [d.pad_t, d.pad_l]
-        else:
-          xp, pad = torch.nn.functional.pad(x, (d.pad_l, pr, d.pad_t, pb)), [0, 0]
-        return torch.ops.aten.convolution_backward(
-            g, xp, weight.to(g.dtype), None, [d.stride, d.stride], pad, [1, 1], False,
-            [0, 0], 1, [False, True, False])[1].to(weight.dtype)
+        return _weight_gradient(p, d, x, g, weight)
       gw = _wgrad_async(weight, wgrad, x, g)
-    if ctx.needs_input_grad[0]:
-      gx = _igemm('lsi_conv2d_bwd_data', d, g, weight,
-                  _empty_cl(d.N, d.Cin, d.H, d.W, x.device))
-    return gx, gw, None, None, None, None, None, None
+    if ctx.needs_input_grad[1]:
+      gx = _run(p, d, 1, weight, g, _empty_cl(d.N, d.Cin, d.H, d.W, x.device, p.dtype))
+    return None, gx, gw, None, None, None, None, None, None
 
 
-def conv2d(x, weight, stride, pad_t, pad_l, oh, ow, bn_groups=0):
-  """bn_groups > 0: the batch-norm sums of the output (that many sub-batch groups)
-  are left for _hip_bn.batch_norm_relu(out, ..., groups, prestat=True), which has
-  to be the next batch-norm call on this stream."""
-  return _Conv2dIgemm.apply(x, weight, stride, pad_t, pad_l, oh, ow, bn_groups)
+class _Conv2dCat(torch.autograd.Function):
+  """slim.conv2d over a skip connection's concatenation (reference nets.py:104-106,
+  300-345) without the concatenated tensor: forward, data gradient (into two
+  tensors) and weight gradient read / write the two activations directly."""
+
+  @staticmethod
+  def forward(ctx, p, x1, x2, weight, stride, pad_t, pad_l, oh, ow, bn_groups):
+    n, c1, h, w = x1.shape
+    cout, cin, kh, kw = weight.shape
+    assert cin == c1 + x2.shape[1]
+    desc = _conv_desc(n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l)
+    ctx.p, ctx.desc = p, desc
+    ctx.save_for_backward(x1, x2, weight)
+    return _run(p, desc, 0, weight, x1, _empty_cl(n, cout, oh, ow, x1.device, p.dtype),
+                x2=x2, c1=c1, bn_groups=bn_groups, training=True)
+
+  @staticmethod
+  def backward(ctx, g):
+    x1, x2, weight = ctx.saved_tensors
+    p, d = ctx.p, ctx.desc
+    dev = x1.device
+    c1 = x1.shape[1]
+    g = _incoming(p, g)
+    gx1 = gx2 = gw = None
+    if ctx.needs_input_grad[3]:   # (first: it may go to the side stream)
+      gw = _wgrad_async(weight, lambda: _weight_gradient(p, d, x1, g, weight, x2), x1, x2, g)
+    if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+      gx1 = _empty_cl(d.N, c1, d.H, d.W, dev, p.dtype)
+      gx2 = _empty_cl(d.N, d.Cin - c1, d.H, d.W, dev, p.dtype)
+      _run(p, d, 1, weight, g, gx1, out2=gx2, c1=c1)
+    return None, gx1, gx2, gw, None, None, None, None, None, None
+
+
+class _ConvTranspose2d(torch.autograd.Function):
+  """slim.conv2d_transpose 4 x 4 stride 2 (torch ConvTranspose2d(k, stride 2,
+  padding p); reference nets.py:100-103, 295-345): the data gradient (mode 1) of
+  the forward convolution {2h x 2w x Cout_T -> h x w x Cin_T} with the same weight
+  memory -- four parity classes, 2 x 2 taps each; its own data gradient is that
+  forward convolution (mode 0); its weight gradient that convolution's with the
+  roles of the tensors swapped."""
+
+  @staticmethod
+  def forward(ctx, p, x, weight, stride, pad, bn_groups):
+    n, cin_t, h, w = x.shape
+    _, cout_t, kh, kw = weight.shape
+    desc = _conv_desc(n, stride * h, stride * w, cout_t, h, w, cin_t, kh, kw, stride, pad, pad)
+    ctx.p, ctx.desc = p, desc
+    ctx.save_for_backward(x, weight)
+    return _run(p, desc, 1, weight, x,
+                _empty_cl(n, cout_t, stride * h, stride * w, x.device, p.dtype),
+                bn_groups=bn_groups, training=True)
+
+  @staticmethod
+  def backward(ctx, g):
+    x, weight = ctx.saved_tensors
+    p, d = ctx.p, ctx.desc
+    g = _incoming(p, g)
+    gx = gw = None
+    if ctx.needs_input_grad[2]:   # (first: it may go to the side stream)
+      # the descriptor's convolution: "input" = this layer's output gradient,
+      # "output gradient" = this layer's input
+      gw = _wgrad_async(weight, lambda: _weight_gradient(p, d, g, x, weight, transposed=True),
+                        x, g)
+    if ctx.needs_input_grad[1]:
+      gx = _run(p, d, 0, weight, g, _empty_cl(d.N, d.Cout, d.OH, d.OW, x.device, p.dtype))
+    return None, gx, gw, None, None, None
+
+
+def conv2d(x, weight, stride, pad_t, pad_l, oh, ow, bn_groups=0, precision=BF16):
+  """bn_groups > 0 (bf16 only): the batch-norm sums of the output (that many
+  sub-batch groups) are left for _hip_bn.batch_norm_relu(out, ..., groups,
+  prestat=True), which has to be the next batch-norm call on this stream."""
+  return _Conv2d.apply(precision, x, weight, stride, pad_t, pad_l, oh, ow, bn_groups)
+
+
+def conv2d_cat(x1, x2, weight, stride, pad_t, pad_l, oh, ow, bn_groups=0, precision=BF16):
+  return _Conv2dCat.apply(precision, x1, x2, weight, stride, pad_t, pad_l, oh, ow, bn_groups)
+
+
+def conv_transpose2d(x, weight, stride=2, pad=1, bn_groups=0, precision=BF16):
+  return _ConvTranspose2d.apply(precision, x, weight, stride, pad, bn_groups)
+
+
+def conv2d_f32(x, weight, stride, pad_t, pad_l, oh, ow):
+  return _Conv2d.apply(F32, x, weight, stride, pad_t, pad_l, oh, ow, 0)
+
+
+def conv2d_cat_f32(x1, x2, weight, stride, pad_t, pad_l, oh, ow):
+  return _Conv2dCat.apply(F32, x1, x2, weight, stride, pad_t, pad_l, oh, ow, 0)
+
+
+def conv_transpose2d_f32(x, weight, stride=2, pad=1):
+  return _ConvTranspose2d.apply(F32, x, weight, stride, pad, 0)
 
 
 CAT_CONV = os.environ.get('LSI_CAT_CONV', '1') != '0'
 
 
-def cat_supported(x1, x2, cout, k, stride):
-  """A convolution over tf.concat([x1, x2], axis=3) read from the two tensors
-  (lsi_conv2d_fwd_cat / _bwd_data_cat / _wgrad_cat): both bf16 channels-last on
-  the GPU with the same N, H, W; channel counts multiples of 32, x1's also of the
-  data-gradient kernel's channel block (64 when the sum is a multiple of 64)."""
-  if not (CAT_CONV and OWN_WGRAD and _cl_bf16(x1) and _cl_bf16(x2)):
+def _cat_supported(p, x1, x2, cout, k, stride, min_pixels=0):
+  if not (_cl(x1, p.dtype) and _cl(x2, p.dtype)):
     return False
   if x1.shape[0] != x2.shape[0] or x1.shape[2:] != x2.shape[2:]:
     return False
   c1, c2 = x1.shape[1], x2.shape[1]
   blk = 64 if (c1 + c2) % 64 == 0 else 32
   if not (c1 % 32 == 0 and c2 % 32 == 0 and c1 % blk == 0 and 1 <= k <= 7 and
-          stride in (1, 2) and x1.shape[0] * x1.shape[2] * x1.shape[3] >= IGEMM_MIN_PIXELS):
+          stride in (1, 2) and x1.shape[0] * x1.shape[2] * x1.shape[3] >= min_pixels):
     return False
   n, _, h, w = x1.shape
-  oh, ow = -(-h // stride), -(-w // stride)
-  pad = max((oh - 1) * stride + k - h, 0) // 2
-  return _desc_supported(n, h, w, c1 + c2, oh, ow, cout, k, stride, pad)
+  oh, ow, pad_t, pad_l = same_geometry(h, w, k, stride)
+  return _desc_supported(p, (n, h, w, c1 + c2, oh, ow, cout, k, k, stride, pad_t, pad_l))
 
 
-class _Conv2dCatIgemm(torch.autograd.Function):
-  """slim.conv2d over a skip connection's concatenation (reference nets.py:104-106,
-  300-345) without the concatenated tensor: forward, data gradient (into two
-  tensors) and weight gradient read / write the two activations directly."""
-
-  @staticmethod
-  def forward(ctx, x1, x2, weight, stride, pad_t, pad_l, oh, ow, bn_groups=0):
-    n, c1, h, w = x1.shape
-    c2 = x2.shape[1]
-    cout, cin, kh, kw = weight.shape
-    assert cin == c1 + c2
-    desc = _conv_desc(n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l)
-    ctx.desc = desc
-    ctx.save_for_backward(x1, x2, weight)
-    dev = x1.device
-    out = _empty_cl(n, cout, oh, ow, dev)
-    packed = _packed(desc, 0, weight, True)
-    ws_ptr = 0
-    if bn_groups:
-      from lsi.nnutils import _hip_bn  # pylint: disable=g-import-not-at-top
-      ws_ptr = _hip_bn.stats_workspace(tuple(out.shape), dev, 1, bn_groups).data_ptr()
-    _run(desc, 0, packed.data_ptr(), dev, x=x1.data_ptr(), x2=x2.data_ptr(), out=out.data_ptr(),
-         c1=c1, bn_ws=ws_ptr, groups=bn_groups)
-    return out
-
-  @staticmethod
-  def backward(ctx, g):
-    x1, x2, weight = ctx.saved_tensors
-    d = ctx.desc
-    dev = x1.device
-    c1 = x1.shape[1]
-    if g.dtype != torch.bfloat16:
-      g = g.to(torch.bfloat16)
-    g = g.contiguous(memory_format=torch.channels_last)
-    lib = _C.lib()
-    gx1 = gx2 = gw = None
-    if ctx.needs_input_grad[2]:   # (first: it may go to the side stream)
-      gw = _wgrad_async(weight, lambda: _igemm_wgrad(d, x1, g, weight, x2), x1, x2, g)
-    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-      gx1 = _empty_cl(d.N, c1, d.H, d.W, dev)
-      gx2 = _empty_cl(d.N, d.Cin - c1, d.H, d.W, dev)
-      packed = _packed(d, 1, weight)
-      _run(d, 1, packed.data_ptr(), dev, x=g.data_ptr(), out=gx1.data_ptr(),
-           out2=gx2.data_ptr(), c1=c1)
-    return gx1, gx2, gw, None, None, None, None, None, None
+def cat_supported(x1, x2, cout, k, stride):
+  """A convolution over tf.concat([x1, x2], axis=3) read from the two tensors
+  (lsi_conv2d_run with x2 / out2, lsi_conv2d_wgrad_cat): both bf16 channels-last on
+  the GPU with the same N, H, W; channel counts multiples of 32, x1's also of the
+  data-gradient kernel's channel block (64 when the sum is a multiple of 64)."""
+  return (CAT_CONV and OWN_WGRAD and
+          _cat_supported(BF16, x1, x2, cout, k, stride, IGEMM_MIN_PIXELS))
 
 
-def conv2d_cat(x1, x2, weight, stride, pad_t, pad_l, oh, ow, bn_groups=0):
-  return _Conv2dCatIgemm.apply(x1, x2, weight, stride, pad_t, pad_l, oh, ow, bn_groups)
+def f32_cat_supported(x1, x2, cout, k, stride):
+  """The same on the fp32 kernels for two fp32 tensors."""
+  return _cat_supported(F32, x1, x2, cout, k, stride)
 
 
-class _ConvTranspose2dIgemm(torch.autograd.Function):
-  """slim.conv2d_transpose 4 x 4 stride 2 (torch ConvTranspose2d(k, stride 2,
-  padding p); reference nets.py:100-103, 295-345): the data gradient of the
-  forward convolution {2h x 2w x Cout_T -> h x w x Cin_T} with the same weight
-  memory -- four parity classes, 2 x 2 taps each (lsi_conv2d_bwd_data); its own
-  data gradient is that forward convolution (lsi_conv2d_fwd)."""
-
-  @staticmethod
-  def forward(ctx, x, weight, stride, pad, bn_groups=0):
-    n, cin_t, h, w = x.shape
-    _, cout_t, kh, kw = weight.shape
-    desc = _conv_desc(n, stride * h, stride * w, cout_t, h, w, cin_t, kh, kw, stride, pad, pad)
-    ctx.desc = desc
-    ctx.save_for_backward(x, weight)
-    ctx.args = (stride, pad)
-    return _igemm('lsi_conv2d_bwd_data', desc, x, weight,
-                  _empty_cl(n, cout_t, stride * h, stride * w, x.device), bn_groups,
-                  True)
-
-  @staticmethod
-  def backward(ctx, g):
-    x, weight = ctx.saved_tensors
-    d = ctx.desc
-    stride, pad = ctx.args
-    if g.dtype != torch.bfloat16:
-      g = g.to(torch.bfloat16)
-    g = g.contiguous(memory_format=torch.channels_last)
-    gx = gw = None
-    if ctx.needs_input_grad[1]:   # (first: it may go to the side stream)
-      def wgrad():
-        if OWN_WGRAD and _igemm_wgrad_bytes(d) > 0:
-          # the descriptor's convolution: "input" = this layer's output gradient,
-          # "output gradient" = this layer's input
-          return _igemm_wgrad(d, g, x, weight)
-        return torch.ops.aten.convolution_backward(
-            g, x, weight.to(g.dtype), None, [stride, stride], [pad, pad], [1, 1], True,
-            [0, 0], 1, [False, True, False])[1].to(weight.dtype)
-      gw = _wgrad_async(weight, wgrad, x, g)
-    if ctx.needs_input_grad[0]:
-      gx = _igemm('lsi_conv2d_fwd', d, g, weight,
-                  _empty_cl(d.N, d.Cout, d.OH, d.OW, x.device))
-    return gx, gw, None, None, None
-
-
-def conv_transpose2d(x, weight, stride=2, pad=1, bn_groups=0):
-  return _ConvTranspose2dIgemm.apply(x, weight, stride, pad, bn_groups)
+def _convt_supported(p, x, cin, cout, k, stride, min_pixels=0):
+  if not (_cl(x, p.dtype) and x.shape[1] == cin and k <= 7 and stride == 2 and
+          x.shape[0] * x.shape[2] * x.shape[3] * 4 >= min_pixels):
+    return False
+  n, _, h, w = x.shape
+  # (the descriptor of _ConvTranspose2d: the convolution whose data gradient this
+  # layer's forward is; padding 1)
+  return _desc_supported(p, (n, stride * h, stride * w, cout, h, w, cin, k, k, stride, 1, 1))
 
 
 def convt_supported(x, cin, cout, k, stride):
-  if not (_cl_bf16(x) and x.shape[1] == cin and k <= 7 and stride == 2 and
-          x.shape[0] * x.shape[2] * x.shape[3] * 4 >= IGEMM_MIN_PIXELS):
-    return False
-  n, _, h, w = x.shape
-  # (the descriptor of _ConvTranspose2dIgemm: the convolution whose data gradient
-  # this layer's forward is)
-  return _desc_supported(n, stride * h, stride * w, cout, h, w, cin, k, stride, 1)
+  return _convt_supported(BF16, x, cin, cout, k, stride, IGEMM_MIN_PIXELS)
+
+
+def f32_convt_supported(x, cin, cout, k, stride):
+  """A transposed convolution (k x k, stride 2, padding 1) on the fp32 kernels."""
+  return _convt_supported(F32, x, cin, cout, k, stride)
 
 
 # ---- the first convolution: 3 image channels (csrc/lsi_conv_first.hip) -------------
@@ -899,24 +1006,13 @@ def first_supported(x, cin, cout, k, stride):
   if not x.is_contiguous(memory_format=torch.channels_last):
     return False
   n, _, h, w = x.shape
-  oh, ow = -(-h // stride), -(-w // stride)
-  pad = max((oh - 1) * stride + k - h, 0) // 2
-  key = ('first', n, h, w, cin, oh, ow, cout, k, stride, pad)
+  oh, ow, pad_t, pad_l = same_geometry(h, w, k, stride)
+  key = ('first', (n, h, w, cin, oh, ow, cout, k, k, stride, pad_t, pad_l))
   ok = _DESC_OK.get(key)
   if ok is None:
-    d = _conv_desc(n, h, w, cin, oh, ow, cout, k, k, stride, pad, pad)
+    d = _conv_desc(*key[1])
     ok = _DESC_OK[key] = bool(_C.lib().lsi_conv2d_first_supported(ctypes.byref(d)))
   return ok
-
-
-def _weight_layout(weight):
-  """(tensor the kernels read in place, layout bit): fp32 contiguous (0) or
-  channels-last strides (2); anything else is copied to fp32 contiguous."""
-  w = weight.detach()
-  cl = _pack_layout(w)
-  if cl is None:
-    return w.float().contiguous(), 0
-  return w, cl
 
 
 class _Conv2dFirst(torch.autograd.Function):
@@ -930,8 +1026,8 @@ class _Conv2dFirst(torch.autograd.Function):
     cout, _, kh, kw = weight.shape
     desc = _conv_desc(n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l)
     dev = x.device
-    out = _empty_cl(n, cout, oh, ow, dev)
-    wsrc, cl = _weight_layout(weight)
+    out = _empty_cl(n, cout, oh, ow, dev, torch.bfloat16)
+    wsrc, cl = _pack_source(weight)
     ws_ptr = 0
     if bn_groups:
       from lsi.nnutils import _hip_bn  # pylint: disable=g-import-not-at-top
@@ -958,10 +1054,7 @@ class _Conv2dFirst(torch.autograd.Function):
       lib = _C.lib()
       nbytes = int(lib.lsi_conv2d_first_wgrad_workspace_bytes(ctypes.byref(d)))
       ws = _wgrad_workspace(dev, nbytes)
-      cl = 2 if (not weight.is_contiguous() and
-                 weight.is_contiguous(memory_format=torch.channels_last)) else 0
-      gw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=dev,
-                       memory_format=torch.channels_last if cl else torch.contiguous_format)
+      gw, cl = _grad_like(weight)
       rc = lib.lsi_conv2d_first_wgrad(ctypes.byref(d), x.data_ptr(),
                                       int(x.dtype == torch.bfloat16), g.data_ptr(), gw.data_ptr(),
                                       cl, ws.data_ptr(), ws.numel() * 4, _C.stream_ptr(dev))
@@ -974,273 +1067,3 @@ class _Conv2dFirst(torch.autograd.Function):
 
 def conv2d_first(x, weight, stride, pad_t, pad_l, oh, ow, bn_groups=0):
   return _Conv2dFirst.apply(x, weight, stride, pad_t, pad_l, oh, ow, bn_groups)
-
-
-# ---- exact fp32 convolutions (csrc/lsi_conv_f32.hip) --------------------------------
-# The fp32 counterparts of _Conv2dIgemm, _Conv2dCatIgemm and _ConvTranspose2dIgemm on
-# fp32 channels-last activations (the reference's own arithmetic: --bf16 false),
-# opted into with nets.F32_CONV (LSI_F32_CONV=1, the trainer's --fp32_convs own).
-# Forward, data gradient and weight gradient on the matrix cores
-# (v_mfma_f32_16x16x4_f32: exact fp32, deterministic folds); the batch norm behind
-# them stays on the two-pass kernels (no statistics in the epilogue).  The weight
-# gradients the kernel does not take (partial sums over the workspace cap: the
-# bottleneck layers) go to aten.
-_F32_OK = {}
-_F32_WGRAD_BYTES = {}
-_F32_RUN_BYTES = {}
-USED_F32 = [0]   # kernel launches of this route (tests check that it ran)
-
-
-def _cl_f32(t):
-  return (t.is_cuda and t.dim() == 4 and t.dtype == torch.float32 and
-          t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0)
-
-
-def _f32_desc_supported(n, h, w, cin, oh, ow, cout, k, stride, pad):
-  """lsi_conv2d_f32_supported for the geometry, cached; the forward's AND the data
-  gradient's channel rules (the data gradient takes Cout as its input)."""
-  key = (n, h, w, cin, oh, ow, cout, k, stride, pad)
-  ok = _F32_OK.get(key)
-  if ok is None:
-    d = _conv_desc(n, h, w, cin, oh, ow, cout, k, k, stride, pad, pad)
-    ok = _F32_OK[key] = bool(_C.lib().lsi_conv2d_f32_supported(ctypes.byref(d))) and \
-        cout % 32 == 0
-  return ok
-
-
-def f32_supported(x, cin, cout, k, stride):
-  """fp32 channels-last 16-byte aligned GPU activations, channel counts that are
-  multiples of 32, kernels up to 7 x 7, stride 1 or 2 (lsi_conv2d_f32_supported)."""
-  if not (_cl_f32(x) and x.shape[1] == cin and 1 <= k <= 7 and stride in (1, 2)):
-    return False
-  n, _, h, w = x.shape
-  oh, ow = -(-h // stride), -(-w // stride)
-  pad = max((oh - 1) * stride + k - h, 0) // 2
-  return _f32_desc_supported(n, h, w, cin, oh, ow, cout, k, stride, pad)
-
-
-def f32_cat_supported(x1, x2, cout, k, stride):
-  """A convolution over tf.concat([x1, x2], axis=3) on the fp32 kernels, read from
-  the two tensors: both fp32 channels-last with the same N, H, W; x1's channels a
-  multiple of the data-gradient kernel's block (64 when the sum is a multiple of
-  64, else 32)."""
-  if not (_cl_f32(x1) and _cl_f32(x2)):
-    return False
-  if x1.shape[0] != x2.shape[0] or x1.shape[2:] != x2.shape[2:]:
-    return False
-  c1, c2 = x1.shape[1], x2.shape[1]
-  blk = 64 if (c1 + c2) % 64 == 0 else 32
-  if not (c1 % 32 == 0 and c2 % 32 == 0 and c1 % blk == 0 and 1 <= k <= 7 and
-          stride in (1, 2)):
-    return False
-  n, _, h, w = x1.shape
-  oh, ow = -(-h // stride), -(-w // stride)
-  pad = max((oh - 1) * stride + k - h, 0) // 2
-  return _f32_desc_supported(n, h, w, c1 + c2, oh, ow, cout, k, stride, pad)
-
-
-def f32_convt_supported(x, cin, cout, k, stride):
-  """A transposed convolution (k x k, stride 2, padding 1) on the fp32 kernels."""
-  if not (_cl_f32(x) and x.shape[1] == cin and k <= 7 and stride == 2):
-    return False
-  n, _, h, w = x.shape
-  return _f32_desc_supported(n, stride * h, stride * w, cout, h, w, cin, k, stride, 1)
-
-
-def f32_wgrad_bytes(d):
-  """lsi_conv2d_wgrad_f32_workspace_bytes per geometry (0: the library takes it)."""
-  key = (d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout, d.KH, d.KW, d.stride, d.pad_t, d.pad_l)
-  n = _F32_WGRAD_BYTES.get(key)
-  if n is None:
-    n = _F32_WGRAD_BYTES[key] = int(_C.lib().lsi_conv2d_wgrad_f32_workspace_bytes(ctypes.byref(d)))
-  return n
-
-
-def _cl_f32_copy(t):
-  """t as an fp32 channels-last 16-byte aligned tensor (a copy only if needed)."""
-  t = t.float().contiguous(memory_format=torch.channels_last)
-  if t.data_ptr() % 16:
-    t = t.clone(memory_format=torch.channels_last)
-  return t
-
-
-def _empty_cl_f32(n, c, h, w, dev):
-  return torch.empty((n, c, h, w), dtype=torch.float32, device=dev,
-                     memory_format=torch.channels_last)
-
-
-def _run_f32(desc, mode, weight, dev, x, out, x2=None, out2=None, c1=0, training=False):
-  """lsi_conv2d_f32_run: forward (mode 0) / data gradient (mode 1) with the
-  fp32 pack of `weight`, the split over the input channels where the library
-  asks for a workspace."""
-  if training:
-    _FWD_SEQ[0] += 1
-  packed = _packed(desc, mode, weight, training, torch.float32)
-  io = _C.LsiConvIO()
-  io.x, io.packed, io.out = x.data_ptr(), packed.data_ptr(), out.data_ptr()
-  io.x2 = x2.data_ptr() if x2 is not None else None
-  io.out2 = out2.data_ptr() if out2 is not None else None
-  io.c1 = int(c1)
-  key = (mode, desc.N, desc.H, desc.W, desc.Cin, desc.OH, desc.OW, desc.Cout, desc.KH,
-         desc.KW, desc.stride, desc.pad_t, desc.pad_l)
-  nb = _F32_RUN_BYTES.get(key)
-  if nb is None:
-    nb = _F32_RUN_BYTES[key] = int(_C.lib().lsi_conv2d_f32_workspace_bytes(ctypes.byref(desc), mode))
-  if nb and SPLITK:
-    ws = _wgrad_workspace(dev, nb)
-    io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-  rc = _C.lib().lsi_conv2d_f32_run(ctypes.byref(desc), mode, ctypes.byref(io), _C.stream_ptr(dev))
-  if rc:
-    _C.check(rc, 'lsi_conv2d_f32_run(mode %d)' % mode)
-  USED_F32[0] += 1
-  return out
-
-
-def _f32_wgrad(d, x, gy, weight, x2=None):
-  """lsi_conv2d_wgrad_f32: x (and x2) = the descriptor's input, gy its output
-  gradient; the gradient in the parameter's own memory layout."""
-  dev = x.device
-  ws = _wgrad_workspace(dev, f32_wgrad_bytes(d))
-  cl = 2 if (weight.dim() == 4 and not weight.is_contiguous() and
-             weight.is_contiguous(memory_format=torch.channels_last)) else 0
-  gw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=dev,
-                   memory_format=torch.channels_last if cl else torch.contiguous_format)
-  rc = _C.lib().lsi_conv2d_wgrad_f32(
-      ctypes.byref(d), x.data_ptr(), x2.data_ptr() if x2 is not None else 0,
-      x.shape[1] if x2 is not None else 0, gy.data_ptr(), gw.data_ptr(), cl, ws.data_ptr(),
-      ws.numel() * 4, _C.stream_ptr(dev))
-  if rc:
-    _C.check(rc, 'lsi_conv2d_wgrad_f32')
-  USED_F32[0] += 1
-  return gw if weight.dtype == torch.float32 else gw.to(weight.dtype)
-
-
-def _aten_wgrad(d, x, g, weight, transposed=False):
-  """dL/dW on aten (MIOpen): explicit padding where TF SAME is asymmetric."""
-  if transposed:
-    return torch.ops.aten.convolution_backward(
-        g, x, weight.to(g.dtype), None, [d.stride, d.stride], [d.pad_t, d.pad_l], [1, 1], True,
-        [0, 0], 1, [False, True, False])[1].to(weight.dtype)
-  pb = max((d.OH - 1) * d.stride + d.KH - d.H - d.pad_t, 0)
-  pr = max((d.OW - 1) * d.stride + d.KW - d.W - d.pad_l, 0)
-  if pb == d.pad_t and pr == d.pad_l:
-    xp, pad = x, [d.pad_t, d.pad_l]
-  else:
-    xp, pad = torch.nn.functional.pad(x, (d.pad_l, pr, d.pad_t, pb)), [0, 0]
-  return torch.ops.aten.convolution_backward(
-      g, xp, weight.to(g.dtype), None, [d.stride, d.stride], pad, [1, 1], False,
-      [0, 0], 1, [False, True, False])[1].to(weight.dtype)
-
-
-class _Conv2dF32(torch.autograd.Function):
-  """slim.conv2d without bias in exact fp32: forward and data gradient on
-  lsi_conv2d_f32_run, the weight gradient on lsi_conv2d_wgrad_f32 (aten where
-  its workspace bytes are 0)."""
-
-  @staticmethod
-  def forward(ctx, x, weight, stride, pad_t, pad_l, oh, ow):
-    n, cin, h, w = x.shape
-    cout, _, kh, kw = weight.shape
-    desc = _conv_desc(n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l)
-    ctx.desc = desc
-    ctx.save_for_backward(x, weight)
-    return _run_f32(desc, 0, weight, x.device, x, _empty_cl_f32(n, cout, oh, ow, x.device),
-                    training=True)
-
-  @staticmethod
-  def backward(ctx, g):
-    x, weight = ctx.saved_tensors
-    d = ctx.desc
-    g = _cl_f32_copy(g)
-    gx = gw = None
-    if ctx.needs_input_grad[1]:   # (first: it may go to the side stream)
-      def wgrad():
-        if f32_wgrad_bytes(d) > 0:
-          return _f32_wgrad(d, x, g, weight)
-        return _aten_wgrad(d, x, g, weight)
-      gw = _wgrad_async(weight, wgrad, x, g)
-    if ctx.needs_input_grad[0]:
-      gx = _run_f32(d, 1, weight, x.device, g, _empty_cl_f32(d.N, d.Cin, d.H, d.W, x.device))
-    return gx, gw, None, None, None, None, None
-
-
-def conv2d_f32(x, weight, stride, pad_t, pad_l, oh, ow):
-  return _Conv2dF32.apply(x, weight, stride, pad_t, pad_l, oh, ow)
-
-
-class _Conv2dCatF32(torch.autograd.Function):
-  """slim.conv2d over a skip connection's concatenation in exact fp32, without
-  the concatenated tensor (forward, data gradient into two tensors, weight
-  gradient)."""
-
-  @staticmethod
-  def forward(ctx, x1, x2, weight, stride, pad_t, pad_l, oh, ow):
-    n, c1, h, w = x1.shape
-    cout, cin, kh, kw = weight.shape
-    assert cin == c1 + x2.shape[1]
-    desc = _conv_desc(n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l)
-    ctx.desc = desc
-    ctx.save_for_backward(x1, x2, weight)
-    return _run_f32(desc, 0, weight, x1.device, x1, _empty_cl_f32(n, cout, oh, ow, x1.device),
-                    x2=x2, c1=c1, training=True)
-
-  @staticmethod
-  def backward(ctx, g):
-    x1, x2, weight = ctx.saved_tensors
-    d = ctx.desc
-    dev = x1.device
-    c1 = x1.shape[1]
-    g = _cl_f32_copy(g)
-    gx1 = gx2 = gw = None
-    if ctx.needs_input_grad[2]:
-      def wgrad():
-        if f32_wgrad_bytes(d) > 0:
-          return _f32_wgrad(d, x1, g, weight, x2)
-        return _aten_wgrad(d, torch.cat([x1, x2], 1), g, weight)
-      gw = _wgrad_async(weight, wgrad, x1, x2, g)
-    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-      gx1 = _empty_cl_f32(d.N, c1, d.H, d.W, dev)
-      gx2 = _empty_cl_f32(d.N, d.Cin - c1, d.H, d.W, dev)
-      _run_f32(d, 1, weight, dev, g, gx1, out2=gx2, c1=c1)
-    return gx1, gx2, gw, None, None, None, None, None
-
-
-def conv2d_cat_f32(x1, x2, weight, stride, pad_t, pad_l, oh, ow):
-  return _Conv2dCatF32.apply(x1, x2, weight, stride, pad_t, pad_l, oh, ow)
-
-
-class _ConvTranspose2dF32(torch.autograd.Function):
-  """slim.conv2d_transpose 4 x 4 stride 2 in exact fp32: the data gradient of the
-  forward convolution {2h x 2w x Cout_T -> h x w x Cin_T} (four parity classes);
-  its own data gradient is that forward convolution; its weight gradient that
-  convolution's with the roles of the tensors swapped."""
-
-  @staticmethod
-  def forward(ctx, x, weight, stride, pad):
-    n, cin_t, h, w = x.shape
-    _, cout_t, kh, kw = weight.shape
-    desc = _conv_desc(n, stride * h, stride * w, cout_t, h, w, cin_t, kh, kw, stride, pad, pad)
-    ctx.desc = desc
-    ctx.save_for_backward(x, weight)
-    return _run_f32(desc, 1, weight, x.device, x,
-                    _empty_cl_f32(n, cout_t, stride * h, stride * w, x.device), training=True)
-
-  @staticmethod
-  def backward(ctx, g):
-    x, weight = ctx.saved_tensors
-    d = ctx.desc
-    g = _cl_f32_copy(g)
-    gx = gw = None
-    if ctx.needs_input_grad[1]:
-      def wgrad():
-        if f32_wgrad_bytes(d) > 0:
-          return _f32_wgrad(d, g, x, weight)
-        return _aten_wgrad(d, x, g, weight, transposed=True)
-      gw = _wgrad_async(weight, wgrad, x, g)
-    if ctx.needs_input_grad[0]:
-      gx = _run_f32(d, 0, weight, x.device, g, _empty_cl_f32(d.N, d.Cout, d.OH, d.OW, x.device))
-    return gx, gw, None, None
-
-
-def conv_transpose2d_f32(x, weight, stride=2, pad=1):
-  return _ConvTranspose2dF32.apply(x, weight, stride, pad)

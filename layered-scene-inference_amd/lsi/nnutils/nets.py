@@ -35,6 +35,7 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
+from lsi.nnutils import _hip_conv
 from lsi.nnutils import helpers as nn_helpers
 
 
@@ -61,9 +62,8 @@ BF16_BATCH_NORM = os.environ.get('LSI_BF16_BN', '1') != '0'
 # `cnv7b`, `icnv7`, `upcnv6/7` are small GEMMs with few tiles for this kernel,
 # where MIOpen is 1.1 - 1.4 x ahead -- 77 us of a 10 ms step in all
 # (tools/conv_bench.py: profiles/r05/conv_bench.txt); by default they too run on
-# the own kernel.
+# the own kernel (_hip_conv.IGEMM_MIN_PIXELS: read there, and here at call time).
 IGEMM_CONV = os.environ.get('LSI_IGEMM_CONV', '1') != '0'
-IGEMM_MIN_PIXELS = int(os.environ.get('LSI_IGEMM_MIN_PIXELS', '0'))
 # fp32 activations outside bf16 autocast (--bf16 false) on the exact-fp32 MFMA
 # kernels (csrc/lsi_conv_f32.hip): every batch-normed convolution with channel
 # counts that are multiples of 32, its data and weight gradients; `cnv1`, the
@@ -81,9 +81,12 @@ def _f32_route(x):
                torch.get_autocast_dtype('cuda') != torch.float32))
 
 
-def _igemm_pays(x, stride):
-  n, _, h, w = x.shape
-  return n * (-(-h // stride)) * (-(-w // stride)) >= IGEMM_MIN_PIXELS
+def _igemm_pays(n, oh, ow):
+  """(pixels on the smaller side of the layer: the output of a stride-2
+  convolution, the input of a transposed one)"""
+  return n * oh * ow >= _hip_conv.IGEMM_MIN_PIXELS
+
+
 # batch norm + ReLU of the conv layers as the fused HIP kernels (csrc/lsi_bn.hip)
 # for channels-last activations on the GPU; LSI_FUSED_BN=0 keeps MIOpen's
 FUSED_BN = os.environ.get('LSI_FUSED_BN', '1') != '0'
@@ -229,68 +232,64 @@ class SlimConv2d(nn.Module):
     self.bn = SlimBatchNorm(cout) if batch_norm else None
     self.activation = activation
 
+  def _route(self, x, cin, cout, oh, ow):
+    """(the first kernel route that takes the layer, the sub-batch groups whose
+    batch-norm sums its epilogue leaves).  The order is behaviour: `first` (cnv1),
+    the heads' 32-channel kernel (`pred`, `c32`), the implicit-GEMM kernel
+    (`igemm`), the library with the own weight gradient (`lib_wgrad`), exact fp32
+    (`f32`); None: the library."""
+    k, s, bn = self.k, self.stride, self.bn is not None
+    if MFMA_CONV and x.is_cuda:
+      # `cnv1`: the image itself (fp32 under autocast: rounded to bf16 inside the
+      # kernel, as autocast's cast would) through the first-layer kernel
+      if (IGEMM_CONV and bn and cin <= 4 and
+          (x.dtype == torch.bfloat16 or
+           (x.dtype == torch.float32 and torch.is_autocast_enabled('cuda') and
+            torch.get_autocast_dtype('cuda') == torch.bfloat16)) and
+          _hip_conv.first_supported(x, cin, cout, k, s)):
+        return 'first', _stats_bn(self.bn, self.activation, x.shape[0], cout)
+      if x.dtype == torch.bfloat16:
+        head = not bn and self.activation == 'sigmoid'
+        if (head or bn) and _hip_conv.supported(x, cin, cout, k, s, head):
+          return ('pred' if head else 'c32'), 0
+        # every other batch-normed layer: forward and data gradient on the
+        # implicit-GEMM kernel, weight gradient on lsi_conv3x3_wgrad or its own
+        if (IGEMM_CONV and bn and _hip_conv.igemm_supported(x, cin, cout, k, s) and
+            _igemm_pays(x.shape[0], oh, ow)):
+          return 'igemm', _stats_bn(self.bn, self.activation, x.shape[0], cout)
+        # forward and data gradient on the library, weight gradient on the
+        # matrix-core kernel (K = pixels)
+        if (bn and torch.is_grad_enabled() and self.conv.weight.requires_grad and
+            _hip_conv.wgrad_supported(x, cin, cout, k, s)):
+          return 'lib_wgrad', 0
+    if bn and _f32_route(x) and _hip_conv.f32_supported(x, cin, cout, k, s):
+      return 'f32', 0
+    return None, 0
+
   def forward(self, x, x2=None):
     """x2: the layer reads tf.concat([x, x2], axis=3) (a skip connection)."""
     if x2 is not None:
       return self.forward_cat(x, x2)
-    if (MFMA_CONV and IGEMM_CONV and x.is_cuda and self.bn is not None and
-        self.conv.weight.shape[1] <= 4 and
-        (x.dtype == torch.bfloat16 or
-         (x.dtype == torch.float32 and torch.is_autocast_enabled('cuda') and
-          torch.get_autocast_dtype('cuda') == torch.bfloat16))):
-      # `cnv1`: the image itself (fp32 under autocast: rounded to bf16 inside the
-      # kernel, as autocast's cast would) through the first-layer kernel
-      from lsi.nnutils import _hip_conv  # pylint: disable=g-import-not-at-top
-      cout, cin = self.conv.weight.shape[:2]
-      if _hip_conv.first_supported(x, cin, cout, self.k, self.stride):
-        ph = _same_pad(x.shape[2], self.k, self.stride)
-        pw = _same_pad(x.shape[3], self.k, self.stride)
-        st = _stats_bn(self.bn, self.activation, x.shape[0], cout)
-        y = _hip_conv.conv2d_first(x, self.conv.weight, self.stride, ph[0], pw[0],
-                                   -(-x.shape[2] // self.stride),
-                                   -(-x.shape[3] // self.stride), st)
-        if st:
-          return _bn_relu(self.bn, y, True)
-        return self._bn_act(y)
-    if MFMA_CONV and x.is_cuda and x.dtype == torch.bfloat16:
-      from lsi.nnutils import _hip_conv  # pylint: disable=g-import-not-at-top
-      cout, cin = self.conv.weight.shape[:2]
-      head = self.bn is None and self.activation == 'sigmoid'
-      if (head or self.bn is not None) and _hip_conv.supported(
-          x, cin, cout, self.k, self.stride, head):
-        if head:    # bias + sigmoid inside the kernel, fp32 RGBD pixels out
-          return _hip_conv.conv3x3_c32_sigmoid(x, self.conv.weight, self.conv.bias)
-        x = _hip_conv.conv3x3_c32(x, self.conv.weight)
-        return self._bn_act(x)
-      if (IGEMM_CONV and self.bn is not None and
-          _hip_conv.igemm_supported(x, cin, cout, self.k, self.stride) and
-          _igemm_pays(x, self.stride)):
-        # every other batch-normed layer: the implicit-GEMM kernel (forward and
-        # data gradient; weight gradient on lsi_conv3x3_wgrad or the library)
-        ph = _same_pad(x.shape[2], self.k, self.stride)
-        pw = _same_pad(x.shape[3], self.k, self.stride)
-        st = _stats_bn(self.bn, self.activation, x.shape[0], cout)
-        x = _hip_conv.conv2d(x, self.conv.weight, self.stride, ph[0], pw[0],
-                             -(-x.shape[2] // self.stride), -(-x.shape[3] // self.stride), st)
-        if st:
-          return _bn_relu(self.bn, x, True)
-        return self._bn_act(x)
-      if (self.bn is not None and torch.is_grad_enabled() and
-          self.conv.weight.requires_grad and
-          _hip_conv.wgrad_supported(x, cin, cout, self.k, self.stride)):
-        # forward and data gradient on the library, weight gradient on the
-        # matrix-core kernel (K = pixels)
-        x = _hip_conv.conv3x3_lib_own_wgrad(x, self.conv.weight)
-        return self._bn_act(x)
-    if self.bn is not None and _f32_route(x):
-      from lsi.nnutils import _hip_conv  # pylint: disable=g-import-not-at-top
-      cout, cin = self.conv.weight.shape[:2]
-      if _hip_conv.f32_supported(x, cin, cout, self.k, self.stride):
-        ph = _same_pad(x.shape[2], self.k, self.stride)
-        pw = _same_pad(x.shape[3], self.k, self.stride)
-        x = _hip_conv.conv2d_f32(x, self.conv.weight, self.stride, ph[0], pw[0],
-                                 -(-x.shape[2] // self.stride), -(-x.shape[3] // self.stride))
-        return self._bn_act(x)
+    weight, s = self.conv.weight, self.stride
+    oh, ow, pad_t, pad_l = _hip_conv.same_geometry(x.shape[2], x.shape[3], self.k, s)
+    route, st = self._route(x, weight.shape[1], weight.shape[0], oh, ow)
+    if route == 'pred':     # bias + sigmoid inside the kernel, fp32 RGBD pixels out
+      return _hip_conv.conv3x3_c32_sigmoid(x, weight, self.conv.bias)
+    if route == 'first':
+      y = _hip_conv.conv2d_first(x, weight, s, pad_t, pad_l, oh, ow, st)
+    elif route == 'c32':
+      y = _hip_conv.conv3x3_c32(x, weight)
+    elif route == 'igemm':
+      y = _hip_conv.conv2d(x, weight, s, pad_t, pad_l, oh, ow, st)
+    elif route == 'lib_wgrad':
+      y = _hip_conv.conv3x3_lib_own_wgrad(x, weight)
+    elif route == 'f32':
+      y = _hip_conv.conv2d_f32(x, weight, s, pad_t, pad_l, oh, ow)
+    else:
+      y = self._library(x)
+    return self._bn_act(y, st)
+
+  def _library(self, x):
     ph = _same_pad(x.shape[2], self.k, self.stride)
     pw = _same_pad(x.shape[3], self.k, self.stride)
     # Symmetric SAME padding (the stride-1 layers) goes into the convolution:
@@ -300,58 +299,48 @@ class SlimConv2d(nn.Module):
     # activations and bf16 batch norm it no longer does.)  Asymmetric padding
     # (the stride-2 layers: TF pads one more pixel after) stays explicit.
     if IMPLICIT_PAD and ph[0] == ph[1] and pw[0] == pw[1]:
-      x = F.conv2d(x, self.conv.weight, self.conv.bias, self.stride,
-                   (ph[0], pw[0]))
-    else:
-      if ph[0] or ph[1] or pw[0] or pw[1]:
-        x = F.pad(x, (pw[0], pw[1], ph[0], ph[1]))
-      x = self.conv(x)
-    return self._bn_act(x)
+      return F.conv2d(x, self.conv.weight, self.conv.bias, self.stride, (ph[0], pw[0]))
+    if ph[0] or ph[1] or pw[0] or pw[1]:
+      x = F.pad(x, (pw[0], pw[1], ph[0], ph[1]))
+    return self.conv(x)
+
+  def _cat_route(self, x1, x2, cout, oh, ow):
+    """(the precision whose two-tensor kernels take the skip connection -- bf16
+    first, then exact fp32 -- or None, the batch-norm groups as in _route)."""
+    k, s = self.k, self.stride
+    if self.bn is None:
+      return None, 0
+    if (MFMA_CONV and IGEMM_CONV and x1.is_cuda and x1.dtype == torch.bfloat16 and
+        x2.dtype == torch.bfloat16 and _hip_conv.cat_supported(x1, x2, cout, k, s) and
+        _igemm_pays(x1.shape[0], oh, ow)):
+      return _hip_conv.BF16, _stats_bn(self.bn, self.activation, x1.shape[0], cout)
+    if (_f32_route(x1) and x2.dtype == torch.float32 and
+        _hip_conv.f32_cat_supported(x1, x2, cout, k, s)):
+      return _hip_conv.F32, 0
+    return None, 0
 
   def forward_cat(self, x1, x2):
     """forward(tf.concat([x1, x2], axis=3)) -- the skip connections -- with the
     convolution kernels reading the two tensors where they can."""
-    if (MFMA_CONV and IGEMM_CONV and self.bn is not None and x1.is_cuda and
-        x1.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16):
-      from lsi.nnutils import _hip_conv  # pylint: disable=g-import-not-at-top
-      cout = self.conv.weight.shape[0]
-      if (_hip_conv.cat_supported(x1, x2, cout, self.k, self.stride) and
-          _igemm_pays(x1, self.stride) and
-          _hip_conv._igemm_wgrad_bytes(_hip_conv._conv_desc(
-              x1.shape[0], x1.shape[2], x1.shape[3], x1.shape[1] + x2.shape[1],
-              -(-x1.shape[2] // self.stride), -(-x1.shape[3] // self.stride), cout,
-              self.k, self.k, self.stride, _same_pad(x1.shape[2], self.k, self.stride)[0],
-              _same_pad(x1.shape[3], self.k, self.stride)[0])) > 0):
-        ph = _same_pad(x1.shape[2], self.k, self.stride)
-        pw = _same_pad(x1.shape[3], self.k, self.stride)
-        st = _stats_bn(self.bn, self.activation, x1.shape[0], cout)
-        y = _hip_conv.conv2d_cat(x1, x2, self.conv.weight, self.stride, ph[0], pw[0],
-                                 -(-x1.shape[2] // self.stride),
-                                 -(-x1.shape[3] // self.stride), st)
-        if st:
-          return _bn_relu(self.bn, y, True)
-        return self._bn_act(y)
-    if self.bn is not None and _f32_route(x1) and x2.dtype == torch.float32:
-      from lsi.nnutils import _hip_conv  # pylint: disable=g-import-not-at-top
-      cout = self.conv.weight.shape[0]
-      ph = _same_pad(x1.shape[2], self.k, self.stride)
-      pw = _same_pad(x1.shape[3], self.k, self.stride)
-      oh, ow = -(-x1.shape[2] // self.stride), -(-x1.shape[3] // self.stride)
-      # (the two tensors where the weight gradient runs on the kernel too; the
-      # concatenation otherwise: its weight gradient goes to the library)
-      if (_hip_conv.f32_cat_supported(x1, x2, cout, self.k, self.stride) and
-          _hip_conv.f32_wgrad_bytes(_hip_conv._conv_desc(
-              x1.shape[0], x1.shape[2], x1.shape[3], x1.shape[1] + x2.shape[1], oh, ow,
-              cout, self.k, self.k, self.stride, ph[0], pw[0])) > 0):
-        y = _hip_conv.conv2d_cat_f32(x1, x2, self.conv.weight, self.stride, ph[0], pw[0],
-                                     oh, ow)
-        return self._bn_act(y)
+    weight, k, s = self.conv.weight, self.k, self.stride
+    n, c1, h, w = x1.shape
+    cout = weight.shape[0]
+    oh, ow, pad_t, pad_l = _hip_conv.same_geometry(h, w, k, s)
+    p, st = self._cat_route(x1, x2, cout, oh, ow)
+    # (the two tensors where the weight gradient runs on the kernel too; the
+    # concatenation otherwise: its weight gradient goes to the library)
+    if p is not None and _hip_conv.wgrad_bytes(p, _hip_conv._conv_desc(
+        n, h, w, c1 + x2.shape[1], oh, ow, cout, k, k, s, pad_t, pad_l)) > 0:
+      y = _hip_conv.conv2d_cat(x1, x2, weight, s, pad_t, pad_l, oh, ow, st, p)
+      return self._bn_act(y, st)
     return self.forward(torch.cat([x1, x2], dim=1))
 
-  def _bn_act(self, x):
-    """Batch norm (if any) and the activation behind the convolution."""
+  def _bn_act(self, x, prestat=0):
+    """Batch norm (if any) and the activation behind the convolution; prestat:
+    the groups whose batch-norm sums the convolution has left (_stats_bn: only
+    ever in front of batch norm + ReLU)."""
     if self.bn is not None and self.activation == 'relu':
-      return _bn_relu(self.bn, x)
+      return _bn_relu(self.bn, x, bool(prestat))
     if self.bn is not None:
       x = self.bn(x)
     if self.activation == 'relu':
@@ -383,21 +372,23 @@ class SlimConvTranspose2d(nn.Module):
                              1, False):
           return _bn_relu(self.bn, _hip_fc.conv_transpose_1x1(x, self.conv.weight))
         _hip_fc.CALLS['declined'] += 1
-    if MFMA_CONV and IGEMM_CONV and x.is_cuda and x.dtype == torch.bfloat16:
-      from lsi.nnutils import _hip_conv  # pylint: disable=g-import-not-at-top
-      cin, cout = self.conv.weight.shape[:2]
-      # four parity classes of 2 x 2 taps on the implicit-GEMM kernel
-      if (_hip_conv.convt_supported(x, cin, cout, 4, 2) and
-          x.shape[0] * x.shape[2] * x.shape[3] >= IGEMM_MIN_PIXELS):
-        st = _stats_bn(self.bn, 'relu', x.shape[0], cout)
-        y = _hip_conv.conv_transpose2d(x, self.conv.weight, 2, 1, st)
-        return _bn_relu(self.bn, y, bool(st))
-    if _f32_route(x):
-      from lsi.nnutils import _hip_conv  # pylint: disable=g-import-not-at-top
-      cin, cout = self.conv.weight.shape[:2]
-      if _hip_conv.f32_convt_supported(x, cin, cout, 4, 2):
-        return _bn_relu(self.bn, _hip_conv.conv_transpose2d_f32(x, self.conv.weight, 2, 1))
-    return _bn_relu(self.bn, self.conv(x))
+    weight = self.conv.weight
+    p, st = self._route(x, weight.shape[0], weight.shape[1])
+    if p is None:
+      return _bn_relu(self.bn, self.conv(x))
+    # four parity classes of 2 x 2 taps on the implicit-GEMM kernels
+    return _bn_relu(self.bn, _hip_conv.conv_transpose2d(x, weight, 2, 1, st, p), bool(st))
+
+  def _route(self, x, cin, cout):
+    """(the precision whose kernels take the layer -- bf16 first, then exact fp32
+    -- or None: the library, the batch-norm groups as in SlimConv2d._route)."""
+    if (MFMA_CONV and IGEMM_CONV and x.is_cuda and x.dtype == torch.bfloat16 and
+        _hip_conv.convt_supported(x, cin, cout, 4, 2) and
+        _igemm_pays(x.shape[0], x.shape[2], x.shape[3])):
+      return _hip_conv.BF16, _stats_bn(self.bn, 'relu', x.shape[0], cout)
+    if _f32_route(x) and _hip_conv.f32_convt_supported(x, cin, cout, 4, 2):
+      return _hip_conv.F32, 0
+    return None, 0
 
 
 class SlimFC(nn.Module):

@@ -98,25 +98,25 @@ def bench_fp32():
       d = _hip_conv._conv_desc(N, h, w, cin, oh, ow, cout, k, k, s, pt, pl)
       gy = torch.randn((N, cout, oh, ow), generator=g).to(dev).contiguous(
           memory_format=torch.channels_last)
-      own_f = lambda: _hip_conv._run_f32(d, 0, wt, dev, x, _hip_conv._empty_cl_f32(N, cout, oh, ow, dev))
+      own_f = lambda: _hip_conv._run(_hip_conv.F32, d, 0, wt, x, _hip_conv._empty_cl(N, cout, oh, ow, dev, torch.float32))
       lib_f = lambda: F.conv2d(xp, wt, None, s, pad)
-      own_d = lambda: _hip_conv._run_f32(d, 1, wt, dev, gy, torch.empty_like(x))
+      own_d = lambda: _hip_conv._run(_hip_conv.F32, d, 1, wt, gy, torch.empty_like(x))
       lib_b = lambda m: torch.ops.aten.convolution_backward(
           gy, xp, wt, None, [s, s], pad, [1, 1], False, [0, 0], 1, m)
-      own_w = (lambda: _hip_conv._f32_wgrad(d, x, gy, wt)) if _hip_conv.f32_wgrad_bytes(d) > 0 else None
+      own_w = (lambda: _hip_conv._wgrad(_hip_conv.F32, d, x, gy, wt)) if _hip_conv.f32_wgrad_bytes(d) > 0 else None
     else:
       wt = (torch.randn((cin, cout, 4, 4), generator=g) * 0.05).to(dev)
       flop = 2.0 * N * (2 * h) * (2 * w) * cin * cout * 4
       d = _hip_conv._conv_desc(N, 2 * h, 2 * w, cout, h, w, cin, 4, 4, 2, 1, 1)
       gy = torch.randn((N, cout, 2 * h, 2 * w), generator=g).to(dev).contiguous(
           memory_format=torch.channels_last)
-      own_f = lambda: _hip_conv._run_f32(d, 1, wt, dev, x,
-                                         _hip_conv._empty_cl_f32(N, cout, 2 * h, 2 * w, dev))
+      own_f = lambda: _hip_conv._run(_hip_conv.F32, d, 1, wt, x,
+                                     _hip_conv._empty_cl(N, cout, 2 * h, 2 * w, dev, torch.float32))
       lib_f = lambda: F.conv_transpose2d(x, wt, None, 2, 1)
-      own_d = lambda: _hip_conv._run_f32(d, 0, wt, dev, gy, torch.empty_like(x))
+      own_d = lambda: _hip_conv._run(_hip_conv.F32, d, 0, wt, gy, torch.empty_like(x))
       lib_b = lambda m: torch.ops.aten.convolution_backward(
           gy, x, wt, None, [2, 2], [1, 1], [1, 1], True, [0, 0], 1, m)
-      own_w = (lambda: _hip_conv._f32_wgrad(d, gy, x, wt)) if _hip_conv.f32_wgrad_bytes(d) > 0 else None
+      own_w = (lambda: _hip_conv._wgrad(_hip_conv.F32, d, gy, x, wt)) if _hip_conv.f32_wgrad_bytes(d) > 0 else None
     lib_d = lambda: lib_b([True, False, False])
     lib_w = lambda: lib_b([False, True, False])
     diff = float((own_f() - lib_f()).abs().max())
@@ -181,7 +181,7 @@ for name, kind, cin, cout, k, s, h, w in L:
     y = own_f()
     gy = torch.randn_like(y)
     d = _hip_conv._conv_desc(N, h, w, cin, oh, ow, cout, k, k, s, pt, pl)
-    own_d = lambda: _hip_conv._igemm('lsi_conv2d_bwd_data', d, gy, wt, torch.empty_like(x))
+    own_d = lambda: _hip_conv._run(_hip_conv.BF16, d, 1, wt, gy, torch.empty_like(x))
     xp = x if sym else F.pad(x, (pl, pr, pt, pb))
     lib_d = lambda: torch.ops.aten.convolution_backward(
         gy, xp, wb, None, [s, s], [pt, pl] if sym else [0, 0], [1, 1], False, [0, 0], 1,
@@ -189,8 +189,8 @@ for name, kind, cin, cout, k, s, h, w in L:
     ref = lib_f().float()
     if k == 3 and s == 1 and _hip_conv.wgrad_supported(x, cin, cout, 3, 1):
       own_w = lambda: _hip_conv._weight_grad(x, gy, wt)
-    elif _hip_conv._igemm_wgrad_bytes(d) > 0:
-      own_w = lambda: _hip_conv._igemm_wgrad(d, x, gy, wt)
+    elif _hip_conv.wgrad_bytes(_hip_conv.BF16, d) > 0:
+      own_w = lambda: _hip_conv._wgrad(_hip_conv.BF16, d, x, gy, wt)
     else:
       own_w = None
     lib_w = lambda: torch.ops.aten.convolution_backward(
@@ -207,11 +207,11 @@ for name, kind, cin, cout, k, s, h, w in L:
     y = own_f()
     gy = torch.randn_like(y)
     d = _hip_conv._conv_desc(N, 2 * h, 2 * w, cout, h, w, cin, 4, 4, 2, 1, 1)
-    own_d = lambda: _hip_conv._igemm('lsi_conv2d_fwd', d, gy, wt, torch.empty_like(x))
+    own_d = lambda: _hip_conv._run(_hip_conv.BF16, d, 0, wt, gy, torch.empty_like(x))
     lib_d = lambda: torch.ops.aten.convolution_backward(
         gy, x, wb, None, [2, 2], [1, 1], [1, 1], True, [0, 0], 1, [True, False, False])
     ref = lib_f().float()
-    own_w = (lambda: _hip_conv._igemm_wgrad(d, gy, x, wt)) if _hip_conv._igemm_wgrad_bytes(d) > 0 else None
+    own_w = (lambda: _hip_conv._wgrad(_hip_conv.BF16, d, gy, x, wt)) if _hip_conv.wgrad_bytes(_hip_conv.BF16, d) > 0 else None
     lib_w = lambda: torch.ops.aten.convolution_backward(
         gy, x, wb, None, [2, 2], [1, 1], [1, 1], True, [0, 0], 1, [False, True, False])
     if own_w is not None:

@@ -76,7 +76,7 @@ for it in range(n_cases):
   e1 = float((x.grad.float() - xr.grad).abs().max()) / sc
   assert e1 <= 2.0 ** -7 + 1e-6, (tag, 'data gradient', e1)
   worst[keys[1]] = max(worst[keys[1]], e1)
-  own = _hip_conv._igemm_wgrad_bytes(d) > 0
+  own = _hip_conv.wgrad_bytes(_hip_conv.BF16, d) > 0
   own_w += int(own)
   sw = float(wr.grad.abs().max()) + 1e-20
   e2 = float((wt.grad - wr.grad).abs().max()) / sw

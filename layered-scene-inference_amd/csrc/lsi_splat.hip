@@ -794,6 +794,18 @@ int pick_band_rows(const LsiSplatDesc* d) {
   return best;
 }
 
+// The kernels' argument from the descriptor and the inputs, everything else
+// zero / NULL with one 4-channel canvas: all that lsi_project_indices and the
+// backward pass; the forwards add their outputs and canvases.
+SplatArgs splat_args(const LsiSplatDesc* d, const float* tex, const float* disp,
+                     const float* mask, const float* M) {
+  SplatArgs a = {};
+  a.d = *d;
+  a.tex = tex; a.disp = disp; a.mask = mask; a.M = M;
+  a.nch = 4; a.ncanv = 1;
+  return a;
+}
+
 }  // namespace
 
 extern "C" {
@@ -855,17 +867,13 @@ int lsi_splat_fwd(const LsiSplatDesc* d, const float* tex, const float* disp,
   if ((d->flags & LSI_WANT_DISP) && !out_disp) return LSI_ENULL;
   if ((d->flags & LSI_HAS_MASK) && !mask) return LSI_ENULL;
   hipStream_t stream = (hipStream_t)stream_;
-  SplatArgs a;
-  a.d = *d;
-  a.tex = tex; a.disp = disp; a.mask = mask; a.M = M;
+  SplatArgs a = splat_args(d, tex, disp, mask, M);
   a.out_img = out_img; a.out_wts = out_wts; a.out_disp = out_disp;
   a.canvas = (float*)workspace;
   a.ws_bytes = workspace_bytes;
   a.nch = canvas_channels(d);
   a.ncanv = canvas_count(d);
   a.shared = (d->flags & LSI_COMPOSE) && !(d->flags & LSI_WANT_DISP);
-  a.band_rows = 0;
-  a.out_img_c = a.out_wts_c = nullptr;
 
   int path = d->path;
   // AUTO without a host copy of M: the any-pose tile path (callers that have
@@ -921,13 +929,7 @@ int lsi_project_indices(const LsiSplatDesc* d, const float* disp,
   if (rc != LSI_OK) return rc;
   if (!disp || !M || !idx4 || !upd4) return LSI_ENULL;
   if ((d->flags & LSI_HAS_MASK) && !mask) return LSI_ENULL;
-  SplatArgs a;
-  a.d = *d;
-  a.tex = nullptr; a.disp = disp; a.mask = mask; a.M = M;
-  a.out_img = a.out_wts = a.out_disp = a.canvas = nullptr;
-  a.ws_bytes = 0;
-  a.nch = 4; a.ncanv = 1; a.shared = 0; a.band_rows = 0;
-  a.out_img_c = a.out_wts_c = nullptr;
+  const SplatArgs a = splat_args(d, nullptr, disp, mask, M);
   const int npx = d->H * d->W;
   hipLaunchKernelGGL(project_indices_kernel,
                      dim3((npx + 255) / 256, d->B, d->L), dim3(256), 0,
@@ -974,6 +976,61 @@ int grad_m_args(const LsiSplatDesc* d, const float* g_M) {
   return g_M ? LSI_EINVAL : LSI_OK;
 }
 
+// A backward call whose entry has checked its arguments: what lsi_splat_bwd_m,
+// lsi_splat_bwd_disp and lsi_splat_bwd_both_m hand to bwd_run.
+struct BwdCall {
+  const LsiSplatDesc* d;
+  const float *tex, *disp, *mask, *M;
+  LsiBwdCanvas ci;         // the per-layer (or the only) outputs and their gradients
+  const LsiBwdCanvas* cc;  // lsi_splat_bwd_both: the composed ones (else NULL)
+  float *g_tex, *g_disp, *g_mask;
+  float* g_M;              // NULL without LSI_GRAD_M; its partials follow the canvas
+  void* canvas;            // the workspace: the gather's gradient canvas first
+  const float2* GD;        // lsi_splat_bwd_disp: the (gS, gW) canvases (else NULL)
+};
+
+// The streamed gather where it applies (rectified pairs rendered by STREAM:
+// 16-byte loads and stores, the band's gradient-canvas rows built in LDS, no
+// pre-pass); else the pre-pass that writes the gradient canvas and the gather
+// kernel.  Either way dL/dM is folded from the workgroups' partials.
+int bwd_run(const BwdCall& c, hipStream_t stream) {
+  const LsiSplatDesc* d = c.d;
+  float* const gm_part =
+      c.g_M ? (float*)((char*)c.canvas + grad_m_part_offset(d)) : nullptr;
+  // lsi_splat_bwd_disp: streamed where lsi_splat_bwd_m would take that path for
+  // the same descriptor without the disparity output
+  LsiSplatDesc ds;
+  if (c.GD) { ds = *d; ds.flags &= ~LSI_WANT_DISP; }
+  if (lsi_bwd_stream_applies(c.GD ? &ds : d, c.tex, c.disp, c.mask, c.g_tex,
+                             c.g_disp, c.g_mask)) {
+    int nper = 0;
+    const int rc = lsi_bwd_stream_launch(d, c.tex, c.disp, c.mask, c.M, &c.ci, c.cc,
+                                         c.g_tex, c.g_disp, c.g_mask, gm_part,
+                                         &nper, stream, c.GD);
+    if (rc != LSI_OK || !c.g_M) return rc;
+    return grad_m_fold(d, gm_part, nper, c.g_M, stream);
+  }
+  if ((long)d->B * d->L > 65535 || d->H > 65535) return LSI_EINVAL;  // grid.y / z
+  const size_t n1 = (size_t)d->B * d->Ht * d->Wt;
+  if (c.cc) {
+    hipLaunchKernelGGL(splat_bwd_pre_both_kernel, dim3((unsigned)((n1 + 255) / 256)),
+                       dim3(256), 0, stream, n1, d->L, c.ci.img, c.ci.wts, c.cc->img,
+                       c.cc->wts, c.ci.g_img, c.ci.g_wts, c.cc->g_img, c.cc->g_wts,
+                       (float4*)c.canvas);
+  } else {
+    const size_t n = ((d->flags & LSI_COMPOSE) ? 1 : (size_t)d->L) * n1;
+    hipLaunchKernelGGL(splat_bwd_pre_kernel, dim3((unsigned)((n + 255) / 256)),
+                       dim3(256), 0, stream, n, c.ci.img, c.ci.wts, c.ci.g_img,
+                       c.ci.g_wts, (float4*)c.canvas);
+  }
+  launch_bwd(splat_args(d, c.tex, c.disp, c.mask, c.M), (const float4*)c.canvas,
+             c.g_tex, c.g_disp, (d->flags & LSI_HAS_MASK) ? c.g_mask : nullptr,
+             gm_part, stream, c.GD);
+  if (c.g_M)
+    return grad_m_fold(d, gm_part, (int)(grad_m_gather_parts(d) / d->B), c.g_M, stream);
+  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1010,39 +1067,12 @@ int lsi_splat_bwd_m(const LsiSplatDesc* d, const float* tex, const float* disp,
     return LSI_ENULL;
   rc = grad_m_args(d, g_M);
   if (rc != LSI_OK) return rc;
-  float* const gm_part =
-      g_M ? (float*)((char*)workspace + grad_m_part_offset(d)) : nullptr;
   if ((d->flags & LSI_HAS_MASK) && !mask) return LSI_ENULL;
   if (!packed_ok(d, tex, disp)) return LSI_EINVAL;
   if (workspace_bytes < lsi_splat_bwd_workspace_bytes(d)) return LSI_EWORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  // rectified pairs rendered by STREAM: the streamed gather (16-byte loads and
-  // stores, the band's gradient-canvas rows built in LDS; no pre-pass)
-  if (lsi_bwd_stream_applies(d, tex, disp, mask, g_tex, g_disp_in, g_mask)) {
-    const LsiBwdCanvas ci = {out_img, out_wts, g_img, g_wts};
-    int nper = 0;
-    rc = lsi_bwd_stream_launch(d, tex, disp, mask, M, &ci, nullptr, g_tex,
-                               g_disp_in, g_mask, gm_part, &nper, stream);
-    if (rc != LSI_OK || !g_M) return rc;
-    return grad_m_fold(d, gm_part, nper, g_M, stream);
-  }
-  const int nl = (d->flags & LSI_COMPOSE) ? 1 : d->L;
-  const size_t n = (size_t)nl * d->B * d->Ht * d->Wt;
-  hipLaunchKernelGGL(splat_bwd_pre_kernel, dim3((unsigned)((n + 255) / 256)),
-                     dim3(256), 0, stream, n, out_img, out_wts, g_img, g_wts,
-                     (float4*)workspace);
-  SplatArgs a;
-  a.d = *d;
-  a.tex = tex; a.disp = disp; a.mask = mask; a.M = M;
-  a.out_img = a.out_wts = a.out_disp = a.canvas = nullptr;
-  a.ws_bytes = 0;
-  a.nch = 4; a.ncanv = 1; a.shared = 0; a.band_rows = 0;
-  a.out_img_c = a.out_wts_c = nullptr;
-  if ((long)d->B * d->L > 65535 || d->H > 65535) return LSI_EINVAL;  // grid.y / z
-  launch_bwd(a, (const float4*)workspace, g_tex, g_disp_in,
-             (d->flags & LSI_HAS_MASK) ? g_mask : nullptr, gm_part, stream);
-  if (g_M) return grad_m_fold(d, gm_part, (int)(grad_m_gather_parts(d) / d->B), g_M, stream);
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+  const BwdCall c = {d, tex, disp, mask, M, {out_img, out_wts, g_img, g_wts}, nullptr,
+                     g_tex, g_disp_in, g_mask, g_M, workspace, nullptr};
+  return bwd_run(c, (hipStream_t)stream_);
 }
 
 }  // extern "C"
@@ -1117,7 +1147,6 @@ int lsi_splat_bwd_disp(const LsiSplatDesc* d, const float* tex, const float* dis
   if (workspace_bytes < ws.total) return LSI_EWORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   char* const base = (char*)workspace;
-  float* const gm_part = g_M ? (float*)(base + grad_m_part_offset(d)) : nullptr;
   float2* const GD = (float2*)(base + ws.gd);
   const bool compose = (d->flags & LSI_COMPOSE) != 0;
   // per-layer W_l and disp_l: the forward's outputs, or (composed) rendered
@@ -1139,33 +1168,9 @@ int lsi_splat_bwd_disp(const LsiSplatDesc* d, const float* tex, const float* dis
                      dim3(256), 0, stream, n, d->L, compose ? 1 : 0, g_disp_out,
                      Wl, Dl, GD);
   if (hipGetLastError() != hipSuccess) return LSI_ELAUNCH;
-  // the streamed kernel where lsi_splat_bwd_m would take it for the same
-  // descriptor without the disparity output
-  LsiSplatDesc ds = *d;
-  ds.flags &= ~LSI_WANT_DISP;
-  if (lsi_bwd_stream_applies(&ds, tex, disp, mask, g_tex, g_disp_in, g_mask)) {
-    const LsiBwdCanvas ci = {out_img, out_wts, g_img, g_wts};
-    int nper = 0;
-    rc = lsi_bwd_stream_launch(d, tex, disp, mask, M, &ci, nullptr, g_tex,
-                               g_disp_in, g_mask, gm_part, &nper, stream, GD);
-    if (rc != LSI_OK || !g_M) return rc;
-    return grad_m_fold(d, gm_part, nper, g_M, stream);
-  }
-  if ((long)d->B * d->L > 65535 || d->H > 65535) return LSI_EINVAL;  // grid.y / z
-  hipLaunchKernelGGL(splat_bwd_pre_kernel, dim3((unsigned)((n + 255) / 256)),
-                     dim3(256), 0, stream, n, out_img, out_wts, g_img, g_wts,
-                     (float4*)workspace);
-  SplatArgs a;
-  a.d = *d;
-  a.tex = tex; a.disp = disp; a.mask = mask; a.M = M;
-  a.out_img = a.out_wts = a.out_disp = a.canvas = nullptr;
-  a.ws_bytes = 0;
-  a.nch = 4; a.ncanv = 1; a.shared = 0; a.band_rows = 0;
-  a.out_img_c = a.out_wts_c = nullptr;
-  launch_bwd(a, (const float4*)workspace, g_tex, g_disp_in,
-             (d->flags & LSI_HAS_MASK) ? g_mask : nullptr, gm_part, stream, GD);
-  if (g_M) return grad_m_fold(d, gm_part, (int)(grad_m_gather_parts(d) / d->B), g_M, stream);
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+  const BwdCall c = {d, tex, disp, mask, M, {out_img, out_wts, g_img, g_wts}, nullptr,
+                     g_tex, g_disp_in, g_mask, g_M, workspace, GD};
+  return bwd_run(c, stream);
 }
 
 int lsi_splat_fwd_both(const LsiSplatDesc* d, const float* tex,
@@ -1183,12 +1188,10 @@ int lsi_splat_fwd_both(const LsiSplatDesc* d, const float* tex,
     // one sweep: every layer's tile is written out and added to a second tile
     if (!tex || !disp || !M) return LSI_ENULL;
     if ((d->flags & LSI_HAS_MASK) && !mask) return LSI_ENULL;
-    SplatArgs a;
-    a.d = *d;
-    a.tex = tex; a.disp = disp; a.mask = mask; a.M = M;
-    a.out_img = out_img; a.out_wts = out_wts; a.out_disp = nullptr;
+    SplatArgs a = splat_args(d, tex, disp, mask, M);
+    a.out_img = out_img; a.out_wts = out_wts;
     a.canvas = (float*)workspace; a.ws_bytes = workspace_bytes;
-    a.nch = 4; a.ncanv = d->L; a.shared = 0; a.band_rows = 0;
+    a.ncanv = d->L;
     a.out_img_c = out_img_c; a.out_wts_c = out_wts_c;
     return lsi_stream_launch(a, stream);
   }
@@ -1233,40 +1236,15 @@ int lsi_splat_bwd_both_m(const LsiSplatDesc* d, const float* tex,
   if (!tex || !disp || !M || !g_tex || !g_disp_in || !workspace) return LSI_ENULL;
   rc = grad_m_args(d, g_M);
   if (rc != LSI_OK) return rc;
-  float* const gm_part =
-      g_M ? (float*)((char*)workspace + grad_m_part_offset(d)) : nullptr;
   if (!packed_ok(d, tex, disp)) return LSI_EINVAL;
   if (g_img && (!out_img || !out_wts)) return LSI_ENULL;
   if (g_img_c && (!out_img_c || !out_wts_c)) return LSI_ENULL;
   if ((d->flags & LSI_HAS_MASK) && !mask) return LSI_ENULL;
   if (workspace_bytes < lsi_splat_bwd_workspace_bytes(d)) return LSI_EWORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (lsi_bwd_stream_applies(d, tex, disp, mask, g_tex, g_disp_in, g_mask)) {
-    const LsiBwdCanvas ci = {out_img, out_wts, g_img, g_wts};
-    const LsiBwdCanvas cc = {out_img_c, out_wts_c, g_img_c, g_wts_c};
-    int nper = 0;
-    rc = lsi_bwd_stream_launch(d, tex, disp, mask, M, &ci, &cc, g_tex, g_disp_in,
-                               g_mask, gm_part, &nper, stream);
-    if (rc != LSI_OK || !g_M) return rc;
-    return grad_m_fold(d, gm_part, nper, g_M, stream);
-  }
-  const size_t n1 = (size_t)d->B * d->Ht * d->Wt;
-  hipLaunchKernelGGL(splat_bwd_pre_both_kernel,
-                     dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, stream,
-                     n1, d->L, out_img, out_wts, out_img_c, out_wts_c, g_img,
-                     g_wts, g_img_c, g_wts_c, (float4*)workspace);
-  SplatArgs a;
-  a.d = *d;
-  a.tex = tex; a.disp = disp; a.mask = mask; a.M = M;
-  a.out_img = a.out_wts = a.out_disp = a.canvas = nullptr;
-  a.ws_bytes = 0;
-  a.nch = 4; a.ncanv = 1; a.shared = 0; a.band_rows = 0;
-  a.out_img_c = a.out_wts_c = nullptr;
-  if ((long)d->B * d->L > 65535 || d->H > 65535) return LSI_EINVAL;  // grid.y / z
-  launch_bwd(a, (const float4*)workspace, g_tex, g_disp_in,
-             (d->flags & LSI_HAS_MASK) ? g_mask : nullptr, gm_part, stream);
-  if (g_M) return grad_m_fold(d, gm_part, (int)(grad_m_gather_parts(d) / d->B), g_M, stream);
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+  const LsiBwdCanvas cc = {out_img_c, out_wts_c, g_img_c, g_wts_c};
+  const BwdCall c = {d, tex, disp, mask, M, {out_img, out_wts, g_img, g_wts}, &cc,
+                     g_tex, g_disp_in, g_mask, g_M, workspace, nullptr};
+  return bwd_run(c, (hipStream_t)stream_);
 }
 
 }  // extern "C"

@@ -570,29 +570,16 @@ int lsi_bwd_stream_launch(const LsiSplatDesc* d, const float* tex,
   a.GR = rows_for(rs);
   size_t lds = bytes_for(rs);
   if (lds > cap) { a.GR = 0; lds = 0; }
-  const void* fn;
-  if (gd) {
-    if (gm_part)
-      fn = (d->flags & LSI_PACKED_RGBD)
-               ? (const void*)splat_bwd_stream_kernel<true, false, true, true>
-               : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, true, true>
-                           : (const void*)splat_bwd_stream_kernel<false, false, true, true>);
-    else
-      fn = (d->flags & LSI_PACKED_RGBD)
-               ? (const void*)splat_bwd_stream_kernel<true, false, false, true>
-               : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, false, true>
-                           : (const void*)splat_bwd_stream_kernel<false, false, false, true>);
-  } else if (gm_part) {
-    fn = (d->flags & LSI_PACKED_RGBD)
-             ? (const void*)splat_bwd_stream_kernel<true, false, true, false>
-             : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, true, false>
-                         : (const void*)splat_bwd_stream_kernel<false, false, true, false>);
-  } else {
-    fn = (d->flags & LSI_PACKED_RGBD)
-             ? (const void*)splat_bwd_stream_kernel<true, false, false, false>
-             : (has_mask ? (const void*)splat_bwd_stream_kernel<false, true, false, false>
-                         : (const void*)splat_bwd_stream_kernel<false, false, false, false>);
-  }
+  // <PACK, MASK, GRAD_M, WANT_DISP> (RGBD pixels come without a mask: packed_ok)
+  const bool pack = (d->flags & LSI_PACKED_RGBD) != 0;
+#define BS_FN(P_, M_, G_, D_) ((const void*)splat_bwd_stream_kernel<P_, M_, G_, D_>)
+#define BS_PICK(G_, D_)                                                        \
+  (pack ? BS_FN(true, false, G_, D_)                                            \
+        : (has_mask ? BS_FN(false, true, G_, D_) : BS_FN(false, false, G_, D_)))
+  const void* fn = gd ? (gm_part ? BS_PICK(true, true) : BS_PICK(false, true))
+                      : (gm_part ? BS_PICK(true, false) : BS_PICK(false, false));
+#undef BS_PICK
+#undef BS_FN
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)(lds > 0 ? lds : 16)) != hipSuccess) {
     // a device that does not grant the LDS asked for: corners from the arrays

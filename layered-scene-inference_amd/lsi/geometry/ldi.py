@@ -9,6 +9,7 @@ An LDI is {textures, masks, disps}:
 output) -- the kernels take element strides, nothing is copied.
 """
 import collections
+import contextlib
 import ctypes
 import threading
 import weakref
@@ -140,6 +141,14 @@ def _device_matrices(src2trg_mat, mat_host, dev):
   return mat
 
 
+def _matrices(src2trg_mat, mat_host, path, dev):
+  """(the matrices on `dev`, their host copy): the copy is fetched here when
+  the caller gave none and the kernel choice will look at it."""
+  if mat_host is None and path not in ('atomic', 'tile'):
+    mat_host = src2trg_mat.detach().to('cpu', torch.float32)
+  return _device_matrices(src2trg_mat, mat_host, dev), mat_host
+
+
 def _stream_workspace(desc, dev):
   """Zero-filled once, then kept by the library (lsi_hip.h, LSI_WS_KEEP): one
   buffer per (device, stream, call geometry); calls on a stream are ordered.
@@ -205,23 +214,66 @@ def stream_adapt(desc, dev):
   return ad
 
 
-class _NoLock(object):
-  def __enter__(self):
-    return self
-
-  def __exit__(self, *exc):
-    return False
+_NO_LOCK = contextlib.nullcontext()   # (a call without an adaptive record)
 
 
-_NOLOCK = _NoLock()
+def _open_forward(tex, mask, disp, mat_host, cfg, flags):
+  """The common opening of the two autograd forwards: the checks, then the
+  descriptor of the call (`flags` plus what the mask and cfg add) with its
+  kernel family chosen.  Returns (descriptor, Ht, Wt)."""
+  h, w, c = tex.shape[2:]
+  if c != 3:
+    raise ValueError('forward_splat renders 3-channel textures (got %d)' % c)
+  s = cfg['trg_downsampling']
+  ht, wt = h * s, w * s
+  if ht != int(ht) or wt != int(wt):
+    raise ValueError('H*trg_downsampling and W*trg_downsampling must be '
+                     'integral (reference ldi.py:113-125)')
+  if mask is not None:
+    flags |= _C.LSI_HAS_MASK
+  if cfg.get('deterministic'):
+    flags |= _C.LSI_DETERMINISTIC
+  bg_wt = _C.bg_weight(cfg['bg_layer_disp'], cfg['max_disp'],
+                       cfg['zbuf_scale'])
+  desc = _desc(tex, mask, disp, int(ht), int(wt), float(s), float(cfg['max_disp']),
+               float(cfg['zbuf_scale']), bg_wt, flags, 0,
+               cfg.get('band_rows', 0), cfg.get('threads', 0))
+  desc.reserved = int(cfg.get('experiment', 0))
+  select_path(desc, mat_host, cfg.get('path', 'auto'))
+  return desc, int(ht), int(wt)
 
 
-def _grad_m_desc(desc):
-  """A copy of the forward's descriptor that asks the backward for dL/dM too
-  (LSI_GRAD_M: lsi_splat_bwd_m / lsi_splat_bwd_both_m)."""
-  d = _C.LsiSplatDesc.from_buffer_copy(desc)
-  d.flags |= _C.LSI_GRAD_M
-  return d
+def _open_backward(ctx, tex, mask):
+  """The gradient tensors of a backward, written whole by its kernels: g_tex,
+  g_disp, g_mask (None without a mask) and, when the matrices need their
+  gradient, g_m with a copy of the forward's descriptor that asks for it
+  (LSI_GRAD_M: the _m entries).  Returns (descriptor, g_tex, g_disp, g_mask, g_m)."""
+  nl, b, h, w, _ = tex.shape
+  dev = tex.device
+  g_tex = torch.empty((nl, b, h, w, 3), dtype=torch.float32, device=dev)
+  g_disp = torch.empty((nl, b, h, w, 1), dtype=torch.float32, device=dev)
+  g_mask = (torch.empty((nl, b, h, w, 1), dtype=torch.float32, device=dev)
+            if mask is not None else None)
+  desc, g_m = ctx.desc, None
+  if ctx.needs_input_grad[3]:
+    desc = _C.LsiSplatDesc.from_buffer_copy(desc)
+    desc.flags |= _C.LSI_GRAD_M
+    g_m = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
+  return desc, g_tex, g_disp, g_mask, g_m
+
+
+def _call_backward(name, desc, dev, *tensors):
+  """lib.<name>(desc, the tensors' addresses..., workspace, its bytes, stream)
+  with a workspace of the entry's *_workspace_bytes; raises unless LSI_OK."""
+  lib = _C.lib()
+  if name == 'lsi_splat_bwd_disp':
+    ws_bytes = int(lib.lsi_splat_bwd_disp_workspace_bytes(ctypes.byref(desc)))
+  else:
+    ws_bytes = int(lib.lsi_splat_bwd_workspace_bytes(ctypes.byref(desc)))
+  ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+  rc = getattr(lib, name)(ctypes.byref(desc), *[_C.ptr(t) for t in tensors],
+                          ws.data_ptr(), ws_bytes, _C.stream_ptr(dev))
+  _C.check(rc, name)
 
 
 class _ForwardSplat(torch.autograd.Function):
@@ -232,32 +284,12 @@ class _ForwardSplat(torch.autograd.Function):
   @staticmethod
   def forward(ctx, tex, mask, disp, mat, mat_host, cfg):
     dev = _C.require_device(tex, mask, disp, mat)
-    nl, b, h, w, c = tex.shape
-    if c != 3:
-      raise ValueError('forward_splat renders 3-channel textures (got %d)' % c)
-    s = cfg['trg_downsampling']
-    ht, wt = h * s, w * s
-    if ht != int(ht) or wt != int(wt):
-      raise ValueError('H*trg_downsampling and W*trg_downsampling must be '
-                       'integral (reference ldi.py:113-125)')
-    ht, wt = int(ht), int(wt)
-    flags = 0
-    if cfg['compose_layers']:
-      flags |= _C.LSI_COMPOSE
-    if cfg['compute_trg_disp']:
-      flags |= _C.LSI_WANT_DISP
-    if mask is not None:
-      flags |= _C.LSI_HAS_MASK
-    if cfg.get('deterministic'):
-      flags |= _C.LSI_DETERMINISTIC
-    bg_wt = _C.bg_weight(cfg['bg_layer_disp'], cfg['max_disp'],
-                         cfg['zbuf_scale'])
-    desc = _desc(tex, mask, disp, ht, wt, float(s), float(cfg['max_disp']),
-                 float(cfg['zbuf_scale']), bg_wt, flags, 0,
-                 cfg.get('band_rows', 0), cfg.get('threads', 0))
-    desc.reserved = int(cfg.get('experiment', 0))
-    select_path(desc, mat_host, cfg.get('path', 'auto'))
-    nlo = 1 if cfg['compose_layers'] else nl
+    desc, ht, wt = _open_forward(
+        tex, mask, disp, mat_host, cfg,
+        (_C.LSI_COMPOSE if cfg['compose_layers'] else 0) |
+        (_C.LSI_WANT_DISP if cfg['compute_trg_disp'] else 0))
+    b = tex.shape[1]
+    nlo = 1 if cfg['compose_layers'] else tex.shape[0]
     img = torch.empty((nlo, b, ht, wt, 3), dtype=torch.float32, device=dev)
     wts = torch.empty((nlo, b, ht, wt, 1), dtype=torch.float32, device=dev)
     dsp = (torch.empty((nlo, b, ht, wt, 1), dtype=torch.float32, device=dev)
@@ -273,7 +305,7 @@ class _ForwardSplat(torch.autograd.Function):
     mat = mat.contiguous()
     ad = stream_adapt(desc, dev) if cfg.get('adapt', True) else None
     desc.adapt = ctypes.addressof(ad.rec) if ad is not None else None
-    with (ad.lock if ad is not None else _NOLOCK):
+    with (ad.lock if ad is not None else _NO_LOCK):
       rc = lib.lsi_splat_fwd(ctypes.byref(desc), _C.ptr(tex), _C.ptr(disp),
                              _C.ptr(mask), _C.ptr(mat), _C.ptr(img), _C.ptr(wts),
                              _C.ptr(dsp), _C.ptr(ws), ws_bytes,
@@ -295,55 +327,23 @@ class _ForwardSplat(torch.autograd.Function):
   def backward(ctx, g_img, g_wts, g_dsp):
     tex, mask, disp, mat, img, wts, dsp = ctx.saved_tensors
     mask = mask if ctx.has_mask else None
-    desc = ctx.desc
     dev = tex.device
-    nl, b, h, w, _ = tex.shape
     # (None: what autograd materialised as zeros before -- the same pointers'
     # contents, so the same bits)
     g_img = g_img.contiguous() if g_img is not None else torch.zeros_like(img)
     g_wts = g_wts.contiguous() if g_wts is not None else torch.zeros_like(wts)
-    g_tex = torch.empty((nl, b, h, w, 3), dtype=torch.float32, device=dev)
-    g_disp = torch.empty((nl, b, h, w, 1), dtype=torch.float32, device=dev)
-    g_mask = (torch.empty((nl, b, h, w, 1), dtype=torch.float32, device=dev)
-              if mask is not None else None)
-    lib = _C.lib()
+    desc, g_tex, g_disp, g_mask, g_m = _open_backward(ctx, tex, mask)
     if g_dsp is not None and dsp.numel():
-      g_dsp = g_dsp.contiguous()
-      g_m = None
-      if ctx.needs_input_grad[3]:
-        desc = _grad_m_desc(desc)
-        g_m = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
-      ws_bytes = int(lib.lsi_splat_bwd_disp_workspace_bytes(ctypes.byref(desc)))
-      ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-      rc = lib.lsi_splat_bwd_disp(ctypes.byref(desc), _C.ptr(tex), _C.ptr(disp),
-                                  _C.ptr(mask), _C.ptr(mat), _C.ptr(img),
-                                  _C.ptr(wts), _C.ptr(dsp), _C.ptr(g_img),
-                                  _C.ptr(g_wts), _C.ptr(g_dsp), _C.ptr(g_tex),
-                                  _C.ptr(g_disp), _C.ptr(g_mask), _C.ptr(g_m),
-                                  _C.ptr(ws), ws_bytes, _C.stream_ptr(dev))
-      _C.check(rc, 'lsi_splat_bwd_disp')
-      return g_tex, g_mask, g_disp, g_m, None, None
-    if ctx.needs_input_grad[3]:
-      desc = _grad_m_desc(desc)
-      g_m = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
-      ws_bytes = int(lib.lsi_splat_bwd_workspace_bytes(ctypes.byref(desc)))
-      ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-      rc = lib.lsi_splat_bwd_m(ctypes.byref(desc), _C.ptr(tex), _C.ptr(disp),
-                               _C.ptr(mask), _C.ptr(mat), _C.ptr(img), _C.ptr(wts),
-                               _C.ptr(g_img), _C.ptr(g_wts), _C.ptr(g_tex),
-                               _C.ptr(g_disp), _C.ptr(g_mask), _C.ptr(g_m),
-                               _C.ptr(ws), ws_bytes, _C.stream_ptr(dev))
-      _C.check(rc, 'lsi_splat_bwd_m')
-      return g_tex, g_mask, g_disp, g_m, None, None
-    ws_bytes = int(lib.lsi_splat_bwd_workspace_bytes(ctypes.byref(desc)))
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    rc = lib.lsi_splat_bwd(ctypes.byref(desc), _C.ptr(tex), _C.ptr(disp),
-                           _C.ptr(mask), _C.ptr(mat), _C.ptr(img), _C.ptr(wts),
-                           _C.ptr(g_img), _C.ptr(g_wts), _C.ptr(g_tex),
-                           _C.ptr(g_disp), _C.ptr(g_mask), _C.ptr(ws), ws_bytes,
-                           _C.stream_ptr(dev))
-    _C.check(rc, 'lsi_splat_bwd')
-    return g_tex, g_mask, g_disp, None, None, None
+      _call_backward('lsi_splat_bwd_disp', desc, dev, tex, disp, mask, mat, img,
+                     wts, dsp, g_img, g_wts, g_dsp.contiguous(), g_tex, g_disp,
+                     g_mask, g_m)
+    elif g_m is not None:
+      _call_backward('lsi_splat_bwd_m', desc, dev, tex, disp, mask, mat, img, wts,
+                     g_img, g_wts, g_tex, g_disp, g_mask, g_m)
+    else:
+      _call_backward('lsi_splat_bwd', desc, dev, tex, disp, mask, mat, img, wts,
+                     g_img, g_wts, g_tex, g_disp, g_mask)
+    return g_tex, g_mask, g_disp, g_m, None, None
 
 
 class _ForwardSplatBoth(torch.autograd.Function):
@@ -354,25 +354,8 @@ class _ForwardSplatBoth(torch.autograd.Function):
   @staticmethod
   def forward(ctx, tex, mask, disp, mat, mat_host, cfg):
     dev = _C.require_device(tex, mask, disp, mat)
-    nl, b, h, w, c = tex.shape
-    if c != 3:
-      raise ValueError('forward_splat renders 3-channel textures (got %d)' % c)
-    s = cfg['trg_downsampling']
-    ht, wt = h * s, w * s
-    if ht != int(ht) or wt != int(wt):
-      raise ValueError('H*trg_downsampling and W*trg_downsampling must be '
-                       'integral (reference ldi.py:113-125)')
-    ht, wt = int(ht), int(wt)
-    flags = _C.LSI_HAS_MASK if mask is not None else 0
-    if cfg.get('deterministic'):
-      flags |= _C.LSI_DETERMINISTIC
-    bg_wt = _C.bg_weight(cfg['bg_layer_disp'], cfg['max_disp'],
-                         cfg['zbuf_scale'])
-    desc = _desc(tex, mask, disp, ht, wt, float(s), float(cfg['max_disp']),
-                 float(cfg['zbuf_scale']), bg_wt, flags, 0,
-                 cfg.get('band_rows', 0), cfg.get('threads', 0))
-    desc.reserved = int(cfg.get('experiment', 0))
-    select_path(desc, mat_host, cfg.get('path', 'auto'))
+    desc, ht, wt = _open_forward(tex, mask, disp, mat_host, cfg, 0)
+    nl, b = tex.shape[:2]
     img = torch.empty((nl, b, ht, wt, 3), dtype=torch.float32, device=dev)
     wts = torch.empty((nl, b, ht, wt, 1), dtype=torch.float32, device=dev)
     img_c = torch.empty((1, b, ht, wt, 3), dtype=torch.float32, device=dev)
@@ -402,9 +385,6 @@ class _ForwardSplatBoth(torch.autograd.Function):
   def backward(ctx, g_img, g_wts, g_img_c, g_wts_c):
     tex, mask, disp, mat, img, wts, img_c, wts_c = ctx.saved_tensors
     mask = mask if ctx.has_mask else None
-    desc = ctx.desc
-    dev = tex.device
-    nl, b, h, w, _ = tex.shape
 
     def c(t):
       return None if t is None else t.contiguous()
@@ -414,34 +394,16 @@ class _ForwardSplatBoth(torch.autograd.Function):
       g_img = torch.zeros_like(img)
     if g_img_c is None and g_wts_c is not None:
       g_img_c = torch.zeros_like(img_c)
-    g_tex = torch.empty((nl, b, h, w, 3), dtype=torch.float32, device=dev)
-    g_disp = torch.empty((nl, b, h, w, 1), dtype=torch.float32, device=dev)
-    g_mask = (torch.empty((nl, b, h, w, 1), dtype=torch.float32, device=dev)
-              if mask is not None else None)
-    lib = _C.lib()
-    if ctx.needs_input_grad[3]:
-      desc = _grad_m_desc(desc)
-      g_m = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
-      ws_bytes = int(lib.lsi_splat_bwd_workspace_bytes(ctypes.byref(desc)))
-      ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-      rc = lib.lsi_splat_bwd_both_m(
-          ctypes.byref(desc), _C.ptr(tex), _C.ptr(disp), _C.ptr(mask),
-          _C.ptr(mat), _C.ptr(img), _C.ptr(wts), _C.ptr(img_c), _C.ptr(wts_c),
-          _C.ptr(g_img), _C.ptr(g_wts), _C.ptr(g_img_c), _C.ptr(g_wts_c),
-          _C.ptr(g_tex), _C.ptr(g_disp), _C.ptr(g_mask), _C.ptr(g_m), _C.ptr(ws),
-          ws_bytes, _C.stream_ptr(dev))
-      _C.check(rc, 'lsi_splat_bwd_both_m')
-      return g_tex, g_mask, g_disp, g_m, None, None
-    ws_bytes = int(lib.lsi_splat_bwd_workspace_bytes(ctypes.byref(desc)))
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    rc = lib.lsi_splat_bwd_both(
-        ctypes.byref(desc), _C.ptr(tex), _C.ptr(disp), _C.ptr(mask),
-        _C.ptr(mat), _C.ptr(img), _C.ptr(wts), _C.ptr(img_c), _C.ptr(wts_c),
-        _C.ptr(g_img), _C.ptr(g_wts), _C.ptr(g_img_c), _C.ptr(g_wts_c),
-        _C.ptr(g_tex), _C.ptr(g_disp), _C.ptr(g_mask), _C.ptr(ws), ws_bytes,
-        _C.stream_ptr(dev))
-    _C.check(rc, 'lsi_splat_bwd_both')
-    return g_tex, g_mask, g_disp, None, None, None
+    desc, g_tex, g_disp, g_mask, g_m = _open_backward(ctx, tex, mask)
+    if g_m is not None:
+      _call_backward('lsi_splat_bwd_both_m', desc, tex.device, tex, disp, mask, mat,
+                     img, wts, img_c, wts_c, g_img, g_wts, g_img_c, g_wts_c, g_tex,
+                     g_disp, g_mask, g_m)
+    else:
+      _call_backward('lsi_splat_bwd_both', desc, tex.device, tex, disp, mask, mat,
+                     img, wts, img_c, wts_c, g_img, g_wts, g_img_c, g_wts_c, g_tex,
+                     g_disp, g_mask)
+    return g_tex, g_mask, g_disp, g_m, None, None
 
 
 def forward_splat_both(ldi_src, src2trg_mat, trg_downsampling=1,
@@ -457,9 +419,7 @@ def forward_splat_both(ldi_src, src2trg_mat, trg_downsampling=1,
   A `src2trg_mat` that requires grad gets its gradient (lsi_splat_bwd_both_m).
   """
   tex, mask, disp = ldi_src
-  if mat_host is None and path not in ('atomic', 'tile'):
-    mat_host = src2trg_mat.detach().to('cpu', torch.float32)
-  mat = _device_matrices(src2trg_mat, mat_host, tex.device)
+  mat, mat_host = _matrices(src2trg_mat, mat_host, path, tex.device)
   cfg = dict(trg_downsampling=trg_downsampling, bg_layer_disp=bg_layer_disp,
              max_disp=max_disp, zbuf_scale=zbuf_scale, path=path,
              deterministic=bool(deterministic), band_rows=band_rows,
@@ -489,9 +449,7 @@ def forward_splat_matrix(ldi_src, src2trg_mat, compose_layers=True,
   when it feeds no loss the backward is the one without it.
   """
   tex, mask, disp = ldi_src
-  if mat_host is None and path not in ('atomic', 'tile'):
-    mat_host = src2trg_mat.detach().to('cpu', torch.float32)
-  mat = _device_matrices(src2trg_mat, mat_host, tex.device)
+  mat, mat_host = _matrices(src2trg_mat, mat_host, path, tex.device)
   cfg = dict(compose_layers=bool(compose_layers),
              compute_trg_disp=bool(compute_trg_disp),
              trg_downsampling=trg_downsampling, bg_layer_disp=bg_layer_disp,

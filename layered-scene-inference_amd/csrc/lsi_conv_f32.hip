@@ -32,6 +32,7 @@
 #include <string.h>
 
 #include "../../include/lsi_hip.h"
+#include "lsi_conv_host.h"
 #include "lsi_splat_internal.h"
 
 namespace {
@@ -350,20 +351,8 @@ __global__ __launch_bounds__(256) void conv_f32_pack_many_kernel(const LsiPackJo
 bool f_shape(FArgs& k, int* rw_out, int* nct_out, size_t* lds_out) {
   const int nct = (k.Cout % 64 == 0) ? 4 : (k.Cout % 32 == 0) ? 2 : 1;
   const int bn = 16 * nct;
-  int spany = 1, spanx = 1, maxoh = 1;
-  for (int c = 0; c < k.ncls; ++c) {
-    FClass& q = k.cls[c];
-    int dy1 = -128, dx1 = -128, dy0 = 127, dx0 = 127;
-    for (int t = 0; t < q.ntaps; ++t) {
-      dy0 = q.tdy[t] < dy0 ? q.tdy[t] : dy0; dy1 = q.tdy[t] > dy1 ? q.tdy[t] : dy1;
-      dx0 = q.tdx[t] < dx0 ? q.tdx[t] : dx0; dx1 = q.tdx[t] > dx1 ? q.tdx[t] : dx1;
-    }
-    if (q.ntaps == 0) { dy0 = dy1 = dx0 = dx1 = 0; }
-    q.dy0 = dy0; q.dx0 = dx0;
-    spany = dy1 - dy0 + 1 > spany ? dy1 - dy0 + 1 : spany;
-    spanx = dx1 - dx0 + 1 > spanx ? dx1 - dx0 + 1 : spanx;
-    maxoh = q.OHt > maxoh ? q.OHt : maxoh;
-  }
+  const ConvSpans sp = conv_tap_spans(k);
+  const int spany = sp.spany, spanx = sp.spanx, maxoh = sp.maxoh;
   k.PW = 15 * k.s + spanx;
   for (int rw = 4; rw >= 1; rw >>= 1) {
     if (rw > 1 && 4 * (rw / 2) >= maxoh) continue;   // (a shorter block covers the rows)
@@ -379,11 +368,7 @@ bool f_shape(FArgs& k, int* rw_out, int* nct_out, size_t* lds_out) {
       if (patch + (size_t)gc * bn * F_PIX <= F_LDS_CAP) { g = gc; break; }
     if (!g) continue;
     k.G = g;
-    for (int c = 0; c < k.ncls; ++c) {
-      FClass& q = k.cls[c];
-      for (int t = 0; t < F_MAXTAPS + 1; ++t)
-        q.toff[t] = t < q.ntaps ? ((q.tdy[t] - q.dy0) * k.PW + (q.tdx[t] - q.dx0)) * F_PIX : 0;
-    }
+    conv_tap_offsets(k, F_PIX, F_MAXTAPS + 1);
     *rw_out = rw; *nct_out = nct;
     *lds_out = patch + (size_t)g * bn * F_PIX;
     return true;
@@ -391,60 +376,17 @@ bool f_shape(FArgs& k, int* rw_out, int* nct_out, size_t* lds_out) {
   return false;
 }
 
-// Splits over the input channels: as many as bring a launch of `nwg` tiles to
-// ~2 workgroups per CU, at least two chunks each (lsi_conv_igemm.hip: ig_splits).
-int f_splits(const FArgs& k, long nwg) {
-  const int nch = k.Cin / 32;
-  if (nch < 4 || nwg <= 0 || nwg * 2 > 512) return 1;
-  long ks = 512 / nwg;
-  if (ks > nch / 2) ks = nch / 2;
-  if (ks > 16) ks = 16;
-  return ks < 2 ? 1 : (int)ks;
-}
-
-struct FPlan {
-  int rw, nct, ks;
-  size_t lds;
-  dim3 grid;   // (grid.z without the splits)
-};
-
-int f_plan(FArgs& k, FPlan* p) {
-  if (!f_shape(k, &p->rw, &p->nct, &p->lds)) return LSI_EUNSUPPORTED;
-  const int th = 4 * p->rw, bn = 16 * p->nct;
-  int oh = 0, ow = 0;
-  for (int c = 0; c < k.ncls; ++c) {
-    oh = k.cls[c].OHt > oh ? k.cls[c].OHt : oh;
-    ow = k.cls[c].OWt > ow ? k.cls[c].OWt : ow;
-  }
-  p->ks = 1;
-  p->grid = dim3(0, 0, 0);
-  if (oh <= 0 || ow <= 0) return LSI_OK;
-  p->grid = dim3((ow + 15) / 16, (oh + th - 1) / th, k.ncls * k.N * (k.Cout / bn));
-  if (p->grid.z > 65535 || p->grid.y > 65535) return LSI_EUNSUPPORTED;
-  p->ks = f_splits(k, (long)p->grid.x * p->grid.y * p->grid.z);
-  if ((long)p->grid.z * p->ks > 65535) p->ks = 1;
-  return LSI_OK;
-}
-
-size_t f_part_bytes(const FArgs& k, int ks) {
-  return ks > 1 ? (size_t)ks * k.N * k.OHF * k.OWF * k.Cout * sizeof(float) : 0;
-}
+// The plan of a launch: split over the input channels towards 512 workgroups.
+int f_plan(FArgs& k, ConvPlan* p) { return conv_plan(k, f_shape, LSI_EUNSUPPORTED, 512, p); }
 
 int f_launch(FArgs& k, hipStream_t stream, void* workspace, size_t workspace_bytes) {
-  FPlan pl;
+  ConvPlan pl;
   const int prc = f_plan(k, &pl);
   if (prc != LSI_OK) return prc;
   if (pl.grid.x == 0) return LSI_OK;
   const int rw = pl.rw, nct = pl.nct;
   dim3 grid = pl.grid;
-  k.ks = 1;
-  k.part = nullptr;
-  if (pl.ks > 1 && workspace && !((uintptr_t)workspace & 15) &&
-      workspace_bytes >= f_part_bytes(k, pl.ks)) {
-    k.ks = pl.ks;
-    k.part = (float*)workspace;
-    grid.z *= pl.ks;
-  }
+  conv_adopt_split(k, pl, workspace, workspace_bytes, &grid);
   const void* fn = nullptr;
 #define F_CASE(R, C, GG) \
   if (rw == R && nct == C && k.G == GG) fn = (const void*)conv_f32_kernel<R, C, GG>
@@ -486,66 +428,16 @@ int f_launch(FArgs& k, hipStream_t stream, void* workspace, size_t workspace_byt
 // What the fp32 kernels take: the kernel's input channels (Cin forward, Cout
 // data gradient) multiples of 32, its output channels of 16.
 bool f_desc_ok(const LsiConvDesc* d) {
-  if (!d) return false;
-  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->OH <= 0 || d->OW <= 0) return false;
-  if (d->Cin <= 0 || d->Cout <= 0 || d->Cin % 32 || d->Cout % 16) return false;
-  if (d->KH < 1 || d->KW < 1 || d->KH > 7 || d->KW > 7) return false;
-  if (d->stride != 1 && d->stride != 2) return false;
-  if (d->pad_t < 0 || d->pad_l < 0 || d->pad_t >= d->KH || d->pad_l >= d->KW) return false;
+  if (!conv_desc_common(d, 16)) return false;
   // (the output grid must be the one the padding implies: every output pixel reads
   // at least one input pixel)
   if ((int64_t)(d->OH - 1) * d->stride - d->pad_t >= d->H) return false;
   if ((int64_t)(d->OW - 1) * d->stride - d->pad_l >= d->W) return false;
-  // int32 element offsets inside the kernels
-  if ((int64_t)d->N * d->H * d->W * d->Cin >= (1ll << 31)) return false;
-  if ((int64_t)d->N * d->OH * d->OW * d->Cout >= (1ll << 31)) return false;
   return true;
 }
 
 bool f_mode_ok(const LsiConvDesc* d, int mode) {
   return f_desc_ok(d) && (mode == 0 || d->Cout % 32 == 0);
-}
-
-// The tap lists (lsi_conv_igemm.hip: ig_classes).  mode 0: forward; 1: data
-// gradient (stride^2 parity classes of the input pixels).
-void f_classes(const LsiConvDesc* d, int mode, FArgs& k, int8_t* tap) {
-  memset(&k, 0, sizeof(k));
-  int nt = 0;
-  if (mode == 0) {
-    FClass& q = k.cls[0];
-    for (int y = 0; y < d->KH; ++y)
-      for (int xk = 0; xk < d->KW; ++xk) {
-        tap[nt] = (signed char)(y * d->KW + xk);
-        q.tdy[q.ntaps] = (signed char)(y - d->pad_t);
-        q.tdx[q.ntaps] = (signed char)(xk - d->pad_l);
-        ++q.ntaps; ++nt;
-      }
-    q.OHt = d->OH; q.OWt = d->OW; q.wofs = 0;
-    k.ncls = 1;
-    k.N = d->N; k.H = d->H; k.W = d->W; k.Cin = d->Cin; k.Cout = d->Cout;
-    k.s = d->stride; k.os = 1; k.OHF = d->OH; k.OWF = d->OW;
-    return;
-  }
-  const int s = d->stride;
-  for (int p = 0; p < s; ++p)
-    for (int q_ = 0; q_ < s; ++q_) {
-      FClass& q = k.cls[k.ncls++];
-      q.wofs = nt;
-      for (int y = 0; y < d->KH; ++y) {
-        if ((p + d->pad_t - y) % s != 0) continue;
-        for (int xk = 0; xk < d->KW; ++xk) {
-          if ((q_ + d->pad_l - xk) % s != 0) continue;
-          tap[nt] = (signed char)(y * d->KW + xk);
-          q.tdy[q.ntaps] = (signed char)((p + d->pad_t - y) / s);
-          q.tdx[q.ntaps] = (signed char)((q_ + d->pad_l - xk) / s);
-          ++q.ntaps; ++nt;
-        }
-      }
-      q.ooy = p; q.oox = q_;
-      q.OHt = (d->H - p + s - 1) / s; q.OWt = (d->W - q_ + s - 1) / s;
-    }
-  k.N = d->N; k.H = d->OH; k.W = d->OW; k.Cin = d->Cout; k.Cout = d->Cin;
-  k.s = 1; k.os = s; k.OHF = d->H; k.OWF = d->W;
 }
 
 // ---- weight gradient ------------------------------------------------------------
@@ -732,95 +624,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32_kernel(FwArgs a) {
   }
 }
 
-// out (the parameter's layout) = sum over the pixel blocks' partials
-// [blk][tap][co][ci], in block order (lsi_conv_wgrad_igemm.hip's two folds)
-__global__ __launch_bounds__(1024) void conv_wgrad_f32_fold_kernel(const float* part, int nblk,
-                                                                   int nout, float* out, int khw,
-                                                                   int Cin, int cl) {
-  __shared__ float red[16][64];
-  const int o = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
-  float s = 0.0f;
-  if (o < nout) {
-    float s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    int w = grp;
-    for (; w + 48 < nblk; w += 64) {
-      s += part[(size_t)w * nout + o];
-      s1 += part[(size_t)(w + 16) * nout + o];
-      s2 += part[(size_t)(w + 32) * nout + o];
-      s3 += part[(size_t)(w + 48) * nout + o];
-    }
-    for (; w < nblk; w += 16) s += part[(size_t)w * nout + o];
-    s += s1 + s2 + s3;
-  }
-  red[grp][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (grp == 0 && o < nout) {
-    float v = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) v += red[q][threadIdx.x];
-    const int per = nout / khw;
-    const int tap = o / per, rest = o - tap * per;
-    if (cl) {
-      const int co = rest / Cin, ci = rest - co * Cin;
-      out[((size_t)co * khw + tap) * Cin + ci] = v;
-    } else {
-      out[(size_t)rest * khw + tap] = v;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void conv_wgrad_f32_fold_t_kernel(const float* part, int nblk,
-                                                                    int Cout, int Cin, int khw,
-                                                                    float* out, int cl) {
-  extern __shared__ float fw_tile[];  // [64][khw + 1]
-  const int ncc = Cin / 64;
-  const int co = blockIdx.x / ncc, ci0 = (blockIdx.x - co * ncc) * 64;
-  const int l = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const size_t nout = (size_t)khw * Cout * Cin;
-  for (int tap = grp; tap < khw; tap += 4) {
-    const float* p = part + ((size_t)tap * Cout + co) * Cin + ci0 + l;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int w = 0;
-    for (; w + 3 < nblk; w += 4) {
-      s0 += p[(size_t)w * nout];
-      s1 += p[(size_t)(w + 1) * nout];
-      s2 += p[(size_t)(w + 2) * nout];
-      s3 += p[(size_t)(w + 3) * nout];
-    }
-    for (; w < nblk; ++w) s0 += p[(size_t)w * nout];
-    fw_tile[l * (khw + 1) + tap] = (s0 + s1) + (s2 + s3);
-  }
-  __syncthreads();
-  if (cl) {
-    for (int i = threadIdx.x; i < 64 * khw; i += 256) {
-      const int tap = i >> 6, c = i & 63;
-      out[((size_t)co * khw + tap) * Cin + ci0 + c] = fw_tile[c * (khw + 1) + tap];
-    }
-    return;
-  }
-  float* o = out + ((size_t)co * Cin + ci0) * khw;
-  for (int i = threadIdx.x; i < 64 * khw; i += 256) {
-    const int c = i / khw, tap = i - c * khw;
-    o[i] = fw_tile[c * (khw + 1) + tap];
-  }
-}
-
 // Rows per stage, pixel blocks, LDS bytes; false: not taken (partial sums over
 // the cap: small maps with many channels stay on the library).
 bool fw_plan(const LsiConvDesc* d, FwArgs& k, int* nct_out, size_t* lds_out, int* nblk_out) {
   const int nct = (d->Cout % 64 == 0) ? 4 : (d->Cout % 32 == 0) ? 2 : 1;
   const int bn = 16 * nct, gsz = fw_gs(bn), s = d->stride, xs = fw_xs(s);
-  k.ntaps = d->KH * d->KW;
-  k.khw = k.ntaps;
-  k.ntg = (k.ntaps + FW_GT - 1) / FW_GT;
-  int nt = 0;
-  for (int y = 0; y < d->KH; ++y)
-    for (int x = 0; x < d->KW; ++x) {
-      k.tdy[nt] = (signed char)(y - d->pad_t);
-      k.tdx[nt] = (signed char)(x - d->pad_l);
-      ++nt;
-    }
-  k.dy0 = -d->pad_t; k.dx0 = -d->pad_l;
+  conv_wgrad_taps(d, k, FW_GT);
   k.PW = 31 * s + d->KW;
   int th = 0;
   for (int cand = 8; cand >= 1; cand >>= 1) {
@@ -832,16 +641,9 @@ bool fw_plan(const LsiConvDesc* d, FwArgs& k, int* nct_out, size_t* lds_out, int
     break;
   }
   if (!th) return false;
-  k.TH = th;
-  k.nstrip = (d->OW + 31) / 32;
   const long chan_wgs = (long)(d->Cin / 32) * k.ntg * (d->Cout / bn);
   const size_t wbytes = (size_t)d->Cout * d->Cin * k.khw * sizeof(float);
-  k.nrs = (d->OH + th - 1) / th;
-  const long nstage = (long)d->N * k.nrs;
-  long ps = 512 / (chan_wgs * k.nstrip);
-  if (ps < 1) ps = 1;
-  if (ps > nstage) ps = nstage;
-  while (ps > 1 && (size_t)(ps * k.nstrip) * wbytes > FW_PART_CAP) --ps;
+  const long ps = conv_wgrad_ps(d, k, th, chan_wgs, FW_PART_CAP);
   k.PS = (int)ps;
   const long nblk = ps * k.nstrip;
   if ((size_t)nblk * wbytes > FW_PART_CAP || nblk > 65535 * 32L) return false;
@@ -862,20 +664,8 @@ extern "C" size_t lsi_conv2d_f32_packed_bytes(const LsiConvDesc* d) {
 extern "C" int lsi_conv2d_f32_pack_job(const LsiConvDesc* d, int32_t mode, const float* weight,
                                        void* packed, size_t packed_bytes, LsiPackJob* job,
                                        int32_t* nblocks) {
-  if (!d || !weight || !packed || !job || !nblocks) return LSI_ENULL;
-  if (!f_desc_ok(d)) return LSI_EUNSUPPORTED;
-  if (mode < 0 || mode > 3) return LSI_EINVAL;
-  if ((uintptr_t)packed & 15) return LSI_EINVAL;
-  if (packed_bytes < lsi_conv2d_f32_packed_bytes(d)) return LSI_EWORKSPACE;
-  FArgs k;
-  memset(job, 0, sizeof(*job));
-  f_classes(d, mode & 1, k, job->tap);
-  job->w = weight; job->dst = packed;
-  job->D0 = d->Cout; job->D1 = d->Cin; job->khw = d->KH * d->KW; job->tr = mode;
-  job->ntaps = d->KH * d->KW;
-  job->block0 = 0;
-  *nblocks = ((d->Cin + 31) / 32) * ((d->Cout + 31) / 32);
-  return LSI_OK;
+  return conv_pack_job<FArgs>(d, mode, weight, packed, packed_bytes, job, nblocks, f_desc_ok(d),
+                              lsi_conv2d_f32_packed_bytes(d));
 }
 
 extern "C" int lsi_conv2d_f32_pack(const LsiConvDesc* d, int32_t mode, const float* weight,
@@ -902,11 +692,11 @@ extern "C" size_t lsi_conv2d_f32_workspace_bytes(const LsiConvDesc* d, int32_t m
   if (mode < 0 || mode > 1 || !f_mode_ok(d, mode)) return 0;
   FArgs k;
   int8_t tap[56];
-  f_classes(d, mode, k, tap);
+  conv_classes(d, mode, k, tap);
   k.C1 = k.Cin; k.O1 = k.Cout; k.ks = 1;
-  FPlan pl;
+  ConvPlan pl;
   if (f_plan(k, &pl) != LSI_OK || pl.grid.x == 0) return 0;
-  return f_part_bytes(k, pl.ks);
+  return conv_part_bytes(k, pl.ks);
 }
 
 extern "C" int lsi_conv2d_f32_run(const LsiConvDesc* d, int32_t mode, const LsiConvIO* io,
@@ -924,7 +714,7 @@ extern "C" int lsi_conv2d_f32_run(const LsiConvDesc* d, int32_t mode, const LsiC
     return LSI_EUNSUPPORTED;
   FArgs k;
   int8_t tap[56];
-  f_classes(d, mode, k, tap);
+  conv_classes(d, mode, k, tap);
   k.x = (const float*)io->x; k.wp = (const float*)io->packed; k.out = (float*)io->out;
   k.C1 = k.Cin;
   k.O1 = k.Cout;
@@ -992,13 +782,5 @@ extern "C" int lsi_conv2d_wgrad_f32(const LsiConvDesc* d, const void* x1, const 
   void* kargs[1] = {&k};
   if (hipLaunchKernel(fn, grid, dim3(256), kargs, lds, stream) != hipSuccess) return LSI_ELAUNCH;
   if (hipGetLastError() != hipSuccess) return LSI_ELAUNCH;
-  const int khw = d->KH * d->KW;
-  if (d->Cin % 64 == 0 && (long)d->Cout * (d->Cin / 64) >= 1024)
-    hipLaunchKernelGGL(conv_wgrad_f32_fold_t_kernel, dim3((unsigned)(d->Cout * (d->Cin / 64))),
-                       dim3(256), (size_t)64 * (khw + 1) * sizeof(float), stream, k.part, nblk,
-                       d->Cout, d->Cin, khw, g_weight, weight_layout);
-  else
-    hipLaunchKernelGGL(conv_wgrad_f32_fold_kernel, dim3((unsigned)((nout + 63) / 64)), dim3(1024),
-                       0, stream, k.part, nblk, (int)nout, g_weight, khw, d->Cin, weight_layout);
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+  return lsi_conv_wgrad_fold(k.part, nblk, d, g_weight, weight_layout, stream);
 }

@@ -43,6 +43,7 @@
 
 #include "../../include/lsi_hip.h"
 #include "lsi_bn_ws.h"
+#include "lsi_conv_host.h"
 #include "lsi_splat_internal.h"
 
 namespace {
@@ -532,21 +533,8 @@ constexpr size_t IG_LDS_CAP = 80 * 1024;  // two workgroups per CU
 bool ig_shape(IgArgs& k, int* rw_out, int* nct_out, size_t* lds_out) {
   const int nct = (k.Cout % 64 == 0) ? 4 : 2;
   const int bn = 16 * nct;
-  int spany = 1, spanx = 1, maxtaps = 0, maxoh = 1;
-  for (int c = 0; c < k.ncls; ++c) {
-    IgClass& q = k.cls[c];
-    int dy1 = -128, dx1 = -128, dy0 = 127, dx0 = 127;
-    for (int t = 0; t < q.ntaps; ++t) {
-      dy0 = q.tdy[t] < dy0 ? q.tdy[t] : dy0; dy1 = q.tdy[t] > dy1 ? q.tdy[t] : dy1;
-      dx0 = q.tdx[t] < dx0 ? q.tdx[t] : dx0; dx1 = q.tdx[t] > dx1 ? q.tdx[t] : dx1;
-    }
-    if (q.ntaps == 0) { dy0 = dy1 = dx0 = dx1 = 0; }
-    q.dy0 = dy0; q.dx0 = dx0;
-    spany = dy1 - dy0 + 1 > spany ? dy1 - dy0 + 1 : spany;
-    spanx = dx1 - dx0 + 1 > spanx ? dx1 - dx0 + 1 : spanx;
-    maxtaps = q.ntaps > maxtaps ? q.ntaps : maxtaps;
-    maxoh = q.OHt > maxoh ? q.OHt : maxoh;
-  }
+  const ConvSpans sp = conv_tap_spans(k);
+  const int spany = sp.spany, spanx = sp.spanx, maxoh = sp.maxoh;
   k.PW = 15 * k.s + spanx;
   static const char* rw_env = getenv("LSI_IGEMM_MAXRW");   // experiments
   const int rw_max = rw_env ? atoi(rw_env) : 8;
@@ -589,12 +577,7 @@ bool ig_shape(IgArgs& k, int* rw_out, int* nct_out, size_t* lds_out) {
     }
     if (!g) continue;
     k.G = g;
-    for (int c = 0; c < k.ncls; ++c) {
-      IgClass& q = k.cls[c];
-      for (int t = 0; t < IG_MAXTAPS + 7; ++t)
-        q.toff[t] = t < q.ntaps
-            ? ((q.tdy[t] - q.dy0) * k.PW + (q.tdx[t] - q.dx0)) * IG_PIX : 0;
-    }
+    conv_tap_offsets(k, IG_PIX, IG_MAXTAPS + 7);
     *rw_out = rw; *nct_out = nct;
     *lds_out = patch + (size_t)g * bn * IG_PIX;
     return true;
@@ -602,67 +585,23 @@ bool ig_shape(IgArgs& k, int* rw_out, int* nct_out, size_t* lds_out) {
   return false;
 }
 
-// The split over the input channels (IgArgs::ks) of a launch of `nwg` tiles:
-// as many splits as bring the launch to ~2 workgroups per CU, at least two
-// chunks each (LSI_IGEMM_SPLITK: the target workgroup count, 0 = never).
-int ig_splits(const IgArgs& k, long nwg) {
+// The plan of a launch (LSI_IGEMM_SPLITK: the workgroup count the split over the
+// input channels aims at, 0 = never).
+int ig_plan(IgArgs& k, ConvPlan* p) {
   static const char* env = getenv("LSI_IGEMM_SPLITK");   // experiments
-  const long target = env ? atol(env) : 512;
-  const int nch = k.Cin / 32;
-  if (target <= 0 || nch < 4 || nwg <= 0 || nwg * 2 > target) return 1;
-  long ks = target / nwg;
-  if (ks > nch / 2) ks = nch / 2;
-  if (ks > 16) ks = 16;
-  return ks < 2 ? 1 : (int)ks;
-}
-
-static inline int bn_of(int nct) { return 16 * nct; }
-
-struct IgPlan {
-  int rw, nct, ks;
-  size_t lds;
-  dim3 grid;   // (grid.z without the splits)
-};
-
-int ig_plan(IgArgs& k, IgPlan* p) {
-  if (!ig_shape(k, &p->rw, &p->nct, &p->lds)) return LSI_EUNSUPPORTED;
-  const int th = 4 * p->rw, bn = 16 * p->nct;
-  int oh = 0, ow = 0;
-  for (int c = 0; c < k.ncls; ++c) {
-    oh = k.cls[c].OHt > oh ? k.cls[c].OHt : oh;
-    ow = k.cls[c].OWt > ow ? k.cls[c].OWt : ow;
-  }
-  p->ks = 1;
-  p->grid = dim3(0, 0, 0);
-  if (oh <= 0 || ow <= 0) return LSI_OK;
-  p->grid = dim3((ow + 15) / 16, (oh + th - 1) / th, k.ncls * k.N * (k.Cout / bn));
-  if (p->grid.z > 65535 || p->grid.y > 65535) return LSI_EINVAL;
-  p->ks = ig_splits(k, (long)p->grid.x * p->grid.y * p->grid.z);
-  if ((long)p->grid.z * p->ks > 65535) p->ks = 1;
-  return LSI_OK;
-}
-
-size_t ig_part_bytes(const IgArgs& k, int ks) {
-  return ks > 1 ? (size_t)ks * k.N * k.OHF * k.OWF * k.Cout * sizeof(float) : 0;
+  return conv_plan(k, ig_shape, LSI_EINVAL, env ? atol(env) : 512, p);
 }
 
 int ig_launch(IgArgs& k, hipStream_t stream, void* workspace = nullptr,
               size_t workspace_bytes = 0) {
-  IgPlan pl;
+  ConvPlan pl;
   const int prc = ig_plan(k, &pl);
   if (prc != LSI_OK) return prc;
   if (pl.grid.x == 0) return LSI_OK;
   const int rw = pl.rw, nct = pl.nct;
   const size_t lds = pl.lds;
   dim3 grid = pl.grid;
-  k.ks = 1;
-  k.part = nullptr;
-  if (pl.ks > 1 && workspace && !((uintptr_t)workspace & 15) &&
-      workspace_bytes >= ig_part_bytes(k, pl.ks)) {
-    k.ks = pl.ks;
-    k.part = (float*)workspace;
-    grid.z *= pl.ks;
-  }
+  conv_adopt_split(k, pl, workspace, workspace_bytes, &grid);
   {
     // (bijective only when the tiles split evenly over the eight XCDs.  Taken for
     // the parity classes of large maps only -- `upcnv1` 88 -> 71 us forward,
@@ -713,63 +652,7 @@ int ig_launch(IgArgs& k, hipStream_t stream, void* workspace = nullptr,
   return LSI_OK;
 }
 
-bool desc_ok(const LsiConvDesc* d) {
-  if (!d) return false;
-  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->OH <= 0 || d->OW <= 0) return false;
-  if (d->Cin <= 0 || d->Cout <= 0 || d->Cin % 32 || d->Cout % 32) return false;
-  if (d->KH < 1 || d->KW < 1 || d->KH > 7 || d->KW > 7) return false;
-  if (d->stride != 1 && d->stride != 2) return false;
-  if (d->pad_t < 0 || d->pad_l < 0 || d->pad_t >= d->KH || d->pad_l >= d->KW) return false;
-  // int32 element offsets inside the kernels
-  if ((int64_t)d->N * d->H * d->W * d->Cin >= (1ll << 31)) return false;
-  if ((int64_t)d->N * d->OH * d->OW * d->Cout >= (1ll << 31)) return false;
-  return true;
-}
-
-// The tap lists of a call.  mode 0: forward (one class); mode 1: data gradient
-// (stride^2 parity classes of input pixels).  `tap` receives ky * KW + kx of
-// every tap in class order (the order of the packed weights).
-void ig_classes(const LsiConvDesc* d, int mode, IgArgs& k, int8_t* tap) {
-  memset(&k, 0, sizeof(k));
-  int nt = 0;
-  if (mode == 0) {
-    IgClass& q = k.cls[0];
-    for (int y = 0; y < d->KH; ++y)
-      for (int xk = 0; xk < d->KW; ++xk) {
-        tap[nt] = (signed char)(y * d->KW + xk);
-        q.tdy[q.ntaps] = (signed char)(y - d->pad_t);
-        q.tdx[q.ntaps] = (signed char)(xk - d->pad_l);
-        ++q.ntaps; ++nt;
-      }
-    q.OHt = d->OH; q.OWt = d->OW; q.wofs = 0;
-    k.ncls = 1;
-    k.N = d->N; k.H = d->H; k.W = d->W; k.Cin = d->Cin; k.Cout = d->Cout;
-    k.s = d->stride; k.os = 1; k.OHF = d->OH; k.OWF = d->OW;
-    return;
-  }
-  const int s = d->stride;
-  // input pixels (iy, ix) = (s i + p, s j + q): the taps with ky = p + pad_t (mod s)
-  //   gx[s i + p] += gy[oy] W[ky],   s oy + ky - pad_t = s i + p
-  for (int p = 0; p < s; ++p)
-    for (int q_ = 0; q_ < s; ++q_) {
-      IgClass& q = k.cls[k.ncls++];
-      q.wofs = nt;
-      for (int y = 0; y < d->KH; ++y) {
-        if ((p + d->pad_t - y) % s != 0) continue;
-        for (int xk = 0; xk < d->KW; ++xk) {
-          if ((q_ + d->pad_l - xk) % s != 0) continue;
-          tap[nt] = (signed char)(y * d->KW + xk);
-          q.tdy[q.ntaps] = (signed char)((p + d->pad_t - y) / s);
-          q.tdx[q.ntaps] = (signed char)((q_ + d->pad_l - xk) / s);
-          ++q.ntaps; ++nt;
-        }
-      }
-      q.ooy = p; q.oox = q_;
-      q.OHt = (d->H - p + s - 1) / s; q.OWt = (d->W - q_ + s - 1) / s;
-    }
-  k.N = d->N; k.H = d->OH; k.W = d->OW; k.Cin = d->Cout; k.Cout = d->Cin;
-  k.s = 1; k.os = s; k.OHF = d->H; k.OWF = d->W;
-}
+bool desc_ok(const LsiConvDesc* d) { return conv_desc_common(d, 32); }
 
 }  // namespace
 
@@ -783,20 +666,8 @@ extern "C" size_t lsi_conv2d_packed_bytes(const LsiConvDesc* d) {
 extern "C" int lsi_conv2d_pack_job(const LsiConvDesc* d, int32_t mode, const float* weight,
                                    void* packed, size_t packed_bytes, LsiPackJob* job,
                                    int32_t* nblocks) {
-  if (!d || !weight || !packed || !job || !nblocks) return LSI_ENULL;
-  if (!desc_ok(d)) return LSI_EUNSUPPORTED;
-  if (mode < 0 || mode > 3) return LSI_EINVAL;
-  if ((uintptr_t)packed & 15) return LSI_EINVAL;
-  if (packed_bytes < lsi_conv2d_packed_bytes(d)) return LSI_EWORKSPACE;
-  IgArgs k;
-  memset(job, 0, sizeof(*job));
-  ig_classes(d, mode & 1, k, job->tap);
-  job->w = weight; job->dst = packed;
-  job->D0 = d->Cout; job->D1 = d->Cin; job->khw = d->KH * d->KW; job->tr = mode;
-  job->ntaps = d->KH * d->KW;
-  job->block0 = 0;
-  *nblocks = (d->Cin / 32) * (d->Cout / 32);
-  return LSI_OK;
+  return conv_pack_job<IgArgs>(d, mode, weight, packed, packed_bytes, job, nblocks, desc_ok(d),
+                               lsi_conv2d_packed_bytes(d));
 }
 
 extern "C" int lsi_conv2d_pack(const LsiConvDesc* d, int32_t mode, const float* weight,
@@ -832,7 +703,7 @@ static int ig_run(const LsiConvDesc* d, int mode, const void* src, const void* p
   if (((uintptr_t)src & 15) || ((uintptr_t)dst & 7) || ((uintptr_t)packed & 15)) return LSI_EINVAL;
   IgArgs k;
   int8_t tap[56];
-  ig_classes(d, mode, k, tap);
+  conv_classes(d, mode, k, tap);
   k.x = (const __bf16*)src; k.wp = (const __bf16*)packed; k.out = (__bf16*)dst;
   k.C1 = k.Cin;
   k.O1 = k.Cout;
@@ -863,11 +734,11 @@ extern "C" size_t lsi_conv2d_workspace_bytes(const LsiConvDesc* d, int32_t mode)
   if (!desc_ok(d) || mode < 0 || mode > 1) return 0;
   IgArgs k;
   int8_t tap[56];
-  ig_classes(d, mode, k, tap);
+  conv_classes(d, mode, k, tap);
   k.C1 = k.Cin; k.O1 = k.Cout; k.ks = 1;
-  IgPlan pl;
+  ConvPlan pl;
   if (ig_plan(k, &pl) != LSI_OK || pl.grid.x == 0) return 0;
-  return ig_part_bytes(k, pl.ks);
+  return conv_part_bytes(k, pl.ks);
 }
 
 extern "C" int lsi_conv2d_run(const LsiConvDesc* d, int32_t mode, const LsiConvIO* io,

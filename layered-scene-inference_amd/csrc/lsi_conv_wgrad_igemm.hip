@@ -33,6 +33,7 @@
 #include <string.h>
 
 #include "../../include/lsi_hip.h"
+#include "lsi_conv_host.h"
 #include "lsi_splat_internal.h"
 
 namespace {
@@ -326,34 +327,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_fold_t_kernel(const float* par
   }
 }
 
-bool gw_desc_ok(const LsiConvDesc* d) {
-  if (!d) return false;
-  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->OH <= 0 || d->OW <= 0) return false;
-  if (d->Cin <= 0 || d->Cout <= 0 || d->Cin % 32 || d->Cout % 32) return false;
-  if (d->KH < 1 || d->KW < 1 || d->KH > 7 || d->KW > 7) return false;
-  if (d->stride != 1 && d->stride != 2) return false;
-  if (d->pad_t < 0 || d->pad_l < 0 || d->pad_t >= d->KH || d->pad_l >= d->KW) return false;
-  if ((int64_t)d->N * d->H * d->W * d->Cin >= (1ll << 31)) return false;
-  if ((int64_t)d->N * d->OH * d->OW * d->Cout >= (1ll << 31)) return false;
-  return true;
-}
-
 // Tile rows per stage, rows per pixel block, LDS bytes; false: not taken
 // (partial sums too large: small maps with many channels stay on the library).
 bool gw_plan(const LsiConvDesc* d, GwArgs& k, int* nct_out, size_t* lds_out, int* nblk_out) {
   const int nct = (d->Cout % 64 == 0) ? 4 : 2;
   const int bn = 16 * nct, gs = gw_gs(bn), s = d->stride;
-  k.ntaps = d->KH * d->KW;
-  k.khw = k.ntaps;
-  k.ntg = (k.ntaps + GW_GT - 1) / GW_GT;
-  int nt = 0;
-  for (int y = 0; y < d->KH; ++y)
-    for (int x = 0; x < d->KW; ++x) {
-      k.tdy[nt] = (signed char)(y - d->pad_t);
-      k.tdx[nt] = (signed char)(x - d->pad_l);
-      ++nt;
-    }
-  k.dy0 = -d->pad_t; k.dx0 = -d->pad_l;
+  conv_wgrad_taps(d, k, GW_GT);
   k.PW = 31 * s + d->KW;
   int th = 0;
   for (int cand = 8; cand >= 1; cand >>= 1) {
@@ -365,18 +344,9 @@ bool gw_plan(const LsiConvDesc* d, GwArgs& k, int* nct_out, size_t* lds_out, int
     break;
   }
   if (!th) return false;
-  k.TH = th;
-  k.nstrip = (d->OW + 31) / 32;
-  // workgroups per strip: as many as keep the whole launch resident (512 = two per
-  // CU), at most one per stage, partial sums bounded
   const long chan_wgs = (long)(d->Cin / 32) * k.ntg * (d->Cout / bn);
   const size_t wbytes = (size_t)d->Cout * d->Cin * k.khw * sizeof(float);
-  k.nrs = (d->OH + th - 1) / th;
-  const long nstage = (long)d->N * k.nrs;
-  long ps = 512 / (chan_wgs * k.nstrip);
-  if (ps < 1) ps = 1;
-  if (ps > nstage) ps = nstage;
-  while (ps > 1 && (size_t)(ps * k.nstrip) * wbytes > GW_PART_CAP) --ps;
+  long ps = conv_wgrad_ps(d, k, th, chan_wgs, GW_PART_CAP);
   // (the sibling swizzle needs ps * nstrip % 8 == 0: the largest such ps, if it
   // keeps at least three quarters of the workgroups)
   k.swz = 0;
@@ -400,8 +370,22 @@ bool gw_plan(const LsiConvDesc* d, GwArgs& k, int* nct_out, size_t* lds_out, int
 
 }  // namespace
 
+int lsi_conv_wgrad_fold(const float* part, int nblk, const LsiConvDesc* d, float* g_weight,
+                        int cl, hipStream_t stream) {
+  const int khw = d->KH * d->KW;
+  const size_t nout = (size_t)d->Cout * d->Cin * khw;
+  if (d->Cin % 64 == 0 && (long)d->Cout * (d->Cin / 64) >= 1024)
+    hipLaunchKernelGGL(conv_wgrad_fold_t_kernel, dim3((unsigned)(d->Cout * (d->Cin / 64))), dim3(256),
+                       (size_t)64 * (khw + 1) * sizeof(float), stream, part, nblk, d->Cout,
+                       d->Cin, khw, g_weight, cl);
+  else
+    hipLaunchKernelGGL(conv_wgrad_fold_kernel, dim3((unsigned)((nout + 63) / 64)), dim3(1024), 0,
+                       stream, part, nblk, (int)nout, g_weight, khw, d->Cin, cl);
+  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+}
+
 extern "C" size_t lsi_conv2d_wgrad_workspace_bytes(const LsiConvDesc* d) {
-  if (!gw_desc_ok(d)) return 0;
+  if (!conv_desc_common(d, 32)) return 0;
   GwArgs k;
   int nct, nblk;
   size_t lds;
@@ -433,7 +417,7 @@ static int gw_run(const LsiConvDesc* d, const void* x, const void* x2, int c1, c
                   float* g_weight, void* workspace, size_t workspace_bytes,
                   lsi_stream_t stream_, int cl) {
   if (!d || !x || !gy || !g_weight || !workspace) return LSI_ENULL;
-  if (!gw_desc_ok(d)) return LSI_EUNSUPPORTED;
+  if (!conv_desc_common(d, 32)) return LSI_EUNSUPPORTED;
   if (((uintptr_t)x & 15) || ((uintptr_t)gy & 15) || ((uintptr_t)workspace & 15)) return LSI_EINVAL;
   GwArgs k;
   memset(&k, 0, sizeof(k));
@@ -459,13 +443,5 @@ static int gw_run(const LsiConvDesc* d, const void* x, const void* x2, int c1, c
   void* kargs[1] = {&k};
   if (hipLaunchKernel(fn, grid, dim3(256), kargs, lds, stream) != hipSuccess) return LSI_ELAUNCH;
   if (hipGetLastError() != hipSuccess) return LSI_ELAUNCH;
-  const int khw = d->KH * d->KW;
-  if (d->Cin % 64 == 0 && (long)d->Cout * (d->Cin / 64) >= 1024)
-    hipLaunchKernelGGL(conv_wgrad_fold_t_kernel, dim3((unsigned)(d->Cout * (d->Cin / 64))), dim3(256),
-                       (size_t)64 * (khw + 1) * sizeof(float), stream, k.part, nblk, d->Cout,
-                       d->Cin, khw, g_weight, cl);
-  else
-    hipLaunchKernelGGL(conv_wgrad_fold_kernel, dim3((unsigned)((nout + 63) / 64)), dim3(1024), 0,
-                       stream, k.part, nblk, (int)nout, g_weight, khw, d->Cin, cl);
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+  return lsi_conv_wgrad_fold(k.part, nblk, d, g_weight, cl, stream);
 }

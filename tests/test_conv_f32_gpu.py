@@ -263,6 +263,28 @@ def test_every_kernel_repeats_bitwise(case, dev):
     assert torch.equal(a, b)
 
 
+def test_transposing_fold_writes_a_channels_last_weight_gradient(dev):
+  """1 x 4 x 4, 512 -> 128, 3 x 3: Cin a multiple of 64 and Cout * Cin / 64 = 1024,
+  so the partial sums take the fold that writes whole runs of the parameter's
+  layout (conv_wgrad_fold_t_kernel) -- here into a parameter with torch's
+  channels-last strides (weight_layout = 2)."""
+  from lsi.nnutils import _hip_conv
+  n, h, w, cin, cout = 1, 4, 4, 512, 128
+  g = torch.Generator().manual_seed(n + h + w + cin + cout)
+  x = _cl(_rand((n, cin, h, w), g, dev))
+  wt = _rand((cout, cin, 3, 3), g, dev, (1.0 / (cin * 9)) ** 0.5)
+  gy = _cl(_rand((n, cout, h, w), g, dev))
+  d = _hip_conv._conv_desc(n, h, w, cin, h, w, cout, 3, 3, 1, 1, 1)
+  assert _hip_conv.f32_wgrad_bytes(d) > 0
+  gw = _hip_conv._f32_wgrad(d, x, gy, wt.contiguous(memory_format=torch.channels_last))
+  assert gw.is_contiguous(memory_format=torch.channels_last) and not gw.is_contiguous()
+  (_, (_, gw64)), (_, (_, gwa)), (_, (_, gwl)) = _refs(
+      lambda a, b: _conv_ref(a, b, 1), (x, wt), gy)
+  _check('gw', gw, gw64, gwa, gwl)
+  # (the same sums as into a contiguous parameter: only the addresses differ)
+  assert torch.equal(gw, _hip_conv._f32_wgrad(d, x, gy, wt))
+
+
 def test_refusals_fall_back_to_the_library(dev, monkeypatch):
   from lsi import _C
   from lsi.nnutils import _hip_conv, nets

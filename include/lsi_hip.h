@@ -511,6 +511,48 @@ int lsi_view_synth_loss_bwd(int32_t nl, int32_t B, int32_t Ht, int32_t Wt,
                             lsi_stream_t stream);
 
 /*
+ * SSIM view-synthesis loss and metric (csrc/lsi_ssim.hip; no reference
+ * counterpart, the definition is DESIGN.md section 4.13).  recons
+ * [nl,B,Ht,Wt,3] contiguous, target [B,H,W,3] with the element strides t_s*,
+ * H % Ht == 0 and W % Wt == 0; t = the AREA resize of target as in
+ * lsi_view_synth_loss_fwd.  A window is a win x win patch (win odd, 3 .. 11)
+ * wholly inside the crop [y_min, Ht - y_min) x [x_min, Wt - x_min); its weights
+ * are g[i] g[j] with g from lsi_ssim_window.  Per window, layer and channel,
+ * with the weighted means mu_x, mu_y, E_xx, E_yy, E_xy of x = recons, y = t:
+ *   S = (2 mu_x mu_y + c1)(2 s_xy + c2) / ((mu_x^2 + mu_y^2 + c1)(s_x^2 + s_y^2 + c2))
+ *   d = (1 - (S_0 + S_1 + S_2) / 3) / 2
+ * LSI_EINVAL for an even or out-of-range win, a crop that leaves no window or
+ * non-integer factors, then LSI_ENULL, then LSI_EWORKSPACE (workspace:
+ * lsi_loss_workspace_bytes()), all before any launch.  No atomics: the same
+ * inputs give the same bits.
+ */
+typedef struct LsiSsimDesc {
+  int32_t nl, B, Ht, Wt, H, W, x_min, y_min, win;
+  float sigma, c1, c2;     /* sigma <= 0: the box window 1 / win              */
+  int64_t t_sb, t_sy, t_sx, t_sc;
+} LsiSsimDesc;
+
+/* Host only: the win weights the kernels use, g[i] ~ exp(-(i - (win - 1) / 2)^2
+ * / (2 sigma^2)) normalised to sum 1 in double and rounded to fp32. */
+int lsi_ssim_window(int32_t win, float sigma, float* out);
+/* out_loss (one device float) = mean over b and the windows of min_l d. */
+int lsi_ssim_loss_fwd(const LsiSsimDesc* desc, const float* recons,
+                      const float* target, float* out_loss, void* workspace,
+                      size_t workspace_bytes, lsi_stream_t stream);
+/* g_recons [nl,B,Ht,Wt,3], scaled by the device scalar g_loss: a window's share
+ * goes to the layers whose d equals the minimum bit for bit, split evenly.
+ * Every element is written; pixels outside the crop get 0. */
+int lsi_ssim_loss_bwd(const LsiSsimDesc* desc, const float* recons,
+                      const float* target, const float* g_loss, float* g_recons,
+                      lsi_stream_t stream);
+/* Adds the sum over b and the windows of layer 0's (S_0 + S_1 + S_2) / 3 to
+ * acc2[0] and the number of windows to acc2[1] (device doubles, zeroed by the
+ * caller once) in a one-block finishing kernel: no host synchronisation. */
+int lsi_eval_ssim(const LsiSsimDesc* desc, const float* recons, const float* target,
+                  double* acc2, void* workspace, size_t workspace_bytes,
+                  lsi_stream_t stream);
+
+/*
  * layers.compose, lsi/geometry/layers.py:29-70 with helpers.soft_z_buffering
  * (lsi/nnutils/helpers.py:140-160): white background layer at min_disp,
  * per-pixel softmax of log(mask + 1e-8) - depth / temp over the L + 1 layers,

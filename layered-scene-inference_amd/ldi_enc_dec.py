@@ -71,6 +71,14 @@ def build_parser():
   a('--indep_splat_wt', type=float, default=1.0)
   a('--compose_splat_wt', type=float, default=1.0)
   a('--splat_bdry_ignore', type=float, default=0.1)
+  a('--ssim_wt', type=float, default=0.0,
+    help='weight of the structural view-synthesis terms (DSSIM over '
+    '--ssim_win windows, csrc/lsi_ssim.hip): ssim_wt * (compose_splat_wt * '
+    'compose_ssim_loss + indep_splat_wt * indep_ssim_loss) is added to the '
+    'total; 0 = the six reference terms only')
+  a('--ssim_win', type=int, default=7, help='SSIM window size: odd, 3 .. 11')
+  a('--ssim_sigma', type=float, default=1.5,
+    help='sigma of the Gaussian SSIM window; <= 0: the box window')
   a('--zbuf_scale', type=float, default=50)
   a('--trg_splat_downsampling', type=float, default=0.5)
   a('--disp_smoothness_wt', type=float, default=0.1)
@@ -416,6 +424,13 @@ class Trainer(train_utils.Trainer):
     # view synthesis via forward splatting (ldi_enc_dec.py:296-357)
     zero = imgs_src.new_zeros(())
     indep_splat_loss, compose_splat_loss = zero, zero
+    ssim_wt = getattr(opts, 'ssim_wt', 0.0)
+    indep_ssim_loss, compose_ssim_loss = zero, zero
+
+    def ssim_loss(img, target):
+      return loss.ssim_view_synthesis_loss(
+          img, target, opts.splat_bdry_ignore, win=opts.ssim_win,
+          sigma=opts.ssim_sigma)
     # One sweep per direction renders the per-layer AND the composed view
     # (the reference makes four forward_splat calls whose per-layer splats
     # are identical pairwise).
@@ -438,9 +453,13 @@ class Trainer(train_utils.Trainer):
       if opts.indep_splat_wt > 0:
         indep_splat_loss = 2.0 * loss.view_synthesis_loss(
             img_i, target2, opts.splat_bdry_ignore)
+        if ssim_wt > 0:
+          indep_ssim_loss = 2.0 * ssim_loss(img_i, target2)
       if opts.compose_splat_wt > 0:
         compose_splat_loss = 2.0 * loss.view_synthesis_loss(
             img_c, target2, opts.splat_bdry_ignore)
+        if ssim_wt > 0:
+          compose_ssim_loss = 2.0 * ssim_loss(img_c, target2)
     elif opts.indep_splat_wt > 0 or opts.compose_splat_wt > 0:
       for which in ('trg', 'src'):
         if which == 'trg':
@@ -454,9 +473,13 @@ class Trainer(train_utils.Trainer):
         if opts.indep_splat_wt > 0:
           indep_splat_loss = indep_splat_loss + loss.view_synthesis_loss(
               img_i, target, opts.splat_bdry_ignore)
+          if ssim_wt > 0:
+            indep_ssim_loss = indep_ssim_loss + ssim_loss(img_i, target)
         if opts.compose_splat_wt > 0:
           compose_splat_loss = compose_splat_loss + loss.view_synthesis_loss(
               img_c, target, opts.splat_bdry_ignore)
+          if ssim_wt > 0:
+            compose_ssim_loss = compose_ssim_loss + ssim_loss(img_c, target)
 
     # regularisers (ldi_enc_dec.py:388-396): both from one read of each
     # disparity tensor (fused HIP kernel lsi_disp_reg_loss_fwd)
@@ -478,6 +501,10 @@ class Trainer(train_utils.Trainer):
       total = total + opts.compose_splat_wt * compose_splat_loss
     if opts.indep_splat_wt > 0:
       total = total + opts.indep_splat_wt * indep_splat_loss
+    if ssim_wt > 0:
+      # the structural terms ride on the L1 terms' weights
+      total = total + ssim_wt * (opts.compose_splat_wt * compose_ssim_loss +
+                                 opts.indep_splat_wt * indep_ssim_loss)
     if opts.incr_depth_wt > 0:
       total = total + (opts.incr_depth_wt / opts.max_disp) * incr_depth_loss
     if opts.disp_smoothness_wt > 0:
@@ -491,6 +518,9 @@ class Trainer(train_utils.Trainer):
         'disp_smoothness_loss': disp_smoothness_loss,
         'total_loss': total,
     }
+    if ssim_wt > 0:
+      scalars['compose_ssim_loss'] = compose_ssim_loss
+      scalars['indep_ssim_loss'] = indep_ssim_loss
     return total, scalars
 
 

@@ -47,6 +47,10 @@ def build_parser():
     help='accumulate the metrics on the device in the fused kernels of '
     'csrc/lsi_eval.hip and read them back once after the last iteration '
     '(eval_metrics.MetricAccumulator); false: the op route, one dict per view')
+  a('--eval_ssim', type=train_script._bool, default=False,
+    help='also score SSIM (layer 0 of the composed rendering, 11 x 11 Gaussian '
+    'windows, sigma 1.5, inside the border crop): `ssim` in the results, from '
+    'the fused kernel of csrc/lsi_ssim.hip on either metric route')
   return p
 
 
@@ -102,6 +106,7 @@ class Tester(object):
     inv_trans = -torch.matmul(inv_rot, trans)
     pc = nn_helpers.pixel_coords(o.batch_size, o.img_height, o.img_width)
     fused = acc is not None
+    ssim = (11, 1.5) if getattr(o, 'eval_ssim', False) else None
     # ground truth by data set (ldi_pred_eval.py:226-262): synthetic planes
     # carry 14 outputs (fg / bg disparities and background textures), KITTI
     # with --kitti_dl_disparities 8 (the SPS-stereo disparities of both views)
@@ -144,11 +149,12 @@ class Tester(object):
       if fused:
         acc.add_view_synthesis(
             ldi, pc, k_a, k_b, r, t, target, o, valid_mask=valid,
-            disocc_mask=disocc, gt_disp_trg=gt_disp, valid_above=valid_above)
+            disocc_mask=disocc, gt_disp_trg=gt_disp, valid_above=valid_above,
+            ssim=ssim)
       else:
         out.append(eval_metrics.view_synthesis_metrics(
             ldi, pc, k_a, k_b, r, t, target, o, valid_mask=valid,
-            disocc_mask=disocc, gt_disp_trg=gt_disp))
+            disocc_mask=disocc, gt_disp_trg=gt_disp, ssim=ssim))
     if gt is not None:
       if fused:
         acc.add_layer_prediction(ldi_src, ldi_trg, imgs_src, imgs_trg, gt, o)

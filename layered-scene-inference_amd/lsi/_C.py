@@ -66,6 +66,14 @@ class LsiLossDesc(ctypes.Structure):
       [('reserved', ctypes.c_int32)])
 
 
+class LsiSsimDesc(ctypes.Structure):
+  _fields_ = (
+      [(n, ctypes.c_int32) for n in ('nl', 'B', 'Ht', 'Wt', 'H', 'W', 'x_min',
+                                     'y_min', 'win')] +
+      [(n, ctypes.c_float) for n in ('sigma', 'c1', 'c2')] +
+      [(n, ctypes.c_int64) for n in ('t_sb', 't_sy', 't_sx', 't_sc')])
+
+
 class LsiConvDesc(ctypes.Structure):
   _fields_ = [(n, ctypes.c_int32) for n in (
       'N', 'H', 'W', 'Cin', 'OH', 'OW', 'Cout', 'KH', 'KW', 'stride', 'pad_t', 'pad_l')]
@@ -150,6 +158,12 @@ SIGNATURES = {
                                 [_VP] * 2 + [_SZ, _VP]),
     'lsi_view_synth_loss_bwd': (ctypes.c_int, [_I32] * 8 + [_VP] * 2 + [_I64] * 4 +
                                 [_VP] * 3),
+    'lsi_ssim_window': (ctypes.c_int, [_I32, _F32, _VP]),
+    'lsi_ssim_loss_fwd': (ctypes.c_int, [ctypes.POINTER(LsiSsimDesc)] + [_VP] * 4 +
+                          [_SZ, _VP]),
+    'lsi_ssim_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiSsimDesc)] + [_VP] * 5),
+    'lsi_eval_ssim': (ctypes.c_int, [ctypes.POINTER(LsiSsimDesc)] + [_VP] * 4 +
+                      [_SZ, _VP]),
     'lsi_compose_fwd': (ctypes.c_int, [_I32, _I64, _I32] + [_VP] * 3 +
                         [_I32, _F32, _F32, _VP, _VP]),
     'lsi_compose_depth_fwd': (ctypes.c_int, [_I32, _I64] + [_VP] * 2 +

@@ -164,6 +164,89 @@ def view_synthesis_loss(recons_splat, to_recons_img, x_min, y_min):
                           int(y_min))
 
 
+# launches of the SSIM kernels through this binding (the loss and the metric)
+CALLS = {'ssim_fwd': 0, 'ssim_bwd': 0, 'ssim_eval': 0}
+SSIM_C1, SSIM_C2 = 1e-4, 9e-4  # (0.01 R)^2, (0.03 R)^2 at dynamic range R = 1
+
+
+def ssim_desc(recons, target, x_min, y_min, win, sigma, what):
+  """The LsiSsimDesc of recons nl x B x Ht x Wt x 3 against target B x H x W x 3;
+  ValueError for what the kernels would refuse with LSI_EINVAL."""
+  nl, b, ht, wt, c = recons.shape
+  if c != 3 or tuple(target.shape[:1] + target.shape[3:]) != (b, 3):
+    raise ValueError('%s: 3-channel images of one batch size' % what)
+  _, h, w, _ = target.shape
+  if h % ht or w % wt:
+    raise ValueError('%s: the target (%d x %d) is no integer multiple of the '
+                     'rendering (%d x %d)' % (what, h, w, ht, wt))
+  win = int(win)
+  if win < 3 or win > 11 or win % 2 == 0:
+    raise ValueError('%s: the window size is odd, 3 .. 11 (got %d)' % (what, win))
+  if ht - 2 * y_min < win or wt - 2 * x_min < win:
+    raise ValueError('%s: the cropped rendering (%d x %d) holds no %d x %d window'
+                     % (what, ht - 2 * y_min, wt - 2 * x_min, win, win))
+  d = _C.LsiSsimDesc()
+  d.nl, d.B, d.Ht, d.Wt, d.H, d.W = nl, b, ht, wt, h, w
+  d.x_min, d.y_min, d.win = int(x_min), int(y_min), win
+  d.sigma, d.c1, d.c2 = float(sigma), SSIM_C1, SSIM_C2
+  d.t_sb, d.t_sy, d.t_sx, d.t_sc = target.stride()
+  return d
+
+
+class _Ssim(torch.autograd.Function):
+  """lsi_ssim_loss_fwd / _bwd."""
+
+  @staticmethod
+  def forward(ctx, recons, target, x_min, y_min, win, sigma):
+    dev = _C.require_device(recons, target)
+    recons = recons.contiguous()
+    d = ssim_desc(recons, target, x_min, y_min, win, sigma,
+                  'ssim_view_synthesis_loss')
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    ws, n = _workspace(dev)
+    CALLS['ssim_fwd'] += 1
+    rc = _C.lib().lsi_ssim_loss_fwd(ctypes.byref(d), _C.ptr(recons),
+                                    _C.ptr(target), _C.ptr(out), _C.ptr(ws), n,
+                                    _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_ssim_loss_fwd')
+    ctx.save_for_backward(recons, target)
+    ctx.desc = d
+    return out
+
+  @staticmethod
+  def backward(ctx, g):
+    recons, target = ctx.saved_tensors
+    dev = recons.device
+    g = g.contiguous().float()
+    g_recons = torch.empty_like(recons)
+    CALLS['ssim_bwd'] += 1
+    rc = _C.lib().lsi_ssim_loss_bwd(ctypes.byref(ctx.desc), _C.ptr(recons),
+                                    _C.ptr(target), _C.ptr(g), _C.ptr(g_recons),
+                                    _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_ssim_loss_bwd')
+    return g_recons, None, None, None, None, None
+
+
+def ssim_view_synthesis_loss(recons_splat, to_recons_img, x_min, y_min, win, sigma):
+  # the target is data, as in zbuffer_composition_loss
+  if torch.is_tensor(to_recons_img) and to_recons_img.requires_grad:
+    raise RuntimeError('ssim_view_synthesis_loss: to_recons_img is not '
+                       'differentiable on the HIP path (pass '
+                       'to_recons_img.detach())')
+  return _Ssim.apply(_f32(recons_splat), _f32(to_recons_img), int(x_min),
+                     int(y_min), int(win), float(sigma))
+
+
+def ssim_window(win, sigma):
+  """lsi_ssim_window: the `win` fp32 weights the kernels use (host only)."""
+  out = (ctypes.c_float * min(max(int(win), 1), 16))()
+  rc = _C.lib().lsi_ssim_window(int(win), float(sigma),
+                                ctypes.cast(out, ctypes.c_void_p))
+  if rc != _C.LSI_OK:
+    raise ValueError('ssim_window: the window size is odd, 3 .. 11 (got %d)' % win)
+  return list(out)
+
+
 class _Compose(torch.autograd.Function):
   """lsi_compose_fwd / lsi_compose_bwd on imgs [L,N,C], masks [L,N], dmaps
   [L,N] (contiguous fp32)."""

@@ -70,3 +70,19 @@ def view_synthesis_loss(recons_splat, to_recons_img, splat_bdry_ignore=0.05):
   return _hip.view_synthesis_loss(recons_splat, to_recons_img,
                                   _py2_round(wt * splat_bdry_ignore),
                                   _py2_round(ht * splat_bdry_ignore))
+
+
+def ssim_view_synthesis_loss(recons_splat, to_recons_img, splat_bdry_ignore=0.05,
+                             win=7, sigma=1.5):
+  """Structural view-synthesis loss (the reference has none):
+  the target AREA-downsampled and the border cropped as in
+  `view_synthesis_loss`, SSIM over the win x win windows that lie inside the
+  crop (Gaussian weights, sigma <= 0: box; C1 = 1e-4, C2 = 9e-4), DSSIM =
+  (1 - mean_c SSIM) / 2, min over layers, mean.  One fused HIP launch each way
+  (lsi_ssim_loss_fwd / _bwd); the gradient is w.r.t. recons_splat only."""
+  _, _, ht, wt, _ = recons_splat.shape
+  from lsi.loss import _hip  # pylint: disable=g-import-not-at-top
+  return _hip.ssim_view_synthesis_loss(recons_splat, to_recons_img,
+                                       _py2_round(wt * splat_bdry_ignore),
+                                       _py2_round(ht * splat_bdry_ignore), win,
+                                       sigma)

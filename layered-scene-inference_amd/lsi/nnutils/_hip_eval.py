@@ -103,6 +103,25 @@ def view_metrics(acc, ws, ws_bytes, recons, recons_disp, target, x_min, y_min,
   _C.check(rc, 'lsi_eval_view_metrics')
 
 
+def ssim_metric(acc2, recons, target, x_min, y_min, win, sigma):
+  """lsi_eval_ssim: adds the sum of layer 0's SSIM over the windows and their
+  number to `acc2`, two contiguous float64 on the device -- an accumulator of
+  its own, not part of the SLOT_COUNT doubles."""
+  from lsi.loss import _hip as loss_hip  # pylint: disable=g-import-not-at-top
+  dev = _C.require_device(recons, target)
+  if (acc2.device != dev or acc2.dtype != torch.float64 or acc2.numel() != 2 or
+      not acc2.is_contiguous()):
+    raise RuntimeError('the SSIM accumulator is 2 contiguous float64 on %s' % dev)
+  recons = recons.contiguous()
+  d = loss_hip.ssim_desc(recons, target, x_min, y_min, win, sigma, 'ssim_metric')
+  # (the loss kernels' workspace: two partial sums per block)
+  ws, n = loss_hip._workspace(dev)
+  loss_hip.CALLS['ssim_eval'] += 1
+  rc = _C.lib().lsi_eval_ssim(ctypes.byref(d), _C.ptr(recons), _C.ptr(target),
+                              _C.ptr(acc2), _C.ptr(ws), n, _C.stream_ptr(dev))
+  _C.check(rc, 'lsi_eval_ssim')
+
+
 def _layer_desc(tex, disp, bg_layer_disp):
   d = _C.LsiLossDesc()
   d.L, d.B, d.H, d.W = tex.shape[:4]

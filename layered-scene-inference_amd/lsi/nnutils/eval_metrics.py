@@ -22,14 +22,16 @@ def _centre_mask(b, h, w, frac, device):
 
 def view_synthesis_metrics(ldi_src, pixel_coords, k_s, k_t, rot, t, imgs_trg,
                            opts, valid_mask=None, disocc_mask=None,
-                           gt_disp_trg=None):
+                           gt_disp_trg=None, ssim=None):
   """Renders `ldi_src` into the target camera (compose_layers=True,
   compute_trg_disp=True: ldi_pred_eval.py:340-353) and accumulates the masked
   errors against `imgs_trg` (B x H x W x 3).
 
   opts needs: trg_splat_downsampling, zbuf_scale, bg_layer_disp, max_disp,
   splat_bdry_ignore.  valid_mask / disocc_mask / gt_disp_trg: B x H x W x 1 or
-  None.  Returns a dict name -> (sum, norm) of 0-d tensors.
+  None.  Returns a dict name -> (sum, norm) of 0-d tensors.  With ssim = (win,
+  sigma) the dict also holds `ssim`, from the kernel `MetricAccumulator.add_ssim`
+  runs (there is no op form of it).
   """
   recons, _, recons_disp = ldi_utils.forward_splat(
       ldi_src, pixel_coords, k_s, k_t, rot, t, compose_layers=True,
@@ -62,7 +64,22 @@ def view_synthesis_metrics(ldi_src, pixel_coords, k_s, k_t, rot, t, imgs_trg,
     out['depth_splat_loss'] = (pd.sum(), centre.sum())
     if disocc_mask is not None:
       out['depth_splat_loss_disocc'] = ((pd * dm).sum(), (centre * dm).sum())
+  if ssim is not None:
+    out['ssim'] = ssim_metric(recons, imgs_trg, opts.splat_bdry_ignore, *ssim)
   return out
+
+
+def ssim_metric(recons, imgs_trg, splat_bdry_ignore, win=11, sigma=1.5):
+  """(sum over the windows of layer 0's SSIM, number of windows) of a rendering
+  nl x B x Ht x Wt x 3 against imgs_trg B x H x W x 3 as 0-d device tensors
+  (lsi_eval_ssim)."""
+  from lsi.nnutils import _hip_eval  # pylint: disable=g-import-not-at-top
+  ht, wt = recons.shape[2:4]
+  acc2 = torch.zeros((2,), dtype=torch.float64, device=recons.device)
+  _hip_eval.ssim_metric(acc2, recons, imgs_trg,
+                        loss_utils._py2_round(wt * splat_bdry_ignore),
+                        loss_utils._py2_round(ht * splat_bdry_ignore), win, sigma)
+  return acc2[0], acc2[1]
 
 
 def aggregate(metric_dicts):
@@ -131,6 +148,7 @@ class MetricAccumulator(object):
     self.acc = torch.zeros((_hip_eval.SLOT_COUNT,), dtype=torch.float64,
                            device=self.device)
     self._ws = None
+    self.acc_ssim = None  # two doubles of their own, made by the first add_ssim
 
   def _workspace(self):
     if self._ws is None:
@@ -139,6 +157,22 @@ class MetricAccumulator(object):
 
   def reset(self):
     self.acc.zero_()
+    if self.acc_ssim is not None:
+      self.acc_ssim.zero_()
+
+  def add_ssim(self, recons, imgs_trg, splat_bdry_ignore, win=11, sigma=1.5):
+    """Adds the SSIM of layer 0 of a rendering (recons nl x B x Ht x Wt x 3)
+    against imgs_trg B x H x W x 3 -- the sum over the win x win windows inside
+    the border crop and their number -- to an accumulator of two doubles beside
+    the 16 (lsi_eval_ssim).  `sums()` and `results()` carry the key `ssim` once
+    this has been called."""
+    _C.require_device(recons, imgs_trg)
+    if self.acc_ssim is None:
+      self.acc_ssim = torch.zeros((2,), dtype=torch.float64, device=self.device)
+    ht, wt = recons.shape[2:4]
+    self._hip.ssim_metric(self.acc_ssim, recons, imgs_trg,
+                          loss_utils._py2_round(wt * splat_bdry_ignore),
+                          loss_utils._py2_round(ht * splat_bdry_ignore), win, sigma)
 
   def add_rendered(self, recons, recons_disp, imgs_trg, splat_bdry_ignore,
                    valid_mask=None, disocc_mask=None, gt_disp_trg=None,
@@ -160,9 +194,10 @@ class MetricAccumulator(object):
 
   def add_view_synthesis(self, ldi_src, pixel_coords, k_s, k_t, rot, t, imgs_trg,
                          opts, valid_mask=None, disocc_mask=None,
-                         gt_disp_trg=None, valid_above=None):
+                         gt_disp_trg=None, valid_above=None, ssim=None):
     """`view_synthesis_metrics` with the arithmetic after the render fused: the
-    same forward_splat call, then `add_rendered`."""
+    same forward_splat call, then `add_rendered` (and, with ssim = (win, sigma),
+    `add_ssim`)."""
     recons, _, recons_disp = ldi_utils.forward_splat(
         ldi_src, pixel_coords, k_s, k_t, rot, t, compose_layers=True,
         compute_trg_disp=True, trg_downsampling=opts.trg_splat_downsampling,
@@ -171,6 +206,8 @@ class MetricAccumulator(object):
     self.add_rendered(recons, recons_disp, imgs_trg, opts.splat_bdry_ignore,
                       valid_mask=valid_mask, disocc_mask=disocc_mask,
                       gt_disp_trg=gt_disp_trg, valid_above=valid_above)
+    if ssim is not None:
+      self.add_ssim(recons, imgs_trg, opts.splat_bdry_ignore, *ssim)
 
   def add_layer_prediction(self, ldi_src, ldi_trg, imgs_src, imgs_trg, gt, opts):
     """`layer_prediction_metrics` in one pass over both views."""
@@ -181,10 +218,14 @@ class MetricAccumulator(object):
                             gt, opts.bg_layer_disp)
 
   def sums(self):
-    """name -> (sum, norm) as Python floats, from ONE device-to-host copy."""
+    """name -> (sum, norm) as Python floats, from ONE device-to-host copy (one
+    more for `ssim` once `add_ssim` has been called)."""
     v = self.acc.tolist()
     slot = self._hip.SLOTS
-    return {k: (v[slot[s]], v[slot[n]]) for k, (s, n) in self._hip.METRICS.items()}
+    out = {k: (v[slot[s]], v[slot[n]]) for k, (s, n) in self._hip.METRICS.items()}
+    if self.acc_ssim is not None:
+      out['ssim'] = tuple(self.acc_ssim.tolist())
+    return out
 
   def results(self):
     """name -> sum / norm for every metric that was scored (norm > 0)."""

@@ -553,6 +553,57 @@ int lsi_eval_ssim(const LsiSsimDesc* desc, const float* recons, const float* tar
                   lsi_stream_t stream);
 
 /*
+ * Edge-aware disparity smoothness loss (csrc/lsi_edge_smooth.hip; no reference
+ * counterpart, the definition is DESIGN.md section 4.14).  disp [L,B,H,W,1]
+ * with the element strides d_s*, guide 3 channels with the element strides
+ * g_s* (g_sl = 0: one image [B,H,W,3] shared by all layers), o = order (1 or
+ * 2), N = H W, p runs over the L B planes.  Stencils on the raw disparity d of a
+ * plane, G its guide:
+ *   order 1   sx[y,x] = d[y,x] - d[y,x+1],              x in [0, W-2]
+ *             ex[y,x] = mean_c |G[y,x,c] - G[y,x+1,c]|
+ *   order 2   sx[y,x] = d[y,x-1] - 2 d[y,x] + d[y,x+1], x in [1, W-2]
+ *             ex[y,x] = 1/2 mean_c |G[y,x+1,c] - G[y,x-1,c]|
+ * sy, ey the same along y.  wx = exp(-alpha ex), wy = exp(-alpha ey),
+ *   A_p = sum |sx| wx,  B_p = sum |sy| wy,  S_p = sum d   (over plane p)
+ *   k_p = 1 / (S_p / N + eps) if normalise, else 1
+ *   loss = 1 / (L B) sum_p k_p [A_p / (H (W-o)) + B_p / ((H-o) W)]
+ * i.e. mean(|sx| wx) + mean(|sy| wy), with normalise of d / (mean_plane(d) +
+ * eps).  The guide is data: the gradient is w.r.t. disp only, sign(0) = 0:
+ *   dloss/dd_i = k_p / (L B) [gx_i / (H (W-o)) + gy_i / ((H-o) W)]
+ *                - [normalise] k_p^2 / (N L B) [A_p / (H (W-o)) + B_p / ((H-o) W)]
+ * where gx_i, gy_i gather sign(s) w over the stencils that touch pixel i with
+ * that stencil's coefficient (+1, -1 at order 1; +1, -2, +1 at order 2).
+ * LSI_EINVAL for an order other than 1 or 2, H or W < order + 1, a negative or
+ * non-finite alpha or non-positive dimensions, then LSI_ENULL, then
+ * LSI_EWORKSPACE, all before any launch.  No atomics, no host synchronisation,
+ * no allocation: the same inputs give the same bits, and both directions can be
+ * captured in a HIP graph.
+ */
+typedef struct LsiEdgeSmoothDesc {
+  int32_t L, B, H, W, order, normalise;
+  int64_t d_sl, d_sb, d_sy, d_sx;
+  int64_t g_sl, g_sb, g_sy, g_sx, g_sc;
+  float alpha, eps;
+} LsiEdgeSmoothDesc;
+
+/* (3 L B bpp + L B) doubles with bpp = min(max(ceil(H W / 1024), 1), 256) blocks
+ * per plane; 0 for a descriptor the entries below refuse. */
+size_t lsi_edge_smooth_workspace_bytes(const LsiEdgeSmoothDesc* desc);
+/* out_loss (one device float) = the loss; plane_sums (3 L B device doubles, the
+ * caller's) = A_p, B_p, S_p at [3 p .. 3 p + 2], p = l B + b: written by the
+ * finishing kernel, read by the backward.  The library keeps no state. */
+int lsi_edge_smooth_loss_fwd(const LsiEdgeSmoothDesc* desc, const float* disp,
+                             const float* guide, float* out_loss,
+                             double* plane_sums, void* workspace,
+                             size_t workspace_bytes, lsi_stream_t stream);
+/* g_disp [L,B,H,W,1] contiguous, scaled by the device scalar g_loss; the
+ * weights are recomputed from the guide.  Every element is written. */
+int lsi_edge_smooth_loss_bwd(const LsiEdgeSmoothDesc* desc, const float* disp,
+                             const float* guide, const double* plane_sums,
+                             const float* g_loss, float* g_disp,
+                             lsi_stream_t stream);
+
+/*
  * layers.compose, lsi/geometry/layers.py:29-70 with helpers.soft_z_buffering
  * (lsi/nnutils/helpers.py:140-160): white background layer at min_disp,
  * per-pixel softmax of log(mask + 1e-8) - depth / temp over the L + 1 layers,

@@ -79,6 +79,20 @@ def build_parser():
   a('--ssim_win', type=int, default=7, help='SSIM window size: odd, 3 .. 11')
   a('--ssim_sigma', type=float, default=1.5,
     help='sigma of the Gaussian SSIM window; <= 0: the box window')
+  a('--edge_smooth_wt', type=float, default=0.0,
+    help='weight of the edge-aware disparity smoothness term (csrc/'
+    'lsi_edge_smooth.hip, DESIGN.md 4.14): edge_smooth_wt * edge_smooth_loss is '
+    'added to the total, divided by max_disp when --edge_smooth_norm is false; '
+    '0 = no such term')
+  a('--edge_smooth_alpha', type=float, default=1.0,
+    help='the weights are exp(-alpha * mean_c |guide gradient|)')
+  a('--edge_smooth_order', type=int, default=1, choices=[1, 2],
+    help='first or second differences of the disparities')
+  a('--edge_smooth_norm', type=_bool, default=True,
+    help="divide every plane's disparities by their mean (scale-free term)")
+  a('--edge_smooth_guide', default='image', choices=['image', 'texture'],
+    help="'image': every layer is guided by the view's input image; 'texture': "
+    'each layer by its own predicted texture, detached')
   a('--zbuf_scale', type=float, default=50)
   a('--trg_splat_downsampling', type=float, default=0.5)
   a('--disp_smoothness_wt', type=float, default=0.1)
@@ -494,6 +508,23 @@ class Trainer(train_utils.Trainer):
       disp_smoothness_loss = sm_s + sm_t
       incr_depth_loss = (dc_s + dc_t) if opts.n_layers > 1 else zero
 
+    # edge-aware smoothness (no reference counterpart)
+    edge_wt = getattr(opts, 'edge_smooth_wt', 0.0)
+    if edge_wt > 0:
+      by_texture = opts.edge_smooth_guide == 'texture'
+
+      def edge_loss(l, imgs):
+        return loss.edge_aware_smoothness_loss(
+            l[2], l[0].detach() if by_texture else imgs,
+            alpha=opts.edge_smooth_alpha, order=opts.edge_smooth_order,
+            normalise=opts.edge_smooth_norm)
+      if paired:
+        edge_smooth_loss = 2.0 * edge_loss(
+            pair, None if by_texture else torch.cat([imgs_src, imgs_trg], dim=0))
+      else:
+        edge_smooth_loss = (edge_loss(ldi_src, imgs_src) +
+                            edge_loss(ldi_trg, imgs_trg))
+
     total = zero
     if opts.self_cons_wt > 0:
       total = total + opts.self_cons_wt * self_cons_loss
@@ -510,6 +541,10 @@ class Trainer(train_utils.Trainer):
     if opts.disp_smoothness_wt > 0:
       total = total + (opts.disp_smoothness_wt /
                        (opts.max_disp * opts.max_disp)) * disp_smoothness_loss
+    if edge_wt > 0:
+      # normalised, the term is scale-free; else both orders are linear in d
+      total = total + (edge_wt if opts.edge_smooth_norm
+                       else edge_wt / opts.max_disp) * edge_smooth_loss
     scalars = {
         'self_cons_loss': self_cons_loss,
         'compose_splat_loss': compose_splat_loss,
@@ -521,6 +556,8 @@ class Trainer(train_utils.Trainer):
     if ssim_wt > 0:
       scalars['compose_ssim_loss'] = compose_ssim_loss
       scalars['indep_ssim_loss'] = indep_ssim_loss
+    if edge_wt > 0:
+      scalars['edge_smooth_loss'] = edge_smooth_loss
     return total, scalars
 
 

@@ -74,6 +74,14 @@ class LsiSsimDesc(ctypes.Structure):
       [(n, ctypes.c_int64) for n in ('t_sb', 't_sy', 't_sx', 't_sc')])
 
 
+class LsiEdgeSmoothDesc(ctypes.Structure):
+  _fields_ = (
+      [(n, ctypes.c_int32) for n in ('L', 'B', 'H', 'W', 'order', 'normalise')] +
+      [(n, ctypes.c_int64) for n in ('d_sl', 'd_sb', 'd_sy', 'd_sx',
+                                     'g_sl', 'g_sb', 'g_sy', 'g_sx', 'g_sc')] +
+      [(n, ctypes.c_float) for n in ('alpha', 'eps')])
+
+
 class LsiConvDesc(ctypes.Structure):
   _fields_ = [(n, ctypes.c_int32) for n in (
       'N', 'H', 'W', 'Cin', 'OH', 'OW', 'Cout', 'KH', 'KW', 'stride', 'pad_t', 'pad_l')]
@@ -164,6 +172,11 @@ SIGNATURES = {
     'lsi_ssim_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiSsimDesc)] + [_VP] * 5),
     'lsi_eval_ssim': (ctypes.c_int, [ctypes.POINTER(LsiSsimDesc)] + [_VP] * 4 +
                       [_SZ, _VP]),
+    'lsi_edge_smooth_workspace_bytes': (_SZ, [ctypes.POINTER(LsiEdgeSmoothDesc)]),
+    'lsi_edge_smooth_loss_fwd': (ctypes.c_int, [ctypes.POINTER(LsiEdgeSmoothDesc)] +
+                                 [_VP] * 5 + [_SZ, _VP]),
+    'lsi_edge_smooth_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiEdgeSmoothDesc)] +
+                                 [_VP] * 6),
     'lsi_compose_fwd': (ctypes.c_int, [_I32, _I64, _I32] + [_VP] * 3 +
                         [_I32, _F32, _F32, _VP, _VP]),
     'lsi_compose_depth_fwd': (ctypes.c_int, [_I32, _I64] + [_VP] * 2 +

@@ -247,6 +247,91 @@ def ssim_window(win, sigma):
   return list(out)
 
 
+# launches of the edge-aware smoothness kernels through this binding
+CALLS.update({'edge_fwd': 0, 'edge_bwd': 0})
+EDGE_EPS = 1e-7
+
+
+def edge_smooth_desc(disp, guide, alpha, order, normalise, what):
+  """The LsiEdgeSmoothDesc of disp L x B x H x W x 1 guided by B x H x W x 3 (all
+  layers) or L x B x H x W x 3 (per layer); ValueError for what the kernels would
+  refuse with LSI_EINVAL and for a guide of another shape."""
+  if disp.dim() != 5 or disp.shape[4] != 1:
+    raise ValueError('%s: disparities L x B x H x W x 1 (got %s)' %
+                     (what, tuple(disp.shape)))
+  nl, b, h, w, _ = disp.shape
+  if tuple(guide.shape) == (b, h, w, 3):
+    g_sl, (g_sb, g_sy, g_sx, g_sc) = 0, guide.stride()
+  elif tuple(guide.shape) == (nl, b, h, w, 3):
+    g_sl, g_sb, g_sy, g_sx, g_sc = guide.stride()
+  else:
+    raise ValueError('%s: the guide is %s or %s, 3 channels (got %s)' %
+                     (what, (b, h, w, 3), (nl, b, h, w, 3), tuple(guide.shape)))
+  if order not in (1, 2):
+    raise ValueError('%s: the order is 1 or 2 (got %r)' % (what, order))
+  if min(nl, b) < 1 or h < order + 1 or w < order + 1:
+    raise ValueError('%s: order %d needs at least %d rows and columns (got %d x '
+                     '%d)' % (what, order, order + 1, h, w))
+  alpha = float(alpha)
+  if not (alpha >= 0.0 and alpha != float('inf')):
+    raise ValueError('%s: alpha is finite and >= 0 (got %r)' % (what, alpha))
+  d = _C.LsiEdgeSmoothDesc()
+  d.L, d.B, d.H, d.W, d.order, d.normalise = nl, b, h, w, order, int(bool(normalise))
+  d.d_sl, d.d_sb, d.d_sy, d.d_sx = disp.stride()[:4]
+  d.g_sl, d.g_sb, d.g_sy, d.g_sx, d.g_sc = g_sl, g_sb, g_sy, g_sx, g_sc
+  d.alpha, d.eps = alpha, EDGE_EPS
+  return d
+
+
+class _EdgeSmooth(torch.autograd.Function):
+  """lsi_edge_smooth_loss_fwd / _bwd."""
+
+  @staticmethod
+  def forward(ctx, disp, guide, alpha, order, normalise):
+    dev = _C.require_device(disp, guide)
+    d = edge_smooth_desc(disp, guide, alpha, order, normalise,
+                         'edge_smoothness_loss')
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    sums = torch.empty((3 * d.L * d.B,), dtype=torch.float64, device=dev)
+    n = int(_C.lib().lsi_edge_smooth_workspace_bytes(ctypes.byref(d)))
+    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+    CALLS['edge_fwd'] += 1
+    rc = _C.lib().lsi_edge_smooth_loss_fwd(ctypes.byref(d), _C.ptr(disp),
+                                           _C.ptr(guide), _C.ptr(out),
+                                           _C.ptr(sums), _C.ptr(ws), n,
+                                           _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_edge_smooth_loss_fwd')
+    ctx.save_for_backward(disp, guide, sums)
+    ctx.desc = d
+    return out
+
+  @staticmethod
+  def backward(ctx, g):
+    disp, guide, sums = ctx.saved_tensors
+    dev = disp.device
+    g = g.contiguous().float()
+    g_disp = torch.empty(tuple(disp.shape), dtype=torch.float32, device=dev)
+    CALLS['edge_bwd'] += 1
+    rc = _C.lib().lsi_edge_smooth_loss_bwd(ctypes.byref(ctx.desc), _C.ptr(disp),
+                                           _C.ptr(guide), _C.ptr(sums), _C.ptr(g),
+                                           _C.ptr(g_disp), _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_edge_smooth_loss_bwd')
+    return g_disp, None, None, None, None
+
+
+def edge_smoothness_loss(disp, guide, alpha, order, normalise):
+  """Edge-aware smoothness of disp L x B x H x W x 1 (any strides) under guide
+  B x H x W x 3 or L x B x H x W x 3; the gradient is w.r.t. disp only."""
+  # the guide is data, as the target of zbuffer_composition_loss
+  if torch.is_tensor(guide) and guide.requires_grad:
+    raise RuntimeError('edge_smoothness_loss: the guide is not differentiable '
+                       'on the HIP path (pass guide.detach())')
+  if isinstance(order, bool) or int(order) != order:
+    raise ValueError('edge_smoothness_loss: the order is 1 or 2 (got %r)' % (order,))
+  return _EdgeSmooth.apply(_f32(disp), _f32(guide), float(alpha), int(order),
+                           bool(normalise))
+
+
 class _Compose(torch.autograd.Function):
   """lsi_compose_fwd / lsi_compose_bwd on imgs [L,N,C], masks [L,N], dmaps
   [L,N] (contiguous fp32)."""

@@ -86,3 +86,17 @@ def ssim_view_synthesis_loss(recons_splat, to_recons_img, splat_bdry_ignore=0.05
                                        _py2_round(wt * splat_bdry_ignore),
                                        _py2_round(ht * splat_bdry_ignore), win,
                                        sigma)
+
+
+def edge_aware_smoothness_loss(pred_disp, guide_imgs, alpha=1.0, order=1,
+                               normalise=True):
+  """Edge-aware disparity smoothness (the reference has none):
+  mean |d_x d| exp(-alpha mean_c |d_x G|) + the same along y, with first
+  (order 1) or second (order 2) differences of the disparities pred_disp
+  L x B x H x W x 1 and matching differences of the guide images, B x H x W x 3
+  for all layers or L x B x H x W x 3 per layer.  normalise: every plane's
+  disparities are divided by their mean (+ 1e-7), which makes the term
+  independent of the disparity scale.  One fused HIP launch each way
+  (lsi_edge_smooth_loss_fwd / _bwd); the gradient is w.r.t. pred_disp only."""
+  from lsi.loss import _hip  # pylint: disable=g-import-not-at-top
+  return _hip.edge_smoothness_loss(pred_disp, guide_imgs, alpha, order, normalise)

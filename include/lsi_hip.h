@@ -1221,7 +1221,8 @@ int lsi_conv2d_wgrad_f32(const LsiConvDesc* d, const void* x1, const void* x2, i
  *   dx (may be NULL): dX[M][K] = dZ . W in x's type.
  *
  * workspace: lsi_fc_workspace_bytes(d) bytes (forward and backward; 0 for a
- * descriptor lsi_fc_supported(d) refuses), 16-byte aligned, the caller's; no
+ * descriptor lsi_fc_supported(d) refuses; LSI_EWORKSPACE from either entry if
+ * smaller, before any launch), 16-byte aligned, the caller's; no
  * state survives a call.  x, dy, workspace 16-byte aligned (LSI_EINVAL).
  * lsi_fc_desc_bytes(): sizeof(LsiFcDesc) as the library was built.
  */

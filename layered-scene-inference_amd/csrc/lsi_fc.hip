@@ -502,7 +502,7 @@ extern "C" int lsi_fc_fwd(const LsiFcDesc* d, const void* x, const float* w, con
   const bool bn = d->flags & LSI_FC_BN;
   if (!x || !w || !y || !workspace || (bn && (!beta || !mean_rstd))) return LSI_ENULL;
   if (((uintptr_t)x & 15) || ((uintptr_t)workspace & 15)) return LSI_EINVAL;
-  if (workspace_bytes < fwd_bytes(d)) return LSI_EWORKSPACE;
+  if (workspace_bytes < lsi_fc_workspace_bytes(d)) return LSI_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream_;
   float* part = static_cast<float*>(workspace);
   const int splits = launch_stream(d, x, (d->flags & LSI_FC_X_F32) ? 1 : 0, w, part, true, st);
@@ -534,7 +534,7 @@ extern "C" int lsi_fc_bwd(const LsiFcDesc* d, const void* x, const float* w, con
   if (bn && (!y || !z || !mean_rstd || !dbeta)) return LSI_ENULL;
   if (((uintptr_t)x & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)dy & 15))
     return LSI_EINVAL;
-  if (workspace_bytes < bwd_bytes(d)) return LSI_EWORKSPACE;
+  if (workspace_bytes < lsi_fc_workspace_bytes(d)) return LSI_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream_;
   const int io_f32 = (d->flags & LSI_FC_OUT_F32) ? 1 : 0;
   const int x_f32 = (d->flags & LSI_FC_X_F32) ? 1 : 0;

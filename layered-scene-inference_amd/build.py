@@ -28,6 +28,7 @@ HEADERS = [os.path.join(CSRC, 'lsi_common.h'),
            os.path.join(CSRC, 'lsi_splat_internal.h'),
            os.path.join(CSRC, 'lsi_bn_ws.h'),
            os.path.join(CSRC, 'lsi_conv_host.h'),
+           os.path.join(CSRC, 'lsi_conv_device.h'),
            os.path.join(ROOT, 'include', 'lsi_hip.h')]
 
 HIPCC_FLAGS = [

@@ -18,6 +18,12 @@
 
 #pragma clang fp contract(off)
 
+// (host, lsi_host.hip; for every family's launchers)
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) only when this (device,
+// kernel) has not been granted `bytes` yet: an eager caller launches the same
+// kernel with the same plan thousands of times (lsi_splat.hip).
+int lsi_ensure_dynamic_lds(const void* fn, size_t bytes);
+
 namespace lsi {
 
 // helpers.py:82-85

@@ -34,13 +34,12 @@
 #include <stdint.h>
 
 #include "../../include/lsi_hip.h"
+#include "lsi_conv_device.h"
+#include "lsi_conv_host.h"
+
+using namespace lsi;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CV_ROWS = 32;  // output rows per wave (row chunk)
 
@@ -253,12 +252,6 @@ __global__ __launch_bounds__(256) void pred_bwd_data_kernel(PredBwdArgs a) {
 int launch_rc() { return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH; }
 
 }  // namespace
-
-// (lsi_conv_wgrad.hip)
-size_t lsi_pred_wgrad_workspace_bytes(int N, int H, int W, int cout);
-int lsi_pred_wgrad_launch(int N, int H, int W, int cout, const float* g, const float* y,
-                          const void* x, float* g_wb, void* workspace, size_t workspace_bytes,
-                          hipStream_t stream);
 
 extern "C" int lsi_conv3x3_c32_fwd(int32_t N, int32_t H, int32_t W, int32_t cout,
                                    int32_t mode, const void* x, const float* weight,

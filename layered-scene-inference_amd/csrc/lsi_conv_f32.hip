@@ -32,13 +32,13 @@
 #include <string.h>
 
 #include "../../include/lsi_hip.h"
+#include "lsi_common.h"
+#include "lsi_conv_device.h"
 #include "lsi_conv_host.h"
-#include "lsi_splat_internal.h"
+
+using namespace lsi;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int F_MAXTAPS = 49;
 constexpr int F_PIX = 144;   // bytes per staged pixel / weight row (128 + 16 of padding)
@@ -279,71 +279,16 @@ __global__ __launch_bounds__(256) void conv_f32_fold_kernel(FFoldArgs a) {
   }
 }
 
-// Weights into the kernel's operand order, fp32: dst[t][o][i] = W[o][i][ky_t][kx_t]
-// (tr & 1 == 0) or W[i][o][ky_t][kx_t] (tr & 1: the data gradients); tr & 2: the
-// parameter has torch's channels-last strides.  32 x 32 tiles of (d0, d1)
-// through LDS (D0, D1 multiples of 16: the edge tiles are guarded).
-constexpr int FPACK_TC = 8;
-__device__ __forceinline__ void fpack_tile(const LsiPackJob& a, int bx, int by,
-                                           float (*tile)[32][33]) {
-  const int a0 = by * 32, b0 = bx * 32;
-  const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
-  const size_t per = (size_t)a.D0 * a.D1;
-  float* const dst = reinterpret_cast<float*>(a.dst);
-  for (int t0 = 0; t0 < a.ntaps; t0 += FPACK_TC) {
-    float v[FPACK_TC][4];
-#pragma unroll
-    for (int tt = 0; tt < FPACK_TC; ++tt) {
-      const int tap = a.tap[min(t0 + tt, a.ntaps - 1)];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = r0 + 8 * j;
-        v[tt][j] = 0.f;
-        if (a0 + r < a.D0 && b0 + c < a.D1)
-          v[tt][j] = (a.tr & 2) ? a.w[((size_t)(a0 + r) * a.khw + tap) * a.D1 + b0 + c]
-                                : a.w[((size_t)(a0 + r) * a.D1 + b0 + c) * a.khw + tap];
-      }
-    }
-#pragma unroll
-    for (int tt = 0; tt < FPACK_TC; ++tt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tile[tt][r0 + 8 * j][c] = v[tt][j];
-    __syncthreads();
-#pragma unroll
-    for (int tt = 0; tt < FPACK_TC; ++tt) {
-      const int t = t0 + tt;
-      if (t < a.ntaps) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int r = r0 + 8 * j;
-          if (a.tr & 1) {   // dst[t][d1][d0]
-            if (b0 + r < a.D1 && a0 + c < a.D0)
-              dst[(size_t)t * per + (size_t)(b0 + r) * a.D0 + a0 + c] = tile[tt][c][r];
-          } else if (a0 + r < a.D0 && b0 + c < a.D1) {   // dst[t][d0][d1]
-            dst[(size_t)t * per + (size_t)(a0 + r) * a.D1 + b0 + c] = tile[tt][r][c];
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
+// The weights in the kernel's operand order, fp32 (lsi_conv_device.h's pack; D0,
+// D1 multiples of 16: the edge tiles are guarded).
 __global__ __launch_bounds__(256) void conv_f32_pack_kernel(LsiPackJob a) {
-  __shared__ float tile[FPACK_TC][32][33];
-  fpack_tile(a, blockIdx.x, blockIdx.y, tile);
+  __shared__ float tile[PACK_TC][32][33];
+  pack_tile<float, true>(a, blockIdx.x, blockIdx.y, tile);   // block (x, y) = tile (d1, d0) / 32
 }
 __global__ __launch_bounds__(256) void conv_f32_pack_many_kernel(const LsiPackJob* jobs, int njobs) {
-  __shared__ float tile[FPACK_TC][32][33];
+  __shared__ float tile[PACK_TC][32][33];
   __shared__ int which;
-  if (threadIdx.x == 0) {
-    int j = 0;
-    while (j + 1 < njobs && (int)blockIdx.x >= jobs[j + 1].block0) ++j;
-    which = j;
-  }
-  __syncthreads();
-  const LsiPackJob& a = jobs[which];   // (read in place: no private copy of the tap table)
-  const int lb = (int)blockIdx.x - a.block0, nbx = (a.D1 + 31) / 32;
-  fpack_tile(a, lb % nbx, lb / nbx, tile);
+  pack_job_tile<float, true>(jobs, njobs, tile, &which);
 }
 
 // Tile shape: the tallest row block (<= 4 rows per wave) whose patch and one

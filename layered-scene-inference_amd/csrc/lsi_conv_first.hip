@@ -38,15 +38,12 @@
 
 #include "../../include/lsi_hip.h"
 #include "lsi_bn_ws.h"
-#include "lsi_splat_internal.h"
+#include "lsi_common.h"
+#include "lsi_conv_device.h"
+
+using namespace lsi;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int KH = 7, KW = 7, ST = 2;       // the one geometry the networks have
 constexpr int F_TH = 8, F_TW = 64;          // forward tile: output rows x columns
@@ -67,14 +64,6 @@ struct FirstArgs {
 
 __device__ __forceinline__ unsigned short bf16_bits(float f) {
   return __builtin_bit_cast(unsigned short, (__bf16)f);
-}
-
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xb1, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4e, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));
-  return v;
 }
 
 // One input pixel's channels as 4 bf16 (zero outside the image / past Cin).
@@ -154,53 +143,12 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(FirstArgs a) {
   }
   const int j = j0 + 16 * wave + pxl;
   if (a.st_ws) {
-    // batch-norm sums of the ROUNDED outputs (lsi_conv_igemm.hip's protocol)
-    float ss[2][4], qq[2][4];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { ss[c][e] = 0.f; qq[c][e] = 0.f; }
-#pragma unroll
-    for (int r = 0; r < F_TH; ++r) {
-      if (j < a.OW && i0 + r < a.OH) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float v = (float)(__bf16)acc[r][c][e];
-            ss[c][e] += v;
-            qq[c][e] = __builtin_fmaf(v, v, qq[c][e]);
-          }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { ss[c][e] = row16_sum(ss[c][e]); qq[c][e] = row16_sum(qq[c][e]); }
-    if (pxl == 0) {
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          red[(wave * 2 + 0) * 32 + 16 * c + 4 * kg + e] = ss[c][e];
-          red[(wave * 2 + 1) * 32 + 16 * c + 4 * kg + e] = qq[c][e];
-        }
-    }
-    __syncthreads();
+    // batch-norm sums of the ROUNDED outputs (red is this epilogue's alone: no
+    // barrier in front of it)
     const int per_grp = a.N / a.st_groups, grp = n / per_grp;
-    if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0 && n == grp * per_grp)
-      __hip_atomic_store(reinterpret_cast<int*>(a.st_ws + (size_t)grp * LSI_BN_WS_STRIDE) +
-                             LSI_BN_WS_TAG,
-                         LSI_BN_TAG(32, a.st_groups), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < 64) {
-      const int q = tid >> 5, ch = tid & 31;
-      const float v = (red[(0 * 2 + q) * 32 + ch] + red[(1 * 2 + q) * 32 + ch]) +
-                      (red[(2 * 2 + q) * 32 + ch] + red[(3 * 2 + q) * 32 + ch]);
-      const int f = (int)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
-      __hip_atomic_fetch_add(a.st_ws + (size_t)grp * LSI_BN_WS_STRIDE + LSI_BN_WS_ACC +
-                                 (f % a.st_ns) * 2 * 32 + q * 32 + ch,
-                             v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    bn_stats_epilogue<F_TH, 2>(
+        acc, [&](int r) { return j < a.OW && i0 + r < a.OH; }, red, a.st_ws, grp, a.st_groups,
+        a.st_ns, 32, 0, blockIdx.x == 0 && blockIdx.y == 0 && n == grp * per_grp);
   }
   if (j < a.OW) {
 #pragma unroll
@@ -350,36 +298,23 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(FirstGwArgs a) {
 }
 
 // gW[co][c][ky][kx] = sum over the partials of [ky][4 kx + c][co], in a fixed order.
-// Block = 64 entries x 16 groups of partials (group y sums partials y, y + 16,
-// ... four at a time, the 16 group sums are added in order through LDS): 112
-// workgroups of 8 - 32 rounds of loads.  (One thread per entry walking all the
-// partials was 28 workgroups x ~128 dependent rounds: 44 us for a 4704-float
-// gradient.)
+// Block = 64 entries x 16 groups of partials (lsi_conv_device.h's fold: group y
+// sums partials y, y + 16, ... four at a time, the 16 group sums are added in
+// order through LDS): 112 workgroups of 8 - 32 rounds of loads.  (One thread
+// per entry walking all the partials was 28 workgroups x ~128 dependent rounds:
+// 44 us for a 4704-float gradient.)
 __global__ __launch_bounds__(1024) void conv_first_wgrad_fold_kernel(
     const float* __restrict__ part, int nparts, float* __restrict__ gw, int cin, long wsco,
     long wsc, long wsky, long wskx) {
   __shared__ float red[16][64];
   const int idx = blockIdx.x * 64 + threadIdx.x, y = threadIdx.y;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (idx < G_NACC) {
-    int b = y;
-    for (; b + 48 < nparts; b += 64) {
-      s0 += part[(size_t)(b + 0) * G_NACC + idx];
-      s1 += part[(size_t)(b + 16) * G_NACC + idx];
-      s2 += part[(size_t)(b + 32) * G_NACC + idx];
-      s3 += part[(size_t)(b + 48) * G_NACC + idx];
-    }
-    for (; b < nparts; b += 16) s0 += part[(size_t)b * G_NACC + idx];
-  }
-  red[y][threadIdx.x] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  if (idx < G_NACC) part_fold_sums(part, nparts, (size_t)G_NACC, idx, y, s);
+  const float v = part_fold_groups(red, y, threadIdx.x, (s[0] + s[1]) + (s[2] + s[3]));
   if (y != 0 || idx >= G_NACC) return;
   const int co = idx & 31, nn = (idx >> 5) & 31, ky = idx >> 10;
   const int kx = nn >> 2, c = nn & 3;
   if (kx >= KW || c >= cin) return;
-  float v = 0.f;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) v += red[k][threadIdx.x];
   gw[co * wsco + c * wsc + ky * wsky + kx * wskx] = v;
 }
 

@@ -1,7 +1,8 @@
 // Host code that the bf16 (lsi_conv_igemm.hip, lsi_conv_wgrad_igemm.hip) and the
 // fp32 (lsi_conv_f32.hip) implicit-GEMM convolutions share: the descriptor
 // check, the tap lists, the launch plan and its split over the input channels,
-// the pack job, the weight gradient's tap table and pixel blocks.  Host only;
+// the pack job, the weight gradient's tap table and pixel blocks, and the
+// declarations of the family's internal cross-file functions.  Host only;
 // templates over the kernels' argument structs (IgArgs / FArgs, GwArgs /
 // FwArgs), whose layouts belong to the kernels and stay where they are.  Where
 // the two precisions answer differently (a return code, a byte count), the
@@ -234,5 +235,12 @@ long conv_wgrad_ps(const LsiConvDesc* d, Args& k, int th, long chan_wgs, size_t 
 // precision of the convolution.
 int lsi_conv_wgrad_fold(const float* part, int nblk, const LsiConvDesc* d, float* g_weight,
                         int cl, hipStream_t stream);
+
+// The prediction head's weight + bias gradient (lsi_conv_wgrad.hip; called by
+// lsi_conv3x3_pred_bwd, lsi_conv.hip): g_wb = [cout * 288 + cout], written.
+size_t lsi_pred_wgrad_workspace_bytes(int N, int H, int W, int cout);
+int lsi_pred_wgrad_launch(int N, int H, int W, int cout, const float* g, const float* y,
+                          const void* x, float* g_wb, void* workspace, size_t workspace_bytes,
+                          hipStream_t stream);
 
 #endif  // LSI_CONV_HOST_H_

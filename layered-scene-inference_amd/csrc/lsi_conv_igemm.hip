@@ -43,15 +43,13 @@
 
 #include "../../include/lsi_hip.h"
 #include "lsi_bn_ws.h"
+#include "lsi_common.h"
+#include "lsi_conv_device.h"
 #include "lsi_conv_host.h"
-#include "lsi_splat_internal.h"
+
+using namespace lsi;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int IG_MAXTAPS = 49;
 constexpr int IG_PIX = 80;  // bytes per staged pixel / weight row (64 + 16 of padding)
@@ -116,15 +114,6 @@ struct IgArgs {
   int swz;   // XCD-aware workgroup order (see the kernel's index decode)
   IgClass cls[4];
 };
-
-// sum over the 16 lanes of a DPP row (every lane gets it)
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xb1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4e, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));  // row_half_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));  // row_mirror
-  return v;
-}
 
 // RW: pixel rows per wave; NCT: tiles of 16 output channels (BN = 16 NCT); G:
 // taps per weight stage -- a compile-time count, so that a stage is straight-
@@ -308,59 +297,13 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(IgArgs a) {
   }
   if (a.st_ws) {
     // ---- batch-norm statistics of this tile (see IgArgs) -----------------------
-    float ss[NCT][4], qq[NCT][4];
-#pragma unroll
-    for (int c = 0; c < NCT; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { ss[c][e] = 0.f; qq[c][e] = 0.f; }
-#pragma unroll
-    for (int r = 0; r < RW; ++r) {
-      const int i = i0 + wave * RW + r;
-      if (j < k.OWt && i < k.OHt) {
-#pragma unroll
-        for (int c = 0; c < NCT; ++c)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float v = (float)(__bf16)acc[r][c][e];
-            ss[c][e] += v;
-            qq[c][e] = __builtin_fmaf(v, v, qq[c][e]);
-          }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < NCT; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { ss[c][e] = row16_sum(ss[c][e]); qq[c][e] = row16_sum(qq[c][e]); }
-    __syncthreads();  // (the last unit's fragments have been read)
-    float* const red = reinterpret_cast<float*>(ig_smem);   // [4 waves][2][BN]
-    if (pxl == 0) {
-#pragma unroll
-      for (int c = 0; c < NCT; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          red[(wave * 2 + 0) * BN + 16 * c + 4 * kg + e] = ss[c][e];
-          red[(wave * 2 + 1) * BN + 16 * c + 4 * kg + e] = qq[c][e];
-        }
-    }
-    __syncthreads();
-    const int C = a.Cout;
+    __syncthreads();  // (the last unit's fragments have been read: red is the staging memory)
     const int per_grp = a.N / a.st_groups, grp = n / per_grp;
-    // (the hand-over tag of the group, by the workgroup of its first tile: see
-    // lsi_splat_internal.h)
-    if (tid == 0 && bx == 0 && by == 0 && co0 == 0 && ci_ == 0 &&
-        n == grp * per_grp)
-      __hip_atomic_store(reinterpret_cast<int*>(a.st_ws + (size_t)grp * LSI_BN_WS_STRIDE) +
-                             LSI_BN_WS_TAG,
-                         LSI_BN_TAG(C, a.st_groups), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < 2 * BN) {
-      const int q = tid / BN, ch = tid - q * BN;
-      const float v = (red[(0 * 2 + q) * BN + ch] + red[(1 * 2 + q) * BN + ch]) +
-                      (red[(2 * 2 + q) * BN + ch] + red[(3 * 2 + q) * BN + ch]);
-      const int f = (int)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
-      __hip_atomic_fetch_add(a.st_ws + (size_t)grp * LSI_BN_WS_STRIDE + LSI_BN_WS_ACC +
-                                 (f % a.st_ns) * 2 * C + q * C + co0 + ch,
-                             v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    // (the hand-over tag of the group, lsi_bn_ws.h, by the workgroup of its first tile)
+    bn_stats_epilogue<RW, NCT>(
+        acc, [&](int r) { return j < k.OWt && i0 + wave * RW + r < k.OHt; },
+        reinterpret_cast<float*>(ig_smem), a.st_ws, grp, a.st_groups, a.st_ns, a.Cout, co0,
+        bx == 0 && by == 0 && co0 == 0 && ci_ == 0 && n == grp * per_grp);
   }
   if (j < k.OWt) {
 #pragma unroll
@@ -435,95 +378,28 @@ __global__ __launch_bounds__(256) void conv_splitk_fold_kernel(FoldArgs a) {
   const int per_grp = a.N / a.st_groups, grp = n / per_grp;
   const int tid = ty * 64 + tx;
   if (tid == 0 && blockIdx.y == 0 && pbk == 0 && n == grp * per_grp)
-    __hip_atomic_store(reinterpret_cast<int*>(a.st_ws + (size_t)grp * LSI_BN_WS_STRIDE) +
-                           LSI_BN_WS_TAG,
-                       LSI_BN_TAG(C, a.st_groups), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bn_stats_tag(a.st_ws, grp, C, a.st_groups);
   for (int t = tid; t < 512; t += 256) {
     const int q = t >> 8, ch = t & 255;
     const int cc = (int)blockIdx.y * 256 + ch;
     if (cc < C) {
       const float v = (red[0][q][ch] + red[1][q][ch]) + (red[2][q][ch] + red[3][q][ch]);
       const int f = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-      __hip_atomic_fetch_add(a.st_ws + (size_t)grp * LSI_BN_WS_STRIDE + LSI_BN_WS_ACC +
-                                 (f % a.st_ns) * 2 * C + q * C + cc,
-                             v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      bn_stats_add(a.st_ws, grp, f, a.st_ns, C, q, cc, v);
     }
   }
 }
 
-// Weights into the kernel's operand order: dst[t][o][i] = W[o][i][ky_t][kx_t]
-// (tr = 0) or W[i][o][ky_t][kx_t] (tr = 1: the data gradients), rounded to bf16
-// as torch.autocast rounds them.  W is the layer's fp32 parameter
-// D0 x D1 x KH x KW (both multiples of 32).  A workgroup moves a 32 x 32 tile of
-// (d0, d1) per tap through LDS, so that reads and (transposed) writes are both
-// contiguous runs.
-typedef LsiPackJob PackArgs;   // {w, dst, D0, D1, khw, tr, ntaps, block0, tap[]}
-// PACK_TC taps per round: their 4 x PACK_TC loads per thread are in flight
-// together and a round costs one pair of barriers (one tap per round was 338 us
-// for the 36 M parameters x 2 directions of the networks: a chain of load
-// latencies; the trainer packs after every optimiser step).
-constexpr int PACK_TC = 8;
-__device__ __forceinline__ void pack_tile(const PackArgs& a, int bx, int by,
-                                          float (*tile)[32][33]) {
-  const int a0 = by * 32, b0 = bx * 32;
-  const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
-  const size_t per = (size_t)a.D0 * a.D1;
-  __bf16* const dst = reinterpret_cast<__bf16*>(a.dst);
-  for (int t0 = 0; t0 < a.ntaps; t0 += PACK_TC) {
-    float v[PACK_TC][4];
-#pragma unroll
-    for (int tt = 0; tt < PACK_TC; ++tt) {
-      const int tap = a.tap[min(t0 + tt, a.ntaps - 1)];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = r0 + 8 * j;
-        // (the parameter D0 x D1 x KH x KW as torch stores it: contiguous, or --
-        // tr & 2 -- channels-last strides, D0 x KH x KW x D1 in memory: what
-        // module.to(memory_format=torch.channels_last) leaves)
-        v[tt][j] = (a.tr & 2) ? a.w[((size_t)(a0 + r) * a.khw + tap) * a.D1 + b0 + c]
-                              : a.w[((size_t)(a0 + r) * a.D1 + b0 + c) * a.khw + tap];
-      }
-    }
-#pragma unroll
-    for (int tt = 0; tt < PACK_TC; ++tt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tile[tt][r0 + 8 * j][c] = v[tt][j];
-    __syncthreads();
-#pragma unroll
-    for (int tt = 0; tt < PACK_TC; ++tt) {
-      const int t = t0 + tt;
-      if (t < a.ntaps) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int r = r0 + 8 * j;
-          if (a.tr & 1)   // dst[t][d1][d0]
-            dst[(size_t)t * per + (size_t)(b0 + r) * a.D0 + a0 + c] = (__bf16)tile[tt][c][r];
-          else        // dst[t][d0][d1]
-            dst[(size_t)t * per + (size_t)(a0 + r) * a.D1 + b0 + c] = (__bf16)tile[tt][r][c];
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-__global__ __launch_bounds__(256) void conv_pack_kernel(PackArgs a) {
+// The weights in the kernel's operand order, rounded to bf16 (lsi_conv_device.h's
+// pack; D0, D1 multiples of 32: no edge tiles).
+__global__ __launch_bounds__(256) void conv_pack_kernel(LsiPackJob a) {
   __shared__ float tile[PACK_TC][32][33];
-  pack_tile(a, blockIdx.x, blockIdx.y, tile);
+  pack_tile<__bf16, false>(a, blockIdx.x, blockIdx.y, tile);   // block (x, y) = tile (d1, d0) / 32
 }
-// Many layers in one launch: job j owns blocks [block0_j, block0_{j+1}) (the
-// table lives in device memory; the last entry's block0 + its blocks = grid).
-__global__ __launch_bounds__(256) void conv_pack_many_kernel(const PackArgs* jobs, int njobs) {
+__global__ __launch_bounds__(256) void conv_pack_many_kernel(const LsiPackJob* jobs, int njobs) {
   __shared__ float tile[PACK_TC][32][33];
   __shared__ int which;
-  if (threadIdx.x == 0) {
-    int j = 0;
-    while (j + 1 < njobs && (int)blockIdx.x >= jobs[j + 1].block0) ++j;
-    which = j;
-  }
-  __syncthreads();
-  const PackArgs a = jobs[which];
-  const int lb = (int)blockIdx.x - a.block0, nbx = a.D1 / 32;
-  pack_tile(a, lb % nbx, lb / nbx, tile);
+  pack_job_tile<__bf16, false>(jobs, njobs, tile, &which);
 }
 
 constexpr size_t IG_LDS_CAP = 80 * 1024;  // two workgroups per CU

@@ -45,15 +45,12 @@
 #include <stdint.h>
 
 #include "../../include/lsi_hip.h"
+#include "lsi_conv_device.h"
+#include "lsi_conv_host.h"
+
+using namespace lsi;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 #ifndef LSI_WG_ROWS
 #define LSI_WG_ROWS 32
@@ -76,17 +73,6 @@ struct WgradArgs {
 
 // elements per pixel in LDS: the channels, padded to an odd multiple of 32 bytes
 constexpr int padded(int ch) { return ((ch * 2 / 32) % 2 == 0) ? ch + 16 : ch; }
-
-// The fragment of 16 channels x 32 pixels whose first pixel / channel `p`
-// points at: lane (t = lane % 16, g = lane / 16) gets channel t of its 8 pixels.
-template <int STRIDE>
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16* p, int t, int g) {
-  const __bf16* q = p + (16 * (g >> 1) + 4 * (g & 1) + (t >> 2)) * STRIDE + 4 * (t & 3);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)q);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(q + 8 * STRIDE));
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 // CO16: Cout / 16; NW: waves; SW: strip width (pixels, a multiple of 32).
 // A workgroup takes 32 input channels (two tiles): blockIdx.y, and 16 CO16
@@ -302,27 +288,10 @@ __global__ __launch_bounds__(1024) void conv_wgrad_reduce_kernel(const float* pa
                                                                  int nout, float* out) {
   __shared__ float red[16][64];
   const int o = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
-  float s = 0.0f;
-  if (o < nout) {
-    float s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    int w = grp;
-    for (; w + 48 < nblk; w += 64) {  // four loads in flight
-      s += part[(size_t)w * nout + o];
-      s1 += part[(size_t)(w + 16) * nout + o];
-      s2 += part[(size_t)(w + 32) * nout + o];
-      s3 += part[(size_t)(w + 48) * nout + o];
-    }
-    for (; w < nblk; w += 16) s += part[(size_t)w * nout + o];
-    s += s1 + s2 + s3;
-  }
-  red[grp][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (grp == 0 && o < nout) {
-    float v = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v += red[k][threadIdx.x];
-    out[o] = v;
-  }
+  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (o < nout) part_fold_sums(part, nblk, (size_t)nout, o, grp, s);
+  const float v = part_fold_groups(red, grp, threadIdx.x & 63, s[0] + (s[1] + s[2] + s[3]));
+  if (grp == 0 && o < nout) out[o] = v;
 }
 
 constexpr int WG_SW = 64;  // strip width

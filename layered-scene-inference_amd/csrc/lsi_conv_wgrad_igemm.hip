@@ -11,10 +11,10 @@
 //
 // * Both operands are channels-last: a pixel's channels are contiguous, an MFMA
 //   operand wants 8 consecutive K = 8 pixels of one channel per lane.  The LDS
-//   transpose read (`ds_read_b64_tr_b16`, tr_frag below) hands every lane its 8
-//   pixels of one channel out of pixel-major LDS rows; every lane points at its
-//   own rows, so the shifted (tap) and strided (stride 2) pixels of the input
-//   patch are plain address arithmetic.
+//   transpose read (`ds_read_b64_tr_b16`, tr_frag of lsi_conv_device.h) hands
+//   every lane its 8 pixels of one channel out of pixel-major LDS rows; every
+//   lane points at its own rows, so the shifted (tap) and strided (stride 2)
+//   pixels of the input patch are plain address arithmetic.
 // * Workgroup = (image, strip of 32 output columns, block of RB output rows) x
 //   (32 input channels, group of <= 9 taps) x (BN = 64 | 32 output channels); it
 //   walks down its rows TH at a time: the input patch the taps reach and the gy
@@ -33,17 +33,13 @@
 #include <string.h>
 
 #include "../../include/lsi_hip.h"
+#include "lsi_common.h"
+#include "lsi_conv_device.h"
 #include "lsi_conv_host.h"
-#include "lsi_splat_internal.h"
+
+using namespace lsi;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int GW_XS = 48;     // LDS elements per staged input pixel: 32 channels + 16 (96 bytes, odd x 32)
 constexpr int GW_GT = 9;      // taps per workgroup
@@ -77,18 +73,6 @@ struct GwArgs {
   int swz;
   signed char tdy[GW_MAXTAPS + 3], tdx[GW_MAXTAPS + 3];
 };
-
-// 16 channels x 32 pixels at `p` (first pixel / first channel), pixel pitch
-// STRIDE elements: lane (t = lane % 16, g = lane / 16) gets channel t of its 8
-// pixels 16 (g / 2) + 4 (g % 2) + 8 h + r (the K order, the same for A and B).
-template <int STRIDE>
-__device__ __forceinline__ bf16x8 gw_tr_frag(const __bf16* p, int t, int g) {
-  const __bf16* q = p + (16 * (g >> 1) + 4 * (g & 1) + (t >> 2)) * STRIDE + 4 * (t & 3);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)q);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(q + 8 * STRIDE));
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 constexpr int gw_gs(int bn) { return bn == 64 ? 80 : 48; }  // gy pixel pitch (odd x 32 bytes)
 
@@ -212,12 +196,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_igemm_kernel(GwArgs a) {
     for (int r = 0; r < nrow; ++r) {
       bf16x8 af[NCT];
 #pragma unroll
-      for (int m = 0; m < NCT; ++m) af[m] = gw_tr_frag<GS>(gs + (size_t)(r * 32) * GS + 16 * m, t, g);
+      for (int m = 0; m < NCT; ++m) af[m] = tr_frag<GS>(gs + (size_t)(r * 32) * GS + 16 * m, t, g);
       const __bf16* const xrow = xs + (size_t)(r * S) * PW * XS;
 #pragma unroll
       for (int j = 0; j < PB; ++j) {
         if (poff[j] >= 0) {   // (wave-uniform)
-          const bf16x8 bf = gw_tr_frag<XS * S>(xrow + poff[j], t, g);
+          const bf16x8 bf = tr_frag<XS * S>(xrow + poff[j], t, g);
 #pragma unroll
           for (int m = 0; m < NCT; ++m)
             acc[j][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[m], bf, acc[j][m], 0, 0, 0);
@@ -254,25 +238,10 @@ __global__ __launch_bounds__(1024) void conv_wgrad_fold_kernel(const float* part
                                                                int Cin, int cl) {
   __shared__ float red[16][64];
   const int o = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
-  float s = 0.0f;
-  if (o < nout) {
-    float s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    int w = grp;
-    for (; w + 48 < nblk; w += 64) {
-      s += part[(size_t)w * nout + o];
-      s1 += part[(size_t)(w + 16) * nout + o];
-      s2 += part[(size_t)(w + 32) * nout + o];
-      s3 += part[(size_t)(w + 48) * nout + o];
-    }
-    for (; w < nblk; w += 16) s += part[(size_t)w * nout + o];
-    s += s1 + s2 + s3;
-  }
-  red[grp][threadIdx.x & 63] = s;
-  __syncthreads();
+  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (o < nout) part_fold_sums(part, nblk, (size_t)nout, o, grp, s);
+  const float v = part_fold_groups(red, grp, threadIdx.x & 63, s[0] + (s[1] + s[2] + s[3]));
   if (grp == 0 && o < nout) {
-    float v = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v += red[k][threadIdx.x];
     const int per = nout / khw;            // Cout * Cin
     const int tap = o / per, rest = o - tap * per;
     if (cl) {

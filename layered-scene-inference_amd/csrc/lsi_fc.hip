@@ -42,13 +42,11 @@
 #include <stdint.h>
 
 #include "../../include/lsi_hip.h"
+#include "lsi_conv_device.h"   // (the vector types)
+
+using namespace lsi;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kMaxM = 32;
 constexpr int kWaves = 4;         // waves of a streaming workgroup

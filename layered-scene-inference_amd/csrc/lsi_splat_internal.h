@@ -82,11 +82,6 @@ int lsi_tile_launch(const SplatArgs& a, hipStream_t stream);
 #define LSI_SWEEP_MAXL 16
 int lsi_sweep_launch(const SplatArgs& a, const float2* range, hipStream_t stream);
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) only when this (device,
-// kernel) has not been granted `bytes` yet: an eager caller launches the same
-// kernel with the same plan thousands of times (lsi_splat.hip).
-int lsi_ensure_dynamic_lds(const void* fn, size_t bytes);
-
 // ---- device primitives of the STREAM kernels --------------------------------
 // One definition for lsi_splat_stream.hip, its compact instance
 // lsi_splat_stream2.hip and the sweep / backward kernels: the two STREAM kernels

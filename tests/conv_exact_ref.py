@@ -272,6 +272,11 @@ FIRST = [(1, 9, 11), (2, 12, 20), (3, 37, 91)]
 # g. the fp32 family
 F32 = [IGEMM[0], IGEMM[4], IGEMM[10], IGEMM[11]]
 F32_T = [IGEMM_T[0]]
+# h. the fp32 pack's edge tiles (the fp32 forward takes output channels in
+#    multiples of 16, the pack moves 32 x 32 tiles): Cout = 16, less than one
+#    tile, and 48, one whole tile plus a half -- the two smallest channel counts
+#    at which a guard can be wrong on either side of a tile edge
+F32_EDGE = [conv(1, 32, 16, 3, 7, 3, 1), conv(1, 32, 48, 5, 17, 3, 1)]
 
 
 def c32_case(n, h, w, cin=32, cout=32):
@@ -283,11 +288,12 @@ def first_case(n, h, w):
 
 
 def all_cases():
-  """Every case of sections a - g, once."""
+  """Every case of sections a - h, once."""
   cs = IGEMM + IGEMM_T + SPLIT[2:] + [c for _, c in CAT]
   cs += [c32_case(*s) for s in C32_FWD] + [c32_case(n, h, w, 32, 16) for n, h, w in C32_FWD]
   cs += [c32_case(*s) for s in C32_WGRAD]
   cs += [first_case(*s) for s in FIRST]
+  cs += F32_EDGE
   seen, out = set(), []
   for c in cs:
     if c not in seen:

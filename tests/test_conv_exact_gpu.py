@@ -335,6 +335,38 @@ def test_fp32_family_bit_for_bit(case, regime, dev):
   _same('gw', gw, gw64.float())
 
 
+# ---- h. the fp32 pack's edge tiles (D0 or D1 no multiple of 32) -------------------------
+
+@pytest.mark.parametrize('regime', R.REGIMES)
+@pytest.mark.parametrize('layout', ['contig', 'clast'])
+@pytest.mark.parametrize('case', R.F32_EDGE, ids=_ids)
+def test_fp32_pack_edge_tiles_bit_for_bit(case, layout, regime, dev):
+  """Output channels that end inside a 32 x 32 tile of the pack: only the C
+  entries reach them (a layer wants both directions, and the data gradient
+  refuses Cout % 32 != 0).  lsi_conv2d_f32_pack + lsi_conv2d_f32_run (mode 0)
+  and, where it takes the shape, lsi_conv2d_wgrad_f32; the parameter contiguous
+  and with channels-last strides (the pack's and the fold's tr & 2 paths)."""
+  from lsi import _C
+  from lsi.nnutils import _hip_conv
+  assert case.cout % 32 != 0 and case.cout % 16 == 0
+  (x, w, gy), (y64, _, gw64) = _ref(case, regime)
+  d = _desc(case)
+  assert _C.lib().lsi_conv2d_f32_supported(ctypes.byref(d))
+  xf = _cl(x, dev, torch.float32)
+  wp = w.clone()
+  if layout == 'clast':
+    wp = wp.contiguous(memory_format=torch.channels_last)
+  assert _hip_conv._pack_layout(wp) == (2 if layout == 'clast' else 0)
+  oh, ow = R.out_size(case)
+  y = _hip_conv._run(_hip_conv.F32, d, 0, wp, xf,
+                     _hip_conv._empty_cl(case.n, case.cout, oh, ow, dev, torch.float32))
+  _same('y', y, y64.float())
+  if _hip_conv.f32_wgrad_bytes(d) > 0:
+    gw = _hip_conv._wgrad(_hip_conv.F32, d, xf, _cl(gy, dev, torch.float32), wp)
+    assert gw.dtype == torch.float32 and gw.stride() == wp.stride()
+    _same('gw', gw, gw64.float())
+
+
 # ---- every build of conv_igemm_kernel the planner can choose --------------------------
 #
 # 30 of the 32 instantiations are reached; the two that are not, and why:

@@ -1285,6 +1285,71 @@ int lsi_area_resize_u8(int32_t n, const LsiImageDesc* desc_host,
                        size_t packed_bytes, int32_t Ho, int32_t Wo, int32_t Co,
                        float* out, lsi_stream_t stream);
 
+/*
+ * Contact sheet of visuals, one launch: n_items fp32 device
+ * tensors, each with its own size, strides and value range, are quantised to
+ * bytes and laid out on a grid of rows x cols cells of cell_h x cell_w pixels
+ * with `gutter` >= 0 pixels between the cells and around the border.  The
+ * sheet is rows cell_h + (rows + 1) gutter high and cols cell_w + (cols + 1)
+ * gutter wide (lsi_visual_sheet_size), RGB interleaved, rows out_row_bytes
+ * apart.  Item k sits in cell (k / cols, k % cols), at the cell's top-left;
+ * cells without an item, gutters and what an item leaves of its cell take the
+ * colour bg.  Every byte of a row below 3 width is written exactly once, no
+ * byte beyond it.
+ *   item      H x W x C through the element strides (s_y, s_x, s_c), none
+ *             negative; sheet pixel (y, x) of the item shows source
+ *             (y / zoom, x / zoom), zoom >= 1, H zoom <= cell_h, W zoom <=
+ *             cell_w.  No element outside those H x W x C is read.
+ *   kinds     RGB (C = 3, each channel quantised on its own), GRAY (C = 1, the
+ *             byte in all three channels), LUT (C = 1, the byte indexes lut_dev),
+ *             ABSDIFF (C = 1 or 3, a second tensor `ref` of the same size with
+ *             the strides r_*: v = |a0 - b0|, or ((|a0 - b0| + |a1 - b1|) +
+ *             |a2 - b2|) fl(1/3) added in that order in fp32; then as LUT),
+ *             SKIP (no source: the cell stays bg)
+ *   value     fp32, no contraction: a NaN (for RGB in any channel) gives the
+ *             colour nan; else t = fl(fl(v - lo) inv), inv = fl(1 / fl(hi - lo))
+ *             formed by the caller, t = min(max(t, 0), 1) and the byte is
+ *             (int)floorf(fl(fl(t 255) + 0.5))
+ *   lut_dev   256 x 3 bytes on the device, 4-byte aligned; may be NULL when no
+ *             item is LUT or ABSDIFF
+ *   items_dev the n_items descriptors on the device (8-byte aligned), read by
+ *             the kernel; items_host the same in host memory, checked here
+ *             before the launch (the two must agree)
+ *   out       device, 4-byte aligned; out_row_bytes >= 3 width, a multiple of 4
+ * LSI_ENULL for a NULL sheet, out, descriptor array (n_items > 0), src, ref of
+ * an ABSDIFF item or lut_dev when an item needs it; LSI_EINVAL for a grid or
+ * cell size < 1, a negative gutter, n_items outside [0, min(rows cols,
+ * LSI_VIS_MAX_ITEMS)], an unknown kind, a C the kind does not take, zoom < 1,
+ * H or W <= 0, an item larger than its cell, a negative stride, lo or inv not
+ * finite or inv <= 0, a misaligned pointer, a bad out_row_bytes or a sheet of
+ * more than 2^31 - 1 bytes -- all before any launch.  No workspace, no
+ * allocation, no synchronisation, no state.
+ */
+#define LSI_VIS_SKIP 0
+#define LSI_VIS_RGB 1
+#define LSI_VIS_GRAY 2
+#define LSI_VIS_LUT 3
+#define LSI_VIS_ABSDIFF 4
+#define LSI_VIS_MAX_ITEMS 256
+typedef struct LsiVisSheet {
+  int32_t rows, cols, cell_h, cell_w, gutter, n_items;
+  uint8_t bg[3], nan[3];  /* background and NaN marker, R G B               */
+  uint8_t reserved[2];    /* 0                                               */
+} LsiVisSheet;
+typedef struct LsiVisItem {
+  const float* src;       /* device                                          */
+  const float* ref;       /* device; ABSDIFF only, else NULL                 */
+  int64_t s_y, s_x, s_c;  /* element strides of src                          */
+  int64_t r_y, r_x, r_c;  /* ... and of ref                                  */
+  int32_t kind, H, W, C, zoom;
+  int32_t reserved;       /* 0                                               */
+  float lo, inv;
+} LsiVisItem;
+int lsi_visual_sheet_size(const LsiVisSheet* sheet, int64_t* height, int64_t* width);
+int lsi_visual_pack_u8(const LsiVisSheet* sheet, const LsiVisItem* items_host,
+                       const LsiVisItem* items_dev, const uint8_t* lut_dev,
+                       uint8_t* out, int64_t out_row_bytes, lsi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,13 +12,24 @@ composed rendering into the other view in both directions (`compose_loss`), its
 dis-occlusion restricted variant (`compose_loss_disocc`, synthetic: mask from
 projection.disocclusion_mask on the ground-truth disparities), rendered
 disparity error (`depth_loss[_disocc]`), and the per-layer fg / bg texture and
-disparity errors; plus PSNR.  The HTML / PNG / .mat plumbing of the reference
-is not reproduced.
+disparity errors; plus PSNR.
+
+`--save_visuals N` shows what the predictor learnt on the first N iterations
+(the reference's `define_visuals`, ldi_pred_eval.py:272-290, 445-515, for batch
+element 0): the layers' textures and disparities, the renderings beside their
+targets, the per-pixel errors and the dis-occlusion masks, as one contact sheet
+per iteration under `<results_dir>/visuals/` with an `index.html` and a
+`visuals.json` legend.  A sheet is packed by one HIP launch, copied to the host
+once and encoded on a worker thread (lsi/visualization, DESIGN.md 4.15);
+`--save_preds true` also writes the predicted layers of the whole batch to
+`<results_dir>/preds/iter_%06d.npz`.  The reference's .mat files are not
+reproduced.
 """
 import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -27,6 +38,7 @@ if _HERE not in sys.path:
 
 import ldi_enc_dec as train_script  # noqa: E402
 from lsi.geometry import projection  # noqa: E402
+from lsi.loss import loss as loss_utils  # noqa: E402
 from lsi.nnutils import eval_metrics, helpers as nn_helpers, nets, train_utils  # noqa: E402
 
 
@@ -51,7 +63,86 @@ def build_parser():
     help='also score SSIM (layer 0 of the composed rendering, 11 x 11 Gaussian '
     'windows, sigma 1.5, inside the border crop): `ssim` in the results, from '
     'the fused kernel of csrc/lsi_ssim.hip on either metric route')
+  a('--save_visuals', type=int, default=0,
+    help='write a contact sheet of batch element 0 for the first N iterations: '
+    '<results_dir>/visuals/iter_%%06d.png, index.html, visuals.json')
+  a('--visuals_cols', type=int, default=6, help='cells per row of a sheet')
+  a('--visuals_disp_hi', type=float, default=0.0,
+    help='disparities are mapped on [0, this]; 0 = max_disp')
+  a('--visuals_err_hi', type=float, default=0.5,
+    help='error maps are mapped on [0, this]')
+  a('--save_preds', type=train_script._bool, default=False,
+    help='with --save_visuals: also <results_dir>/preds/iter_%%06d.npz, the '
+    'predicted textures and disparities (and masks) of the whole batch, fp32')
   return p
+
+
+def _f32(t):
+  return t if t.dtype == torch.float32 else t.float()
+
+
+class EvalVisuals(object):
+  """The contact sheets (and predictions) of the saved iterations: `eval_batch`
+  hands `save` what it predicted and rendered."""
+
+  def __init__(self, opts, device, res_dir):
+    from lsi.visualization import SheetBuilder, VisualWriter  # pylint: disable=g-import-not-at-top
+    self.builder = SheetBuilder(device, opts.visuals_cols, opts.img_height,
+                                opts.img_width)
+    self.writer = VisualWriter(os.path.join(res_dir, 'visuals'))
+    self.disp_hi = opts.visuals_disp_hi or opts.max_disp
+    self.err_hi = opts.visuals_err_hi
+    self.preds_dir = os.path.join(res_dir, 'preds') if opts.save_preds else None
+    if self.preds_dir:
+      os.makedirs(self.preds_dir, exist_ok=True)
+    self.iteration = 0
+    self._sheet = None
+
+  def save(self, imgs_src, imgs_trg, ldi_src, ldi_trg, views, gt):
+    """views: 'trg' / 'src' (the view reconstructed) -> (recons, recons_disp,
+    target, gt_disp or None, disocc or None)."""
+    sb, dh, eh = self.builder, self.disp_hi, self.err_hi
+    sb.clear()
+    sb.add_rgb('src_im', _f32(imgs_src)[0])
+    sb.add_rgb('trg_im', _f32(imgs_trg)[0])
+    for l in range(ldi_src[0].shape[0]):
+      for key, ldi in (('src', ldi_src), ('trg', ldi_trg)):
+        sb.add_rgb('%s_tex_pred_layer_%d' % (key, l), _f32(ldi[0])[l, 0])
+        sb.add_map('%s_disp_pred_layer_%d' % (key, l), _f32(ldi[2])[l, 0, :, :, 0], 0., dh)
+    for key in ('trg', 'src'):
+      recons, recons_disp, target, gt_disp, disocc = views[key]
+      ht, wt = recons.shape[2:4]
+      sb.add_rgb(key + '_splat_tex', recons[0, 0])
+      sb.add_absdiff(key + '_vs_loss', recons[0, 0],
+                     loss_utils.area_downsample(_f32(target)[:1], ht, wt)[0], eh)
+      sb.add_map(key + '_splat_disp', recons_disp[0, 0, :, :, 0], 0., dh)
+      if gt_disp is not None:
+        small = loss_utils.area_downsample(_f32(gt_disp)[:1], ht, wt)[0]
+        sb.add_map(key + '_gt_disp', small[:, :, 0], 0., dh)
+        sb.add_absdiff(key + '_depth_loss', recons_disp[0, 0], small, eh)
+      if disocc is not None:
+        sb.add_gray(key + '_disocc_mask', _f32(disocc)[0, :, :, 0], 0., 1.)
+    if gt is not None:
+      for key in ('src', 'trg'):
+        sb.add_rgb(key + '_gt_tex_bg', _f32(gt[key + '_gt_tex_bg'])[0])
+        sb.add_map(key + '_gt_disp_bg', _f32(gt[key + '_gt_disp_bg'])[0, :, :, 0], 0., dh)
+    if self._sheet is not None and tuple(self._sheet.shape[:2]) != sb.size():
+      self._sheet = None
+    self._sheet = sb.pack(out=self._sheet)
+    self.writer.submit('iter_%06d' % self.iteration, self._sheet, sb.names, sb.meta())
+    sb.clear()
+    if self.preds_dir:
+      preds = {}
+      for key, ldi in (('src', ldi_src), ('trg', ldi_trg)):
+        preds[key + '_tex'], preds[key + '_disp'] = ldi[0], ldi[2]
+        if ldi[1] is not None:
+          preds[key + '_mask'] = ldi[1]
+      np.savez(os.path.join(self.preds_dir, 'iter_%06d.npz' % self.iteration),
+               **{k: v.float().cpu().numpy() for k, v in preds.items()})
+    self.iteration += 1
+
+  def close(self):
+    self.writer.close()
 
 
 class Tester(object):
@@ -91,10 +182,12 @@ class Tester(object):
     nets.set_is_training(tr.model, bool(self.opts.batch_norm_training))
 
   @torch.no_grad()
-  def eval_batch(self, batch=None, acc=None):
+  def eval_batch(self, batch=None, acc=None, visuals=None):
     """One evaluation iteration on `batch` (None: the next one of the data
     loader).  Returns the op route's metric dicts, or, with a MetricAccumulator
-    `acc`, adds the same metrics to it on the device and returns []."""
+    `acc`, adds the same metrics to it on the device and returns [].  With an
+    `EvalVisuals` the iteration is saved as well: the renderings are made here,
+    by the call the metrics make, scored and handed on."""
     tr, o = self.trainer, self.opts
     if batch is None:
       batch = tr.data_loader.forward(o.batch_size)
@@ -121,7 +214,7 @@ class Tester(object):
     elif len(batch) != 6:
       raise ValueError('unexpected batch layout: %d outputs for dataset %r' %
                        (len(batch), o.dataset))
-    out = []
+    out, views = [], {}
     for ldi, k_a, k_b, r, t, target, key in (
         (ldi_src, k_s, k_t, rot, trans, imgs_trg, 'trg'),
         (ldi_trg, k_t, k_s, inv_rot, inv_trans, imgs_src, 'src')):
@@ -146,39 +239,50 @@ class Tester(object):
           valid, valid_above = gt_disp, o.bg_layer_disp
         else:
           valid = (gt_disp > o.bg_layer_disp).float()
+      rendered = None
+      if visuals is not None:
+        rendered = eval_metrics.render_view(ldi, pc, k_a, k_b, r, t, o)
+        views[key] = rendered + (target, gt_disp, disocc)
       if fused:
         acc.add_view_synthesis(
             ldi, pc, k_a, k_b, r, t, target, o, valid_mask=valid,
             disocc_mask=disocc, gt_disp_trg=gt_disp, valid_above=valid_above,
-            ssim=ssim)
+            ssim=ssim, rendered=rendered)
       else:
         out.append(eval_metrics.view_synthesis_metrics(
             ldi, pc, k_a, k_b, r, t, target, o, valid_mask=valid,
-            disocc_mask=disocc, gt_disp_trg=gt_disp, ssim=ssim))
+            disocc_mask=disocc, gt_disp_trg=gt_disp, ssim=ssim, rendered=rendered))
     if gt is not None:
       if fused:
         acc.add_layer_prediction(ldi_src, ldi_trg, imgs_src, imgs_trg, gt, o)
       else:
         out.append(eval_metrics.layer_prediction_metrics(
             ldi_src, ldi_trg, imgs_src, imgs_trg, gt, o))
+    if visuals is not None:
+      visuals.save(imgs_src, imgs_trg, ldi_src, ldi_trg, views, gt)
     return out
 
-  def test(self):
+  def test(self, batches=None):
+    """`batches`: the iterations' batches instead of the data loader's."""
     self.restore()
-    if self.opts.device_metrics:
-      # the running sums stay on the device; one read-back after the last batch
-      acc = eval_metrics.MetricAccumulator(self.trainer.device)
-      for _ in range(self.opts.num_eval_iter):
-        self.eval_batch(acc=acc)
-      results = acc.results()
-    else:
-      dicts = []
-      for _ in range(self.opts.num_eval_iter):
-        dicts += self.eval_batch()
-      results = eval_metrics.aggregate(dicts)
     res_dir = self.opts.results_dir or os.path.join(self.opts.checkpoint_dir,
                                                     'results')
     os.makedirs(res_dir, exist_ok=True)
+    n_saved = self.opts.save_visuals
+    visuals = EvalVisuals(self.opts, self.trainer.device, res_dir) if n_saved > 0 else None
+    # device_metrics: the running sums stay on the device; one read-back after
+    # the last batch
+    acc = (eval_metrics.MetricAccumulator(self.trainer.device)
+           if self.opts.device_metrics else None)
+    dicts = []
+    try:
+      for it in range(self.opts.num_eval_iter):
+        dicts += self.eval_batch(batch=batches[it] if batches else None, acc=acc,
+                                 visuals=visuals if it < n_saved else None)
+    finally:
+      if visuals is not None:
+        visuals.close()
+    results = acc.results() if acc is not None else eval_metrics.aggregate(dicts)
     with open(os.path.join(res_dir, 'results.txt'), 'w') as f:
       for k in sorted(results):
         f.write('%s : %.6f\n' % (k, results[k]))

@@ -27,6 +27,8 @@ LSI_SCENE_IMG, LSI_SCENE_DISP, LSI_SCENE_IMG_ROOM, LSI_SCENE_DISP_ROOM = 1, 2, 4
 LSI_SCENE_MAX_PLANES = 16
 LSI_FC_BN, LSI_FC_X_F32, LSI_FC_OUT_F32 = 1, 2, 4
 LSI_IMAGE_MAX_PIXELS = 16843009
+LSI_VIS_SKIP, LSI_VIS_RGB, LSI_VIS_GRAY, LSI_VIS_LUT, LSI_VIS_ABSDIFF = 0, 1, 2, 3, 4
+LSI_VIS_MAX_ITEMS = 256
 PATH_NAMES = {1: 'atomic', 2: 'rowband', 3: 'stream', 4: 'tile'}
 
 _c_f = ctypes.POINTER(ctypes.c_float)
@@ -117,6 +119,20 @@ class LsiConvIO(ctypes.Structure):
 class LsiImageDesc(ctypes.Structure):
   _fields_ = ([('offset', ctypes.c_int64)] +
               [(n, ctypes.c_int32) for n in ('H', 'W', 'C', 'reserved')])
+
+
+class LsiVisSheet(ctypes.Structure):
+  _fields_ = ([(n, ctypes.c_int32) for n in ('rows', 'cols', 'cell_h', 'cell_w',
+                                             'gutter', 'n_items')] +
+              [('bg', ctypes.c_uint8 * 3), ('nan', ctypes.c_uint8 * 3),
+               ('reserved', ctypes.c_uint8 * 2)])
+
+
+class LsiVisItem(ctypes.Structure):
+  _fields_ = ([('src', ctypes.c_void_p), ('ref', ctypes.c_void_p)] +
+              [(n, ctypes.c_int64) for n in ('s_y', 's_x', 's_c', 'r_y', 'r_x', 'r_c')] +
+              [(n, ctypes.c_int32) for n in ('kind', 'H', 'W', 'C', 'zoom', 'reserved')] +
+              [('lo', ctypes.c_float), ('inv', ctypes.c_float)])
 
 
 # name -> (restype, argtypes); every symbol include/lsi_hip.h declares.
@@ -240,6 +256,10 @@ SIGNATURES = {
     'lsi_fc_bwd': (ctypes.c_int, [ctypes.POINTER(LsiFcDesc)] + [_VP] * 10 + [_SZ, _VP]),
     'lsi_area_resize_u8': (ctypes.c_int, [_I32, _VP, _VP, _VP, _SZ] + [_I32] * 3 +
                            [_VP, _VP]),
+    'lsi_visual_sheet_size': (ctypes.c_int, [ctypes.POINTER(LsiVisSheet),
+                                             ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    'lsi_visual_pack_u8': (ctypes.c_int, [ctypes.POINTER(LsiVisSheet), _VP, _VP, _VP, _VP,
+                                          _I64, _VP]),
 }
 
 _lib = None

@@ -20,9 +20,21 @@ def _centre_mask(b, h, w, frac, device):
   return m
 
 
+def render_view(ldi_src, pixel_coords, k_s, k_t, rot, t, opts):
+  """The rendering the metrics score (compose_layers=True, compute_trg_disp=True:
+  ldi_pred_eval.py:340-353): (recons nl x B x Ht x Wt x 3, recons_disp nl x B x
+  Ht x Wt x 1)."""
+  recons, _, recons_disp = ldi_utils.forward_splat(
+      ldi_src, pixel_coords, k_s, k_t, rot, t, compose_layers=True,
+      compute_trg_disp=True, trg_downsampling=opts.trg_splat_downsampling,
+      zbuf_scale=opts.zbuf_scale, bg_layer_disp=opts.bg_layer_disp,
+      max_disp=opts.max_disp)
+  return recons, recons_disp
+
+
 def view_synthesis_metrics(ldi_src, pixel_coords, k_s, k_t, rot, t, imgs_trg,
                            opts, valid_mask=None, disocc_mask=None,
-                           gt_disp_trg=None, ssim=None):
+                           gt_disp_trg=None, ssim=None, rendered=None):
   """Renders `ldi_src` into the target camera (compose_layers=True,
   compute_trg_disp=True: ldi_pred_eval.py:340-353) and accumulates the masked
   errors against `imgs_trg` (B x H x W x 3).
@@ -31,13 +43,11 @@ def view_synthesis_metrics(ldi_src, pixel_coords, k_s, k_t, rot, t, imgs_trg,
   splat_bdry_ignore.  valid_mask / disocc_mask / gt_disp_trg: B x H x W x 1 or
   None.  Returns a dict name -> (sum, norm) of 0-d tensors.  With ssim = (win,
   sigma) the dict also holds `ssim`, from the kernel `MetricAccumulator.add_ssim`
-  runs (there is no op form of it).
+  runs (there is no op form of it).  `rendered`: the caller's `render_view` of
+  the same arguments, scored instead of rendering here.
   """
-  recons, _, recons_disp = ldi_utils.forward_splat(
-      ldi_src, pixel_coords, k_s, k_t, rot, t, compose_layers=True,
-      compute_trg_disp=True, trg_downsampling=opts.trg_splat_downsampling,
-      zbuf_scale=opts.zbuf_scale, bg_layer_disp=opts.bg_layer_disp,
-      max_disp=opts.max_disp)
+  recons, recons_disp = rendered or render_view(ldi_src, pixel_coords, k_s, k_t, rot,
+                                                t, opts)
   _, b, ht, wt, _ = recons.shape
   dev = recons.device
   target = loss_utils.area_downsample(imgs_trg, ht, wt)
@@ -194,15 +204,13 @@ class MetricAccumulator(object):
 
   def add_view_synthesis(self, ldi_src, pixel_coords, k_s, k_t, rot, t, imgs_trg,
                          opts, valid_mask=None, disocc_mask=None,
-                         gt_disp_trg=None, valid_above=None, ssim=None):
+                         gt_disp_trg=None, valid_above=None, ssim=None,
+                         rendered=None):
     """`view_synthesis_metrics` with the arithmetic after the render fused: the
-    same forward_splat call, then `add_rendered` (and, with ssim = (win, sigma),
-    `add_ssim`)."""
-    recons, _, recons_disp = ldi_utils.forward_splat(
-        ldi_src, pixel_coords, k_s, k_t, rot, t, compose_layers=True,
-        compute_trg_disp=True, trg_downsampling=opts.trg_splat_downsampling,
-        zbuf_scale=opts.zbuf_scale, bg_layer_disp=opts.bg_layer_disp,
-        max_disp=opts.max_disp)
+    same forward_splat call (or the caller's, `rendered`), then `add_rendered`
+    (and, with ssim = (win, sigma), `add_ssim`)."""
+    recons, recons_disp = rendered or render_view(ldi_src, pixel_coords, k_s, k_t,
+                                                  rot, t, opts)
     self.add_rendered(recons, recons_disp, imgs_trg, opts.splat_bdry_ignore,
                       valid_mask=valid_mask, disocc_mask=disocc_mask,
                       gt_disp_trg=gt_disp_trg, valid_above=valid_above)

@@ -731,6 +731,73 @@ int lsi_eval_layer_metrics(const LsiLossDesc* src_desc, const float* src_tex,
                            lsi_stream_t stream);
 
 /*
+ * Depth accuracy of a predicted inverse-depth map (csrc/lsi_depth_metrics.hip;
+ * no reference counterpart, the definition is DESIGN.md section 4.16): the
+ * seven figures of Eigen et al. 2014 per image, summed over the scored images
+ * into an accumulator of its own, `acc` of LSI_DEPTH_SLOTS device doubles
+ * (zeroed by the caller once; not part of the LSI_EVAL_SLOTS doubles).
+ *   pred [B,H,W] predicted inverse depth, gt [B,H,W] a ground-truth map that
+ *   gt_scale[b] (B device floats) turns into inverse depth, mask [B,H,W] fp32 or
+ *   one-byte bool (LSI_DEPTH_MASK_U8; may be NULL): contiguous
+ * Per pixel in fp32, dg = 1 / (gt gt_scale[b]).  It is scored -- the set V_b, a
+ * function of the ground truth alone -- when gt > valid_above, y0 <= y < y1,
+ * x0 <= x < x1, the mask is absent or non-zero and depth_min <= dg <= depth_max.
+ * dp_raw = 1 / fmaxf(pred, FLT_MIN): a zero, negative or NaN prediction is a
+ * huge finite depth, and no Inf or NaN reaches acc from such predictions.  (A
+ * +Inf prediction is depth 0, clamped to depth_min; the caller keeps +Inf out
+ * of a median-scaled call: were half an image's scored predictions +Inf, the
+ * median depth would be 0 and s_b = Inf would be added to LSI_DEPTH_SCALE.)
+ * s_b = 1, or with LSI_DEPTH_MEDIAN
+ * (float)(med(dg over V_b) / med(dp_raw over V_b)): exact order statistics of
+ * the fp32 values (a radix select on the device), the two middle values of an
+ * even count averaged, mean and quotient in fp64.
+ *   dp = fminf(fmaxf(s_b dp_raw, depth_min), depth_max), e = dg - dp
+ *   terms |e| / dg, e e / dg, e e, (logf(dg) - logf(dp))^2
+ *   r = fmaxf(dg / dp, dp / dg) < 1.25, 1.25^2, 1.25^3
+ * Per image with n_b = |V_b| > 0, sums in fp64: abs_rel, sq_rel = sum / n_b;
+ * rmse, rmse_log = sqrt(sum / n_b); a1..a3 = count / n_b.  Each is ADDED to its
+ * slot, s_b to LSI_DEPTH_SCALE and 1 to LSI_DEPTH_IMAGES, images in index
+ * order, by a one-block finishing kernel; an image without a scored pixel adds
+ * nothing.  per_image (may be NULL): B x LSI_DEPTH_PER_IMAGE device doubles,
+ * overwritten with the image's seven figures, s_b, n_b and 1 (all zeros for an
+ * image that is not scored).  Pixels outside the crop are not read.
+ * LSI_EINVAL for non-positive dimensions (B <= 65535), an empty or
+ * out-of-range crop, depth_min <= 0, depth_max < depth_min, valid_above < 0 or
+ * unknown flags; then LSI_ENULL for a NULL pred, gt, gt_scale, acc or
+ * workspace; then LSI_EWORKSPACE -- all before any launch.  2 launches, 10
+ * with LSI_DEPTH_MEDIAN, whatever the data; no floating-point atomics, no
+ * host synchronisation: the same sequence of calls gives the same doubles bit
+ * for bit.
+ */
+#define LSI_DEPTH_ABS_REL 0
+#define LSI_DEPTH_SQ_REL 1
+#define LSI_DEPTH_RMSE 2
+#define LSI_DEPTH_RMSE_LOG 3
+#define LSI_DEPTH_A1 4
+#define LSI_DEPTH_A2 5
+#define LSI_DEPTH_A3 6
+#define LSI_DEPTH_SCALE 7      /* sum of s_b over the scored images            */
+#define LSI_DEPTH_IMAGES 8     /* number of scored images                      */
+#define LSI_DEPTH_SLOTS 9
+#define LSI_DEPTH_PER_IMAGE 10 /* per_image row: slots 0-7 of the image, n_b,  */
+                               /* scored (0 or 1)                              */
+
+#define LSI_DEPTH_MASK_U8 1u   /* mask holds one-byte bools, not floats        */
+#define LSI_DEPTH_MEDIAN 2u    /* per-image median scaling                     */
+
+/* Bytes of device scratch lsi_eval_depth_metrics needs for B x H x W maps (any
+ * crop), more with median != 0; 0 for dimensions the call refuses. */
+size_t lsi_eval_depth_workspace_bytes(int32_t B, int32_t H, int32_t W,
+                                      int32_t median);
+int lsi_eval_depth_metrics(int32_t B, int32_t H, int32_t W, const float* pred,
+                           const float* gt, const void* mask,
+                           const float* gt_scale, int32_t y0, int32_t y1,
+                           int32_t x0, int32_t x1, float valid_above,
+                           float depth_min, float depth_max, uint32_t flags,
+                           double* acc, double* per_image, void* workspace,
+                           size_t workspace_bytes, lsi_stream_t stream);
+
+/*
  * projection.disocclusion_mask (lsi/geometry/projection.py:109-150) for source
  * points on the pixel-centre grid: (x + .5, y + .5, 1, disps_src) through
  * M [B,4,4] under the floating-point contract of the renderer, divide_safe,

@@ -20,10 +20,11 @@ inline int grid_for(long n) {
 }
 
 // Block-wide sum of NV per-thread values; thread 0 stores them (fp64) to
-// part[v * MAXBLK + blockIdx.x].
+// part[v * stride + blockIdx.x] (stride: the partial sums kept per scalar).
 template <int NV>
 __device__ __forceinline__ void block_store_partials(const float (&v)[NV],
-                                                     double* part) {
+                                                     double* part,
+                                                     int stride = MAXBLK) {
   __shared__ double sm[NV][TPB / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -38,7 +39,7 @@ __device__ __forceinline__ void block_store_partials(const float (&v)[NV],
     for (int k = 0; k < NV; ++k) {
       double s = 0.0;
       for (int w = 0; w < TPB / 64; ++w) s += sm[k][w];
-      part[(size_t)k * MAXBLK + blockIdx.x] = s;
+      part[(size_t)k * stride + blockIdx.x] = s;
     }
   }
 }

@@ -54,6 +54,11 @@ def build_parser():
   a('--kitti_dataset_variant', default='mview',
     choices=['odom', 'mview', 'raw_city'])
   a('--kitti_dl_disparities', type=_bool, default=False)
+  a('--kitti_dl_disparities_px', type=_bool, default=False,
+    help='under the conditions of --kitti_dl_disparities: append the SPS-stereo '
+    'disparities of both views in pixels of the resized image, both bytes of the '
+    '16-bit PNG, nearest-neighbour sampled (the ground truth of --eval_depth; '
+    'the synchronous loader only)')
   a('--kitti_procedural', type=_bool, default=False,
     help='no KITTI files: procedural stereo pairs seen through the KITTI camera '
     'model and constants (throughput runs, tests).  Without this switch a '

@@ -12,7 +12,8 @@ composed rendering into the other view in both directions (`compose_loss`), its
 dis-occlusion restricted variant (`compose_loss_disocc`, synthetic: mask from
 projection.disocclusion_mask on the ground-truth disparities), rendered
 disparity error (`depth_loss[_disocc]`), and the per-layer fg / bg texture and
-disparity errors; plus PSNR.
+disparity errors; plus PSNR.  `--eval_depth true` adds the depth accuracy of
+the predicted input views (abs-rel, sq-rel, RMSE, RMSE-log, delta < 1.25^k).
 
 `--save_visuals N` shows what the predictor learnt on the first N iterations
 (the reference's `define_visuals`, ldi_pred_eval.py:272-290, 445-515, for batch
@@ -63,6 +64,22 @@ def build_parser():
     help='also score SSIM (layer 0 of the composed rendering, 11 x 11 Gaussian '
     'windows, sigma 1.5, inside the border crop): `ssim` in the results, from '
     'the fused kernel of csrc/lsi_ssim.hip on either metric route')
+  a('--eval_depth', type=train_script._bool, default=False,
+    help='also score the predicted depth of both input views (layer 0 of each '
+    "LDI's disparities) with the seven standard figures: depth_abs_rel, "
+    'depth_sq_rel, depth_rmse, depth_rmse_log, depth_a1 .. depth_a3 in the '
+    'results (DESIGN.md 4.16).  Synthetic planes: against the ground-truth '
+    'disparities; KITTI: against the SPS-stereo disparities in pixels '
+    '(--kitti_dl_disparities_px true)')
+  a('--depth_min', type=float, default=1e-3,
+    help='--eval_depth: ground-truth depths outside [depth_min, depth_max] are '
+    'not scored, predicted depths are clamped to it')
+  a('--depth_max', type=float, default=80.)
+  a('--depth_crop', default='none', choices=['none', 'garg'],
+    help="--eval_depth: score the whole image or the crop of Garg et al. 2016")
+  a('--depth_median_scale', type=train_script._bool, default=False,
+    help="--eval_depth: scale every image's predicted depths by the ratio of the "
+    'medians first; `depth_scale` in the results is the mean factor')
   a('--save_visuals', type=int, default=0,
     help='write a contact sheet of batch element 0 for the first N iterations: '
     '<results_dir>/visuals/iter_%%06d.png, index.html, visuals.json')
@@ -203,17 +220,21 @@ class Tester(object):
     # ground truth by data set (ldi_pred_eval.py:226-262): synthetic planes
     # carry 14 outputs (fg / bg disparities and background textures), KITTI
     # with --kitti_dl_disparities 8 (the SPS-stereo disparities of both views)
-    gt, kitti_disp = None, None
+    gt, kitti_disp, kitti_px = None, None, None
+    n_px = 2 if (o.dataset == 'kitti' and len(batch) > 6 and
+                 getattr(o, 'kitti_dl_disparities_px', False)) else 0
     if o.dataset == 'synthetic' and len(batch) >= 14:
       (_, _, d_s_fg, d_s_bg, d_t_fg, d_t_bg, img_s_bg, img_t_bg) = batch[6:14]
       gt = {'src_gt_disp': d_s_fg.to(dev), 'trg_gt_disp': d_t_fg.to(dev),
             'src_gt_disp_bg': d_s_bg.to(dev), 'trg_gt_disp_bg': d_t_bg.to(dev),
             'src_gt_tex_bg': img_s_bg.to(dev), 'trg_gt_tex_bg': img_t_bg.to(dev)}
-    elif o.dataset == 'kitti' and len(batch) == 8:
+    elif o.dataset == 'kitti' and len(batch) - n_px == 8:
       kitti_disp = {'src': batch[6].to(dev), 'trg': batch[7].to(dev)}
-    elif len(batch) != 6:
+    elif len(batch) - n_px != 6:
       raise ValueError('unexpected batch layout: %d outputs for dataset %r' %
                        (len(batch), o.dataset))
+    if n_px:  # --kitti_dl_disparities_px: the last two outputs
+      kitti_px = {'src': batch[-2].to(dev), 'trg': batch[-1].to(dev)}
     out, views = [], {}
     for ldi, k_a, k_b, r, t, target, key in (
         (ldi_src, k_s, k_t, rot, trans, imgs_trg, 'trg'),
@@ -258,8 +279,42 @@ class Tester(object):
       else:
         out.append(eval_metrics.layer_prediction_metrics(
             ldi_src, ldi_trg, imgs_src, imgs_trg, gt, o))
+    if getattr(o, 'eval_depth', False):
+      out += self.eval_depth(acc, ldi_src, ldi_trg, k_s, k_t, trans, gt, kitti_px)
     if visuals is not None:
       visuals.save(imgs_src, imgs_trg, ldi_src, ldi_trg, views, gt)
+    return out
+
+  def eval_depth(self, acc, ldi_src, ldi_trg, k_s, k_t, trans, gt, kitti_px):
+    """--eval_depth: the predicted inverse depth of each input view (layer 0 of
+    its LDI's disparities) against that view's ground truth; with `acc` through
+    the fused kernels, else the op route's dicts."""
+    o, dev = self.opts, self.trainer.device
+    if gt is not None:
+      # inverse depths already; scored where the fg metric is (gt > bg_layer_disp)
+      maps = {'src': (gt['src_gt_disp'], None), 'trg': (gt['trg_gt_disp'], None)}
+      valid_above = o.bg_layer_disp
+    elif kitti_px is not None:
+      # pixel disparities d = f_x |t_x| / depth, each view with its own intrinsics
+      t_x = trans[:, 0, 0].abs()
+      maps = {'src': (kitti_px['src'], (1.0 / (k_s[:, 0, 0] * t_x)).float().to(dev)),
+              'trg': (kitti_px['trg'], (1.0 / (k_t[:, 0, 0] * t_x)).float().to(dev))}
+      valid_above = 0.
+    else:
+      raise ValueError(
+          '--eval_depth needs ground-truth depth: --synth_scene planes, or KITTI '
+          'raw_city (val / test) with --kitti_dl_disparities_px true')
+    kw = dict(crop=(eval_metrics.garg_crop(o.img_height, o.img_width)
+                    if o.depth_crop == 'garg' else None),
+              valid_above=valid_above, depth_min=o.depth_min, depth_max=o.depth_max,
+              median=o.depth_median_scale)
+    out = []
+    for key, ldi in (('src', ldi_src), ('trg', ldi_trg)):
+      gt_map, gt_scale = maps[key]
+      if acc is not None:
+        acc.add_depth_accuracy(ldi[2][0], gt_map, gt_scale, **kw)
+      else:
+        out.append(eval_metrics.depth_accuracy_metrics(ldi[2][0], gt_map, gt_scale, **kw))
     return out
 
   def test(self, batches=None):

@@ -207,6 +207,9 @@ SIGNATURES = {
                               [_SZ, _VP]),
     'lsi_eval_layer_metrics': (ctypes.c_int, ([_LP] + [_VP] * 6) * 2 + [_VP] * 2 +
                                [_SZ, _VP]),
+    'lsi_eval_depth_workspace_bytes': (_SZ, [_I32] * 4),
+    'lsi_eval_depth_metrics': (ctypes.c_int, [_I32] * 3 + [_VP] * 4 + [_I32] * 4 +
+                               [_F32] * 3 + [ctypes.c_uint32] + [_VP] * 3 + [_SZ, _VP]),
     'lsi_disocclusion_mask': (ctypes.c_int, [_I32] * 5 + [_VP] * 3 + [_F32, _VP, _VP]),
     'lsi_render_planes': (ctypes.c_int, [ctypes.POINTER(LsiSceneDesc)] + [_VP] * 8),
     'lsi_render_planes_bwd_workspace_bytes': (_SZ, [ctypes.POINTER(LsiSceneDesc)]),

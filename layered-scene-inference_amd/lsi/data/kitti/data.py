@@ -151,12 +151,30 @@ def _load_image(path, h, w, nc=3):
   return area_resize(arr, h, w), orig
 
 
+def load_disparity_px(path, h, w):
+  """A 16-bit disparity PNG (value = disparity * 256, 0 = no match) as h x w x 1
+  float32 disparities in pixels of the h x w image: both bytes are kept
+  (value / 256), the map is sampled by nearest neighbour at the pixel centres --
+  an AREA mean would blend the matcher's empty pixels into their neighbours --
+  and multiplied by w / W_orig.  Zeros stay zeros."""
+  from PIL import Image  # pylint: disable=g-import-not-at-top
+  with Image.open(path) as im:
+    if im.mode not in ('I;16', 'I;16B', 'I;16L', 'I'):
+      raise ValueError('%s is no 16-bit disparity map (mode %s)' % (path, im.mode))
+    raw = np.asarray(im).astype(np.int64)
+  h0, w0 = raw.shape
+  ys = np.minimum(((np.arange(h) + 0.5) * h0 / h).astype(np.int64), h0 - 1)
+  xs = np.minimum(((np.arange(w) + 0.5) * w0 / w).astype(np.int64), w0 - 1)
+  disp = (raw[ys][:, xs] / 256.0 * (w / float(w0))).astype(np.float32)
+  return disp[:, :, None]
+
+
 class DataLoader(object):
   """KITTI data loading class (reference :78-385).
 
   opts needs: batch_size, kitti_data_root, kitti_dataset_variant ('raw_city',
   'mview' or 'odom'), data_split ('train' | 'val' | 'test'), img_height,
-  img_width[, kitti_dl_disparities]."""
+  img_width[, kitti_dl_disparities, kitti_dl_disparities_px]."""
 
   def __init__(self, opts):
     self.opts = opts
@@ -165,6 +183,12 @@ class DataLoader(object):
     self.output_disparities = (
         self.dataset_variant == 'raw_city' and
         bool(getattr(opts, 'kitti_dl_disparities', False)) and
+        opts.data_split != 'train')
+    # the same maps with both bytes, in pixels (load_disparity_px): appended
+    # after whatever else the batch holds
+    self.output_disparities_px = (
+        self.dataset_variant == 'raw_city' and
+        bool(getattr(opts, 'kitti_dl_disparities_px', False)) and
         opts.data_split != 'train')
     self.root_dir = opts.kitti_data_root
     if self.dataset_variant == 'odom':
@@ -240,7 +264,7 @@ class DataLoader(object):
     if self.dataset_variant == 'raw_city':
       self.img_list_trg = [f.replace('image_02', 'image_03')
                            for f in self.img_list_src]
-      if self.output_disparities:
+      if self.output_disparities or self.output_disparities_px:
         self.img_list_disp_src = []
         for im_name in self.img_list_src:
           parts = im_name.split('/')
@@ -294,13 +318,14 @@ class DataLoader(object):
     return i
 
   def forward(self, bs):
-    """bs instances: [img_s, img_t, k_s, k_t, rot, trans(, disp_s, disp_t)],
-    each stacked along the batch axis (reference :344-385)."""
+    """bs instances: [img_s, img_t, k_s, k_t, rot, trans(, disp_s, disp_t)
+    (, disp_px_s, disp_px_t)], each stacked along the batch axis (reference
+    :344-385)."""
     if self.cam_calibration is None:
       self.preload_calib_files()
     ids = [self._next_index() for _ in range(bs)]
     self.src_image_names = [self.img_list_src[i] for i in ids]
-    instances, disps_s, disps_t = [], [], []
+    instances, disps_s, disps_t, px_s, px_t = [], [], [], [], []
     for i in ids:
       img_src, src_shape = _load_image(self.img_list_src[i], self.h, self.w)
       img_trg, trg_shape = _load_image(self.img_list_trg[i], self.h, self.w)
@@ -310,8 +335,14 @@ class DataLoader(object):
       if self.output_disparities:
         disps_s.append(_load_image(self.img_list_disp_src[i], self.h, self.w, 1)[0])
         disps_t.append(_load_image(self.img_list_disp_trg[i], self.h, self.w, 1)[0])
+      if self.output_disparities_px:
+        px_s.append(load_disparity_px(self.img_list_disp_src[i], self.h, self.w))
+        px_t.append(load_disparity_px(self.img_list_disp_trg[i], self.h, self.w))
     out = [np.stack([inst[k] for inst in instances]) for k in range(6)]
     if self.output_disparities:
       out.append(np.stack(disps_s))
       out.append(np.stack(disps_t))
+    if self.output_disparities_px:
+      out.append(np.stack(px_s))
+      out.append(np.stack(px_t))
     return out

@@ -169,6 +169,11 @@ class PrefetchLoader(object):
                device=None, world_size=1):
     if resize not in ('host', 'device'):
       raise ValueError("resize must be 'host' or 'device', got %r" % (resize,))
+    if getattr(loader, 'output_disparities_px', False):
+      raise ValueError(
+          'kitti_dl_disparities_px (the pixel disparities --eval_depth scores '
+          'against) is served by the synchronous loader only: run with '
+          '--data_workers 0 --kitti_resize host')
     self.loader = loader
     self.resize = resize
     self.depth = max(1, int(prefetch_depth))

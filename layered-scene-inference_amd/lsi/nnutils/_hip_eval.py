@@ -1,7 +1,9 @@
 """ctypes bindings of the fused evaluation kernels (include/lsi_hip.h,
-csrc/lsi_eval.hip): the view-synthesis and per-layer metrics accumulated into a
-device array of SLOT_COUNT doubles, and the dis-occlusion mask.  For tensors on
-a ROCm device; there is no fallback: a missing library raises in lsi._C.lib().
+csrc/lsi_eval.hip, csrc/lsi_depth_metrics.hip): the view-synthesis and per-layer
+metrics accumulated into a device array of SLOT_COUNT doubles, the depth
+accuracy metrics into DEPTH_SLOT_COUNT doubles of their own, and the
+dis-occlusion mask.  For tensors on a ROCm device; there is no fallback: a
+missing library raises in lsi._C.lib().
 None of these calls synchronises with the host."""
 import ctypes
 
@@ -120,6 +122,72 @@ def ssim_metric(acc2, recons, target, x_min, y_min, win, sigma):
   rc = _C.lib().lsi_eval_ssim(ctypes.byref(d), _C.ptr(recons), _C.ptr(target),
                               _C.ptr(acc2), _C.ptr(ws), n, _C.stream_ptr(dev))
   _C.check(rc, 'lsi_eval_ssim')
+
+
+# the header's LSI_DEPTH_* slots of the depth accumulator (lsi_eval_depth_metrics)
+DEPTH_SLOTS = {'ABS_REL': 0, 'SQ_REL': 1, 'RMSE': 2, 'RMSE_LOG': 3, 'A1': 4, 'A2': 5,
+               'A3': 6, 'SCALE': 7, 'IMAGES': 8}
+DEPTH_SLOT_COUNT, DEPTH_PER_IMAGE = 9, 10
+LSI_DEPTH_MASK_U8, LSI_DEPTH_MEDIAN = 1, 2
+# metric name -> sum slot; the normaliser of every one is the IMAGES slot
+DEPTH_METRICS = {
+    'depth_abs_rel': 'ABS_REL', 'depth_sq_rel': 'SQ_REL', 'depth_rmse': 'RMSE',
+    'depth_rmse_log': 'RMSE_LOG', 'depth_a1': 'A1', 'depth_a2': 'A2', 'depth_a3': 'A3',
+    'depth_scale': 'SCALE',
+}
+
+
+def depth_workspace(dev, b, h, w, median):
+  n = int(_C.lib().lsi_eval_depth_workspace_bytes(b, h, w, 1 if median else 0))
+  return torch.empty((n,), dtype=torch.uint8, device=dev), n
+
+
+def depth_metrics(acc9, pred, gt, gt_scale, ws, ws_bytes, mask=None, crop=None,
+                  valid_above=0., depth_min=1e-3, depth_max=80., median=False,
+                  per_image=None):
+  """lsi_eval_depth_metrics: adds the depth accuracy of pred (B x H x W (x 1)
+  inverse depth, fp32 or bf16) against gt (the same shape, fp32) to `acc9`, 9
+  contiguous float64 on the device.  gt_scale: B fp32 on the device; mask
+  B x H x W (x 1) fp32 or bool; crop (y0, y1, x0, x1) or None for the whole
+  image; per_image: B x 10 float64 to be overwritten, or None."""
+  if pred.dtype == torch.bfloat16:
+    pred = pred.float()
+  dev = _C.require_device(pred, gt, gt_scale)
+  if (acc9.device != dev or acc9.dtype != torch.float64 or
+      acc9.numel() != DEPTH_SLOT_COUNT or not acc9.is_contiguous()):
+    raise RuntimeError('the depth accumulator is %d contiguous float64 on %s' %
+                       (DEPTH_SLOT_COUNT, dev))
+  if pred.dim() not in (3, 4):
+    raise ValueError('depth_metrics: pred must be B x H x W (x 1), got %s' %
+                     (tuple(pred.shape),))
+  b, h, w = pred.shape[:3]
+  pred = _map(pred, (b, h, w), 'pred')
+  gt = _map(gt, (b, h, w), 'gt')
+  if gt_scale.dtype != torch.float32 or tuple(gt_scale.shape) != (b,):
+    raise ValueError('depth_metrics: gt_scale must be %d fp32, got %s %s' %
+                     (b, gt_scale.dtype, tuple(gt_scale.shape)))
+  gt_scale = gt_scale.contiguous()
+  flags = LSI_DEPTH_MEDIAN if median else 0
+  if mask is not None:
+    if not mask.is_cuda or mask.device != dev:
+      raise RuntimeError('lsi HIP ops need tensors on a ROCm GPU (got device %s); '
+                         'there is no CPU fallback' % mask.device)
+    if mask.dtype in (torch.bool, torch.uint8):
+      flags |= LSI_DEPTH_MASK_U8
+    elif mask.dtype != torch.float32:
+      raise RuntimeError('the depth mask is fp32 or bool (got %s)' % mask.dtype)
+    mask = _map(mask, (b, h, w), 'mask')
+  if per_image is not None and (
+      per_image.device != dev or per_image.dtype != torch.float64 or
+      tuple(per_image.shape) != (b, DEPTH_PER_IMAGE) or not per_image.is_contiguous()):
+    raise RuntimeError('per_image is %d x %d contiguous float64 on %s' %
+                       (b, DEPTH_PER_IMAGE, dev))
+  y0, y1, x0, x1 = (0, h, 0, w) if crop is None else [int(v) for v in crop]
+  rc = _C.lib().lsi_eval_depth_metrics(
+      b, h, w, _C.ptr(pred), _C.ptr(gt), _C.ptr(mask), _C.ptr(gt_scale), y0, y1, x0,
+      x1, float(valid_above), float(depth_min), float(depth_max), flags,
+      _C.ptr(acc9), _C.ptr(per_image), _C.ptr(ws), ws_bytes, _C.stream_ptr(dev))
+  _C.check(rc, 'lsi_eval_depth_metrics')
 
 
 def _layer_desc(tex, disp, bg_layer_disp):

@@ -141,6 +141,81 @@ def layer_prediction_metrics(ldi_src, ldi_trg, imgs_src, imgs_trg, gt, opts):
   return out
 
 
+DEPTH_KEYS = ('depth_abs_rel', 'depth_sq_rel', 'depth_rmse', 'depth_rmse_log',
+              'depth_a1', 'depth_a2', 'depth_a3')
+_FLT_MIN = 1.1754943508222875e-38
+
+
+def garg_crop(h, w):
+  """The evaluation crop of Garg et al. 2016 on an h x w image as (y0, y1, x0,
+  x1), truncated as the protocol's `astype(int32)` does."""
+  return (int(0.40810811 * h), int(0.99189189 * h),
+          int(0.03594771 * w), int(0.96405229 * w))
+
+
+def _middle_mean(values):
+  """The median of a 1-d fp32 tensor as an fp64 0-d tensor: the mean of the two
+  middle order statistics (torch.median returns the lower one)."""
+  v = torch.sort(values)[0].double()
+  n = v.numel()
+  return (v[(n - 1) // 2] + v[n // 2]) / 2
+
+
+def depth_accuracy_metrics(pred, gt, gt_scale=None, mask=None, crop=None,
+                           valid_above=0., depth_min=1e-3, depth_max=80.,
+                           median=False):
+  """Depth accuracy of pred (B x H x W (x 1) inverse depth) against gt (the same
+  shape; gt_scale[b] turns it into inverse depth, default 1) in torch ops, on any
+  device: the definition of DESIGN.md 4.16, the arithmetic of
+  `MetricAccumulator.add_depth_accuracy`.  A pixel is scored where gt >
+  valid_above, inside crop = (y0, y1, x0, x1), where mask (B x H x W (x 1)) is
+  non-zero and depth_min <= 1 / (gt gt_scale) <= depth_max; with `median` the
+  predicted depths of an image are scaled by med(gt depth) / med(predicted
+  depth) over its scored pixels first.  Returns name -> (sum over the scored
+  images of the per-image figure, number of scored images) as 0-d float64
+  tensors for abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 (`depth_` in front) and,
+  with `median`, depth_scale."""
+  b, h, w = pred.shape[:3]
+  pred = pred.float().reshape(b, h, w)
+  gt = gt.float().reshape(b, h, w)
+  dev = pred.device
+  scale = (torch.ones((b,), device=dev) if gt_scale is None else
+           gt_scale.to(dev, torch.float32))
+  dg = 1.0 / (gt * scale.view(b, 1, 1))
+  valid = (gt > valid_above) & (dg >= depth_min) & (dg <= depth_max)
+  if crop is not None:
+    inside = torch.zeros((h, w), dtype=torch.bool, device=dev)
+    inside[crop[0]:crop[1], crop[2]:crop[3]] = True
+    valid = valid & inside
+  if mask is not None:
+    valid = valid & (mask.reshape(b, h, w) != 0)
+  # (pred > FLT_MIN is false for a NaN: fmaxf(pred, FLT_MIN))
+  floor = torch.full_like(pred, _FLT_MIN)
+  dp_raw = 1.0 / torch.where(pred > _FLT_MIN, pred, floor)
+  names = DEPTH_KEYS + (('depth_scale',) if median else ())
+  sums = torch.zeros((len(names),), dtype=torch.float64, device=dev)
+  n_img = 0
+  for i in range(b):
+    g, p = dg[i][valid[i]], dp_raw[i][valid[i]]
+    n = g.numel()
+    if n == 0:
+      continue
+    s = (_middle_mean(g) / _middle_mean(p)).float() if median else torch.ones((), device=dev)
+    dp = (s * p).clamp(depth_min, depth_max)
+    e = g - dp
+    r = torch.maximum(g / dp, dp / g)
+    row = [(e.abs() / g).double().sum() / n, (e * e / g).double().sum() / n,
+           ((e * e).double().sum() / n).sqrt(),
+           (((g.log() - dp.log())**2).double().sum() / n).sqrt()]
+    row += [(r < t).double().sum() / n for t in (1.25, 1.5625, 1.953125)]
+    if median:
+      row.append(s.double())
+    sums = sums + torch.stack(row)
+    n_img += 1
+  count = torch.tensor(float(n_img), dtype=torch.float64, device=dev)
+  return {k: (sums[j], count) for j, k in enumerate(names)}
+
+
 class MetricAccumulator(object):
   """The same metrics accumulated on the device by the fused kernels of
   csrc/lsi_eval.hip: every add_* call is one metric launch plus a one-block
@@ -159,6 +234,11 @@ class MetricAccumulator(object):
                            device=self.device)
     self._ws = None
     self.acc_ssim = None  # two doubles of their own, made by the first add_ssim
+    # nine doubles of their own and a workspace, made by the first add_depth_accuracy
+    self.acc_depth = None
+    self._depth_ws = (None, 0)
+    self._depth_median = False
+    self._ones = None
 
   def _workspace(self):
     if self._ws is None:
@@ -169,6 +249,8 @@ class MetricAccumulator(object):
     self.acc.zero_()
     if self.acc_ssim is not None:
       self.acc_ssim.zero_()
+    if self.acc_depth is not None:
+      self.acc_depth.zero_()
 
   def add_ssim(self, recons, imgs_trg, splat_bdry_ignore, win=11, sigma=1.5):
     """Adds the SSIM of layer 0 of a rendering (recons nl x B x Ht x Wt x 3)
@@ -183,6 +265,34 @@ class MetricAccumulator(object):
     self._hip.ssim_metric(self.acc_ssim, recons, imgs_trg,
                           loss_utils._py2_round(wt * splat_bdry_ignore),
                           loss_utils._py2_round(ht * splat_bdry_ignore), win, sigma)
+
+  def add_depth_accuracy(self, pred, gt, gt_scale=None, mask=None, crop=None,
+                         valid_above=0., depth_min=1e-3, depth_max=80.,
+                         median=False, per_image=None):
+    """`depth_accuracy_metrics` of the same arguments in the fused kernels of
+    csrc/lsi_depth_metrics.hip: the per-image figures are added to nine doubles
+    beside the 16 (lsi_eval_depth_metrics; 2 launches, 10 with `median`, no
+    host synchronisation).  `sums()` and `results()` carry the `depth_*` keys
+    once this has been called (`depth_scale` once it has been called with
+    `median`).  per_image: B x 10 float64 on the device, overwritten with each
+    image's seven figures, its scale, its number of scored pixels and 1."""
+    _C.require_device(gt, gt_scale)
+    b, h, w = pred.shape[:3]
+    if self.acc_depth is None:
+      self.acc_depth = torch.zeros((self._hip.DEPTH_SLOT_COUNT,), dtype=torch.float64,
+                                   device=self.device)
+    need = int(_C.lib().lsi_eval_depth_workspace_bytes(b, h, w, 1 if median else 0))
+    if self._depth_ws[1] < need:
+      self._depth_ws = self._hip.depth_workspace(self.device, b, h, w, median)
+    if gt_scale is None:
+      if self._ones is None or self._ones.numel() != b:
+        self._ones = torch.ones((b,), dtype=torch.float32, device=self.device)
+      gt_scale = self._ones
+    self._depth_median = self._depth_median or bool(median)
+    self._hip.depth_metrics(
+        self.acc_depth, pred, gt, gt_scale, self._depth_ws[0], self._depth_ws[1],
+        mask=mask, crop=crop, valid_above=valid_above, depth_min=depth_min,
+        depth_max=depth_max, median=median, per_image=per_image)
 
   def add_rendered(self, recons, recons_disp, imgs_trg, splat_bdry_ignore,
                    valid_mask=None, disocc_mask=None, gt_disp_trg=None,
@@ -227,12 +337,19 @@ class MetricAccumulator(object):
 
   def sums(self):
     """name -> (sum, norm) as Python floats, from ONE device-to-host copy (one
-    more for `ssim` once `add_ssim` has been called)."""
+    more for `ssim` once `add_ssim` has been called, and one for the `depth_*`
+    keys once `add_depth_accuracy` has)."""
     v = self.acc.tolist()
     slot = self._hip.SLOTS
     out = {k: (v[slot[s]], v[slot[n]]) for k, (s, n) in self._hip.METRICS.items()}
     if self.acc_ssim is not None:
       out['ssim'] = tuple(self.acc_ssim.tolist())
+    if self.acc_depth is not None:
+      d = self.acc_depth.tolist()
+      slot = self._hip.DEPTH_SLOTS
+      for k, s in self._hip.DEPTH_METRICS.items():
+        if k != 'depth_scale' or self._depth_median:
+          out[k] = (d[slot[s]], d[slot['IMAGES']])
     return out
 
   def results(self):

@@ -1417,6 +1417,53 @@ int lsi_visual_pack_u8(const LsiVisSheet* sheet, const LsiVisItem* items_host,
                        const LsiVisItem* items_dev, const uint8_t* lut_dev,
                        uint8_t* out, int64_t out_row_bytes, lsi_stream_t stream);
 
+/*
+ * Dense stereo disparities of a rectified pair by semi-global matching on a
+ * census cost (csrc/lsi_sgm.hip): all integer, a function of
+ * the input bytes alone.
+ *   left, right  [B,H,W,C] uint8, C = 1 or 3, contiguous, device
+ *   grey         C = 3: (77 R + 150 G + 29 B + 128) >> 8; C = 1: the byte
+ *   census       9 wide x 7 high around the pixel without the centre (62 bits),
+ *                a bit set where the neighbour's grey is < the centre's,
+ *                neighbour coordinates clamped to the image
+ *   cost         left view  popcount(cenL[y][x] ^ cenR[y][x - d]), 62 if x - d < 0
+ *                right view popcount(cenR[y][x] ^ cenL[y][x + d]), 62 if x + d > W - 1
+ *   paths        r in {(0, +-1), (+-1, 0)}, with paths = 8 also (+-1, +-1):
+ *                L_r(p, d) = C(p, d) + min(L_r(p - r, d), L_r(p - r, d - 1) + P1,
+ *                L_r(p - r, d + 1) + P1, m + P2) - m, m = min_k L_r(p - r, k);
+ *                terms with d +- 1 outside [0, D) are absent; L_r = C where p - r
+ *                is outside the image.  L_r <= 62 + P2 <= 255; S = sum_r L_r
+ *   winner       d0 the first argmin of S, s2 the minimum of S over |d - d0| > 1;
+ *                acceptable iff 100 S[d0] <= uniq s2 and d0 > 0
+ *   sub-pixel    0 < d0 < D - 1 and den = S[d0-1] - 2 S[d0] + S[d0+1] > 0:
+ *                off = (S[d0-1] - S[d0+1]) 128 / den (C division), else 0;
+ *                q = 256 d0 + off
+ *   left-right   lr_max >= 0: a left pixel stays iff it is acceptable,
+ *                x - dL >= 0, the right pixel (y, x - dL) is acceptable and
+ *                |dR - dL| <= lr_max on the integer winners; a right pixel alike
+ *                at (y, x + dR), x + dR <= W - 1.  lr_max < 0: every acceptable
+ *                pixel stays
+ *   disp_left, disp_right  [B,H,W] uint16, device: q where the pixel stays,
+ *                else 0 (disparity * 256, 0 = no match)
+ * D a multiple of 16 in [16, 256]; 0 <= P1 <= P2 <= 193; paths 4 or 8; uniq in
+ * [0, 100]; B H W <= 2^27 -- else LSI_EINVAL; then LSI_ENULL for a NULL
+ * pointer; then LSI_EWORKSPACE -- all before any launch.  The workspace
+ * (16-byte aligned) holds both census planes twice, one 16-bit volume
+ * S[2][B][H][W][D] that the path launches add into in place, and the winners:
+ * about B H W (4 D + 42) bytes.  4 + paths launches on `stream`, no atomics,
+ * no floating point, no host synchronisation, no state.
+ */
+/* Bytes of device scratch lsi_sgm_disparity_u8 needs; 0 for arguments the call
+ * refuses. */
+size_t lsi_sgm_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C,
+                               int32_t D, int32_t paths);
+int lsi_sgm_disparity_u8(int32_t B, int32_t H, int32_t W, int32_t C,
+                         const uint8_t* left, const uint8_t* right, int32_t D,
+                         int32_t P1, int32_t P2, int32_t paths, int32_t uniq,
+                         int32_t lr_max, uint16_t* disp_left,
+                         uint16_t* disp_right, void* workspace,
+                         size_t workspace_bytes, lsi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

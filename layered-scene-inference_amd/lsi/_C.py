@@ -263,6 +263,9 @@ SIGNATURES = {
                                              ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     'lsi_visual_pack_u8': (ctypes.c_int, [ctypes.POINTER(LsiVisSheet), _VP, _VP, _VP, _VP,
                                           _I64, _VP]),
+    'lsi_sgm_workspace_bytes': (_SZ, [_I32] * 6),
+    'lsi_sgm_disparity_u8': (ctypes.c_int, [_I32] * 4 + [_VP] * 2 + [_I32] * 6 +
+                             [_VP] * 3 + [_SZ, _VP]),
 }
 
 _lib = None

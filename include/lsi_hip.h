@@ -1464,6 +1464,46 @@ int lsi_sgm_disparity_u8(int32_t B, int32_t H, int32_t W, int32_t C,
                          uint16_t* disp_right, void* workspace,
                          size_t workspace_bytes, lsi_stream_t stream);
 
+/*
+ * Post-filters for the 16-bit disparity maps above (csrc/lsi_disp_filter.hip;
+ * DESIGN.md 4.18): all integer, a function of the input alone.
+ *   in, out      [B,H,W] uint16, contiguous, device: disparity * 256, 0 = no
+ *                match; out != in
+ *   1. median    (median = 3; 0 skips the stage) a pixel that is 0 stays 0 --
+ *                no hole filling; a valid pixel becomes the lower median of the
+ *                valid values of its 3 x 3 neighbourhood, itself included:
+ *                element (n - 1) / 2 of the n sorted values.  Neighbours
+ *                outside the image are absent.  Reads the input, writes another
+ *                buffer.
+ *   2. speckle   (speckle_size > 0; 0 skips the stage) on the output of stage 1.
+ *                Two 4-neighbours of one image (left/right, up/down) are linked
+ *                iff both are non-zero and |a - b| <= speckle_range, the
+ *                difference taken in a wider integer.  Components are the
+ *                transitive closure of the links, never across the images of a
+ *                batch nor from the end of a row to the start of the next.  A
+ *                valid pixel whose component has <= speckle_size pixels becomes
+ *                0; every other pixel is unchanged.
+ *   Both stages off: out is a copy of in.
+ * B, H, W >= 1 and B H W <= 2^27; median 0 or 3; 0 <= speckle_size <= 2^27;
+ * 0 <= speckle_range <= 65535 (units of 1/256 px); out != in -- else
+ * LSI_EINVAL; then LSI_ENULL for a NULL in or out, or a NULL workspace where
+ * one is needed; then LSI_EWORKSPACE -- all before any launch.  Workspace
+ * (16-byte aligned), only with speckle_size > 0: a 4-byte parent and a 4-byte
+ * size per pixel, plus the 2-byte median plane (rounded up to 16 bytes) when
+ * both stages run.  At most 5 launches on `stream`, their number independent
+ * of the data; components are labelled by a lock-free union-find (LDS atomics
+ * inside 32 x 32 tiles, agent-scope atomics across their edges).  No host
+ * synchronisation, no allocation, no state.
+ */
+/* Bytes of device scratch lsi_disparity_filter_u16 needs; 0 for arguments the
+ * call refuses (and where speckle_size = 0: no scratch is needed). */
+size_t lsi_disparity_filter_workspace_bytes(int32_t B, int32_t H, int32_t W,
+                                            int32_t median, int32_t speckle_size);
+int lsi_disparity_filter_u16(int32_t B, int32_t H, int32_t W, const uint16_t* in,
+                             uint16_t* out, int32_t median, int32_t speckle_size,
+                             int32_t speckle_range, void* workspace,
+                             size_t workspace_bytes, lsi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

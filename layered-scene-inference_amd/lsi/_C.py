@@ -266,6 +266,9 @@ SIGNATURES = {
     'lsi_sgm_workspace_bytes': (_SZ, [_I32] * 6),
     'lsi_sgm_disparity_u8': (ctypes.c_int, [_I32] * 4 + [_VP] * 2 + [_I32] * 6 +
                              [_VP] * 3 + [_SZ, _VP]),
+    'lsi_disparity_filter_workspace_bytes': (_SZ, [_I32] * 5),
+    'lsi_disparity_filter_u16': (ctypes.c_int, [_I32] * 3 + [_VP] * 2 + [_I32] * 3 +
+                                 [_VP, _SZ, _VP]),
 }
 
 _lib = None

@@ -3,13 +3,16 @@
 
     python -m lsi.data.kitti.preprocess --kitti_data_root ROOT
         [--max_disp 128 --p1 10 --p2 120 --paths 8 --uniqueness 95 --lr_max 1]
+        [--median 0 --speckle_size 0 --speckle_range 256]
         [--workers 8 --overwrite false --sequences a,b,...]
 
 For every stereo pair of the raw_city sequences (the frame the loader excludes
 is skipped) it decodes image_02 / image_03 on a pool of threads, runs the
 semi-global matcher of lsi.geometry.stereo on the device at the files' own
-resolution, and writes both views' maps as 16-bit PNGs (disparity * 256, 0 = no
-match) to
+resolution, optionally post-filters both maps there (--median 3: a 3 x 3 median
+of the valid values; --speckle_size N: components of at most N pixels are
+removed; both off by default), and writes both views'
+maps as 16-bit PNGs (disparity * 256, 0 = no match) to
 
     ROOT/kitti_raw/spss_stereo_results/<sequence>_sync/
         <frame>_{left,right}_initial_disparity.png
@@ -17,6 +20,8 @@ match) to
 -- the paths data.DataLoader builds.  The reference produces these files with an
 external SPS-stereo executable; the maps written here are this project's own
 matcher's output in the same format (DESIGN.md section 4.17), not SPS-stereo's.
+With --overwrite false a file that exists is kept whatever settings and filters
+it was written with.
 
 The device never waits for a PNG: decodes run ahead of the matcher, and a
 result's download is only waited for by the worker thread that encodes it.
@@ -93,8 +98,10 @@ def _encode_pair(event, host_l, host_r, out_l, out_r):
 
 
 def run(root, max_disp=128, p1=10, p2=120, paths=8, uniqueness=95, lr_max=1, workers=8,
-        overwrite=False, sequences=None, device='cuda', log=None):
-  """Matches every pair under `root`; returns (pairs written, pairs skipped)."""
+        overwrite=False, sequences=None, device='cuda', log=None, median=0,
+        speckle_size=0, speckle_range=256):
+  """Matches every pair under `root`; returns (pairs written, pairs skipped).
+  median, speckle_size, speckle_range: stereo.filter_disparity's, off by default."""
   import torch  # pylint: disable=g-import-not-at-top
   from lsi.geometry import stereo  # pylint: disable=g-import-not-at-top
   dev = torch.device(device)
@@ -125,7 +132,8 @@ def run(root, max_disp=128, p1=10, p2=120, paths=8, uniqueness=95, lr_max=1, wor
         with torch.cuda.device(dev):
           d_l, d_r = stereo.sgm_disparity(
               torch.from_numpy(img_l).to(dev), torch.from_numpy(img_r).to(dev),
-              max_disp, p1, p2, paths, uniqueness, lr_max)
+              max_disp, p1, p2, paths, uniqueness, lr_max, median, speckle_size,
+              speckle_range)
           host_l = torch.empty(d_l.shape, dtype=torch.uint16, pin_memory=True)
           host_r = torch.empty(d_r.shape, dtype=torch.uint16, pin_memory=True)
           host_l.copy_(d_l, non_blocking=True)
@@ -165,7 +173,16 @@ def build_parser():
   p.add_argument('--lr_max', type=int, default=1)
   p.add_argument('--workers', type=int, default=8,
                  help='decode / encode threads, at most %d' % pipeline.MAX_THREADS)
-  p.add_argument('--overwrite', type=_bool, default=False)
+  p.add_argument('--median', type=int, default=0, choices=(0, 3),
+                 help='3: a 3 x 3 median over the valid values after the matcher; 0: off')
+  p.add_argument('--speckle_size', type=int, default=0,
+                 help='remove connected components of at most this many pixels; 0: off')
+  p.add_argument('--speckle_range', type=int, default=256,
+                 help='neighbours belong to one component when they differ by at most '
+                      'this much, in 1/256 px')
+  p.add_argument('--overwrite', type=_bool, default=False,
+                 help='false skips a pair whose files exist, whatever settings and '
+                      'filters they were written with')
   p.add_argument('--sequences', default='',
                  help='comma-separated sequence names; default: all of raw_city')
   p.add_argument('--device', default='cuda')
@@ -178,7 +195,8 @@ def main(argv=None):
   t0 = time.time()
   done, skipped = run(a.kitti_data_root, a.max_disp, a.p1, a.p2, a.paths, a.uniqueness,
                       a.lr_max, a.workers, a.overwrite, seqs, a.device,
-                      log=lambda m: print(m, flush=True))
+                      log=lambda m: print(m, flush=True), median=a.median,
+                      speckle_size=a.speckle_size, speckle_range=a.speckle_range)
   print('%d pairs matched, %d already there, %.1f s' % (done, skipped, time.time() - t0))
   return 0
 

@@ -364,6 +364,11 @@ int lsi_project_indices(const LsiSplatDesc* desc, const float* disp,
  * of a C-channel image at float coordinates onto an initial canvas.
  *   src [B,Hs,Ws,C], coords [B,Hs,Ws,2] (x,y), out [B,Ht,Wt,C]; all contiguous.
  * `out` must already hold init_trg_image; updates are added to it in place.
+ * Sizes, for this and the bilinear entry points below (LSI_EINVAL otherwise,
+ * before any pointer is looked at): B <= 65535; the canvas (here) or the
+ * sampled image (there) has fewer than 2^24 pixels; the number of points,
+ * Hs*Ws here and Ht*Wt there, is at most 2^31 - 256.  A point with a non-finite
+ * coordinate adds and samples nothing and gets zero gradients.
  */
 int lsi_splat_generic(int32_t B, int32_t Hs, int32_t Ws, int32_t C, int32_t Ht,
                       int32_t Wt, const float* src, const float* coords,

@@ -222,8 +222,10 @@ __global__ __launch_bounds__(256) void bilinear_taps_bwd_kernel(
       gx = (g2 * t.wy0 + g3 * t.wy1) - (g0 * t.wy0 + g1 * t.wy1);
       gy = (g1 * t.wx0 + g3 * t.wx1) - (g0 * t.wx0 + g2 * t.wx1);
     }
-    g_coords[2 * ti] = gx;
-    g_coords[2 * ti + 1] = gy;
+    // a non-finite point gets no gradient (its weights are NaN), like
+    // bilinear_bwd_kernel
+    g_coords[2 * ti] = t.ok ? gx : 0.f;
+    g_coords[2 * ti + 1] = t.ok ? gy : 0.f;
   }
   if (!g_imgs || !g_taps || !t.ok) return;
   float* gb = g_imgs + (size_t)b * Hs * Ws * C;
@@ -241,6 +243,12 @@ __global__ __launch_bounds__(256) void bilinear_taps_bwd_kernel(
 
 inline int launch_rc() {
   return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+}
+
+// The kernels index their points with `int i = blockIdx.x * 256 + threadIdx.x`:
+// the point count, rounded up to whole blocks, has to fit in int32.
+inline bool points_fit(int32_t h, int32_t w) {
+  return (int64_t)h * w <= (int64_t)INT32_MAX - 255;
 }
 
 }  // namespace
@@ -274,7 +282,7 @@ int lsi_splat_generic(int32_t B, int32_t Hs, int32_t Ws, int32_t C, int32_t Ht,
                       int32_t Wt, const float* src, const float* coords,
                       float* out, lsi_stream_t stream) {
   if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0 ||
-      B > 65535 || (int64_t)Ht * Wt >= (1 << 24))
+      B > 65535 || (int64_t)Ht * Wt >= (1 << 24) || !points_fit(Hs, Ws))
     return LSI_EINVAL;
   if (!src || !coords || !out) return LSI_ENULL;
   const int Ns = Hs * Ws;
@@ -288,7 +296,7 @@ int lsi_splat_generic_bwd(int32_t B, int32_t Hs, int32_t Ws, int32_t C,
                           const float* coords, const float* g_out, float* g_src,
                           float* g_coords, lsi_stream_t stream) {
   if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0 ||
-      B > 65535 || (int64_t)Ht * Wt >= (1 << 24))
+      B > 65535 || (int64_t)Ht * Wt >= (1 << 24) || !points_fit(Hs, Ws))
     return LSI_EINVAL;
   if (!src || !coords || !g_out) return LSI_ENULL;
   const int Ns = Hs * Ws;
@@ -312,7 +320,7 @@ int lsi_bilinear_fwd(int32_t B, int32_t Hs, int32_t Ws, int32_t C, int32_t Ht,
                      int32_t Wt, const float* imgs, const float* coords,
                      float* out, lsi_stream_t stream) {
   if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0 ||
-      B > 65535 || (int64_t)Hs * Ws >= (1 << 24))
+      B > 65535 || (int64_t)Hs * Ws >= (1 << 24) || !points_fit(Ht, Wt))
     return LSI_EINVAL;
   if (!imgs || !coords || !out) return LSI_ENULL;
   const int Nt = Ht * Wt;
@@ -325,7 +333,7 @@ int lsi_bilinear_taps(int32_t B, int32_t Hs, int32_t Ws, int32_t C, int32_t Ht,
                       int32_t Wt, const float* imgs, const float* coords,
                       float* taps, float* wts, lsi_stream_t stream) {
   if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0 ||
-      B > 65535 || (int64_t)Hs * Ws >= (1 << 24))
+      B > 65535 || (int64_t)Hs * Ws >= (1 << 24) || !points_fit(Ht, Wt))
     return LSI_EINVAL;
   if (!imgs || !coords || !taps || !wts) return LSI_ENULL;
   const int Nt = Ht * Wt;
@@ -340,7 +348,7 @@ int lsi_bilinear_taps_bwd(int32_t B, int32_t Hs, int32_t Ws, int32_t C, int32_t 
                           const float* g_wts, float* g_imgs, float* g_coords,
                           lsi_stream_t stream) {
   if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0 ||
-      B > 65535 || (int64_t)Hs * Ws >= (1 << 24))
+      B > 65535 || (int64_t)Hs * Ws >= (1 << 24) || !points_fit(Ht, Wt))
     return LSI_EINVAL;
   if (!coords) return LSI_ENULL;
   if (g_imgs && !g_taps) return LSI_ENULL;
@@ -356,7 +364,7 @@ int lsi_bilinear_bwd(int32_t B, int32_t Hs, int32_t Ws, int32_t C, int32_t Ht,
                      const float* g_out, float* g_imgs, float* g_coords,
                      lsi_stream_t stream) {
   if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0 ||
-      B > 65535 || (int64_t)Hs * Ws >= (1 << 24))
+      B > 65535 || (int64_t)Hs * Ws >= (1 << 24) || !points_fit(Ht, Wt))
     return LSI_EINVAL;
   if (!imgs || !coords || !g_out) return LSI_ENULL;
   const int Nt = Ht * Wt;

@@ -118,6 +118,63 @@ def test_argument_errors_are_reported_before_any_launch(built_lib):
   assert lib.lsi_scatter_add(1, 8, 0, null, null, null, null) == 0
 
 
+def test_sampling_entry_points_refuse_before_any_launch(built_lib):
+  """The seven entry points of csrc/lsi_sampling.hip with NULL pointers: sizes
+  are judged first (-1, LSI_EINVAL), then the required pointers (-2,
+  LSI_ENULL); neither answer touches the device."""
+  from lsi import _C
+  lib = _C.lib()
+  one = ctypes.c_void_p(64)     # non-NULL, never dereferenced: a NULL follows it
+  # name -> (number of pointers before the stream, the required ones, which of
+  #          Hs x Ws / Ht x Wt is the image or canvas limited to 2^24)
+  entries = {
+      'lsi_splat_generic': (3, (0, 1, 2), 'trg'),
+      'lsi_splat_generic_bwd': (5, (0, 1, 2), 'trg'),
+      'lsi_bilinear_fwd': (3, (0, 1, 2), 'src'),
+      'lsi_bilinear_bwd': (5, (0, 1, 2), 'src'),
+      'lsi_bilinear_taps': (4, (0, 1, 2, 3), 'src'),
+      'lsi_bilinear_taps_bwd': (5, (0,), 'src'),
+  }
+  for name, (nptr, required, limited) in entries.items():
+    fn = getattr(lib, name)
+    call = lambda b, hs, ws, c, ht, wt, ptrs=None: fn(
+        b, hs, ws, c, ht, wt, *((ptrs or [None] * nptr) + [None]))
+    assert call(1, 4, 4, 3, 4, 4) == -2, name
+    assert call(0, 4, 4, 3, 4, 4) == -1, name
+    assert call(65536, 4, 4, 3, 4, 4) == -1, name
+    assert call(65535, 4, 4, 3, 4, 4) == -2, name
+    for dims in ((1, 0, 4, 3, 4, 4), (1, 4, -1, 3, 4, 4), (1, 4, 4, 0, 4, 4),
+                 (1, 4, 4, 3, 0, 4), (1, 4, 4, 3, 4, 0)):
+      assert call(*dims) == -1, (name, dims)
+    # the sampled image / the canvas: an area of 2^24 is refused, 2^24 - 1 is not
+    area = lambda h, w: (1, h, w, 3, 4, 4) if limited == 'src' else (1, 4, 4, 3, h, w)
+    assert call(*area(4096, 4096)) == -1, name
+    assert call(*area(1, (1 << 24) - 1)) == -2, name
+    # the point count on the other side has to fit the kernels' int32 index
+    pts = lambda h, w: (1, 4, 4, 3, h, w) if limited == 'src' else (1, h, w, 3, 4, 4)
+    assert call(*pts(65536, 65536)) == -1, name
+    assert call(*pts(32768, 65536)) == -1, name            # 2^31
+    assert call(*pts(1, 0x7fffffff)) == -1, name           # whole blocks do not fit
+    assert call(*pts(1, 0x7fffffff - 255)) == -2, name
+    assert call(*pts(32768, 65535)) == -2, name
+    # each required pointer on its own
+    for miss in required:
+      ptrs = [None if k == miss else one for k in range(nptr)]
+      assert call(1, 4, 4, 3, 4, 4, ptrs) == -2, (name, miss)
+  # lsi_bilinear_taps_bwd(coords, g_taps, g_wts, g_imgs, g_coords): an image
+  # gradient cannot be formed without the taps' incoming gradient
+  assert lib.lsi_bilinear_taps_bwd(1, 4, 4, 3, 4, 4, one, None, one, one, None,
+                                   None) == -2
+  # lsi_scatter_add(B, P, N, idx, upd, out)
+  sa = lambda b, p, n, ptrs=(None, None, None): lib.lsi_scatter_add(b, p, n, *ptrs, None)
+  assert sa(1, 8, 0) == 0 and sa(65535, 8, 0) == 0
+  assert sa(0, 8, 4) == -1 and sa(65536, 8, 4) == -1
+  assert sa(1, 0, 4) == -1 and sa(1, 8, -1) == -1
+  assert sa(1, 8, 4) == -2
+  for miss in range(3):
+    assert sa(1, 8, 4, [None if k == miss else one for k in range(3)]) == -2, miss
+
+
 def test_no_cpu_fallback(built_lib):
   from lsi.geometry import ldi, sampling
   tex = torch.rand(1, 1, 8, 8, 3)

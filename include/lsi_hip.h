@@ -1509,6 +1509,64 @@ int lsi_disparity_filter_u16(int32_t B, int32_t H, int32_t W, const uint16_t* in
                              int32_t speckle_range, void* workspace,
                              size_t workspace_bytes, lsi_stream_t stream);
 
+/*
+ * LiDAR scans rasterised into depth maps (csrc/lsi_lidar.hip):
+ * a scatter with a z-buffer, a function of its inputs alone.
+ *   desc_host, desc_dev  the same B descriptors in host and in device memory:
+ *                scan b is the points [first, first + n) of `pts`.  Padded
+ *                batches (first = b Nmax) and packed ones use the same form.
+ *   pts          [n_pts_total, 4] float x y z reflectance, device, 16-byte
+ *                aligned; may be NULL only when every n is 0
+ *   mats         [B, V, 12] float, device: a 3 x 4 row-major matrix per scan
+ *                and view
+ *   projection   all fp32, in this order, never contracted:
+ *                X = ((m0 x + m1 y) + m2 z) + m3, Y and Z from rows 1 and 2;
+ *                kept iff Z >= z_min && Z <= z_max (a NaN drops the point);
+ *                u = X / Z, v = Y / Z, correctly rounded; kept iff
+ *                u >= 0 && u < W && v >= 0 && v < H as floats; the pixel is
+ *                (floorf(v), floorf(u))
+ *   z-buffer     a pixel's depth is the smallest Z that lands on it (positive
+ *                floats order as their bit patterns: an unsigned atomic
+ *                minimum, independent of the order of points and threads)
+ *   filter       on iff win_y > 0 || win_x > 0.  mn = the minimum of the
+ *                unfiltered z-buffer over the non-empty pixels of
+ *                [r - win_y, r + win_y] x [c - win_x, c + win_x] clipped to the
+ *                image; a non-empty pixel of depth z becomes empty iff
+ *                mn * occl_ratio < z (one fp32 multiply, one compare).  Not
+ *                iterative, not in place.
+ *   out          [B, V, H, W] float, device, written fully: the depth, with
+ *                LSI_LIDAR_INVERSE 1.0f / depth (correctly rounded), 0 where
+ *                the pixel is empty
+ * LSI_EINVAL for B outside [1, 65535], V not 1 or 2, H or W < 1,
+ * B V H W > 2^27, win_y or win_x outside [0, 8], n_pts_total outside
+ * [0, 2^27], a descriptor with n < 0, first < 0, first + n > n_pts_total or a
+ * non-zero reserved, !(0 < z_min <= z_max) or a non-finite bound,
+ * !(occl_ratio >= 1) with a window on, unknown flags, a pts that is not
+ * 16-byte aligned; then LSI_ENULL; then LSI_EWORKSPACE -- all before any
+ * launch.  Workspace: the z-buffer, 4 bytes per pixel of out.  3 launches on
+ * `stream` whatever the data (scans without points included: out is zeros);
+ * the window minimum is taken per LSI_LIDAR_TILE_H x LSI_LIDAR_TILE_W tile in
+ * LDS.  No host synchronisation, no allocation, no state.
+ */
+#define LSI_LIDAR_INVERSE 1u /* out holds 1 / depth                           */
+#define LSI_LIDAR_TILE_H 16
+#define LSI_LIDAR_TILE_W 64
+typedef struct LsiScanDesc { /* one scan of a batch */
+  int64_t first;             /* index of its first point in `pts` (points, not bytes) */
+  int32_t n;                 /* number of points, >= 0 */
+  int32_t reserved;          /* 0 */
+} LsiScanDesc;
+/* Bytes of device scratch lsi_lidar_rasterize needs; 0 for arguments the call
+ * refuses. */
+size_t lsi_lidar_workspace_bytes(int32_t B, int32_t V, int32_t H, int32_t W,
+                                 int32_t win_y, int32_t win_x);
+int lsi_lidar_rasterize(int32_t B, int32_t V, int32_t H, int32_t W,
+                        const LsiScanDesc* desc_host, const LsiScanDesc* desc_dev,
+                        const float* pts, int64_t n_pts_total, const float* mats,
+                        float z_min, float z_max, int32_t win_y, int32_t win_x,
+                        float occl_ratio, uint32_t flags, float* out,
+                        void* workspace, size_t workspace_bytes, lsi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

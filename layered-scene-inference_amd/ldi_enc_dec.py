@@ -59,6 +59,11 @@ def build_parser():
     'disparities of both views in pixels of the resized image, both bytes of the '
     '16-bit PNG, nearest-neighbour sampled (the ground truth of --eval_depth; '
     'the synchronous loader only)')
+  a('--kitti_dl_velodyne', type=_bool, default=False,
+    help='under the conditions of --kitti_dl_disparities: append the Velodyne '
+    'scan of every pair (velodyne_points/data/N.bin, NaN-padded), its point '
+    'count and the two 3 x 4 projections into the resized views (the standard '
+    'ground truth of --eval_depth; the synchronous loader only)')
   a('--kitti_procedural', type=_bool, default=False,
     help='no KITTI files: procedural stereo pairs seen through the KITTI camera '
     'model and constants (throughput runs, tests).  Without this switch a '
@@ -278,7 +283,10 @@ class KittiBatches(object):
     return self.loader.src_image_names
 
   def forward(self, bs):
-    return tuple(torch.as_tensor(a, dtype=torch.float32)
+    # (integer outputs -- the point counts of --kitti_dl_velodyne -- stay integers)
+    # (a prefetching loader hands on tensors: their dtype has no `kind`)
+    return tuple(torch.as_tensor(a) if getattr(getattr(a, 'dtype', None), 'kind', None)
+                 in ('i', 'u') else torch.as_tensor(a, dtype=torch.float32)
                  for a in self.loader.forward(bs))
 
   def close(self):

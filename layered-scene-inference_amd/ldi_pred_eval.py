@@ -69,8 +69,10 @@ def build_parser():
     "LDI's disparities) with the seven standard figures: depth_abs_rel, "
     'depth_sq_rel, depth_rmse, depth_rmse_log, depth_a1 .. depth_a3 in the '
     'results (DESIGN.md 4.16).  Synthetic planes: against the ground-truth '
-    'disparities; KITTI: against the SPS-stereo disparities in pixels '
-    '(--kitti_dl_disparities_px true)')
+    'disparities; KITTI: against the Velodyne scans rasterised into both views '
+    '(--kitti_dl_velodyne true: the protocol of Eigen et al. / Garg et al.) or '
+    'against the SPS-stereo disparities in pixels (--kitti_dl_disparities_px '
+    'true), one of the two')
   a('--depth_min', type=float, default=1e-3,
     help='--eval_depth: ground-truth depths outside [depth_min, depth_max] are '
     'not scored, predicted depths are clamped to it')
@@ -80,6 +82,16 @@ def build_parser():
   a('--depth_median_scale', type=train_script._bool, default=False,
     help="--eval_depth: scale every image's predicted depths by the ratio of the "
     'medians first; `depth_scale` in the results is the mean factor')
+  a('--lidar_origin', type=float, default=0.0,
+    help='--kitti_dl_velodyne: the pixel a projected point belongs to is '
+    'floor(x + 0.5 - origin) of its KITTI coordinate x.  0: the pixel whose area '
+    "holds it; 1: the monodepth evaluation script's `round(x) - 1`")
+  a('--lidar_occl_window', type=int, nargs=2, default=[0, 0], metavar=('Y', 'X'),
+    help='--kitti_dl_velodyne: half height and half width of the occlusion filter\'s '
+    'window, 0 .. 8 each; 0 0 = no filter (lsi.geometry.lidar)')
+  a('--lidar_occl_ratio', type=float, default=1.25,
+    help='--kitti_dl_velodyne with a window: a return is dropped when the '
+    "window's nearest depth times this is nearer than it (>= 1)")
   a('--save_visuals', type=int, default=0,
     help='write a contact sheet of batch element 0 for the first N iterations: '
     '<results_dir>/visuals/iter_%%06d.png, index.html, visuals.json')
@@ -166,6 +178,12 @@ class Tester(object):
   """Template of test_utils.py:69-255 for the LDI predictor."""
 
   def __init__(self, opts):
+    if (getattr(opts, 'kitti_dl_velodyne', False) and
+        getattr(opts, 'kitti_dl_disparities_px', False)):
+      raise ValueError(
+          '--kitti_dl_velodyne and --kitti_dl_disparities_px both name a ground '
+          'truth for --eval_depth: pick the Velodyne scans (the standard '
+          'protocol) or the stereo disparities, not both')
     self.opts = opts
     self.device = torch.device('cpu' if opts.cpu or not torch.cuda.is_available()
                                else 'cuda')
@@ -220,20 +238,24 @@ class Tester(object):
     # ground truth by data set (ldi_pred_eval.py:226-262): synthetic planes
     # carry 14 outputs (fg / bg disparities and background textures), KITTI
     # with --kitti_dl_disparities 8 (the SPS-stereo disparities of both views)
-    gt, kitti_disp, kitti_px = None, None, None
-    n_px = 2 if (o.dataset == 'kitti' and len(batch) > 6 and
+    gt, kitti_disp, kitti_px, kitti_velo = None, None, None, None
+    n_tail = 2 if (o.dataset == 'kitti' and len(batch) > 6 and
                  getattr(o, 'kitti_dl_disparities_px', False)) else 0
+    if o.dataset == 'kitti' and len(batch) > 6 and getattr(o, 'kitti_dl_velodyne', False):
+      # --kitti_dl_velodyne: the last three outputs (points, counts, matrices)
+      n_tail = 3
+      kitti_velo = (batch[-3].to(dev), batch[-2], batch[-1].to(dev))
     if o.dataset == 'synthetic' and len(batch) >= 14:
       (_, _, d_s_fg, d_s_bg, d_t_fg, d_t_bg, img_s_bg, img_t_bg) = batch[6:14]
       gt = {'src_gt_disp': d_s_fg.to(dev), 'trg_gt_disp': d_t_fg.to(dev),
             'src_gt_disp_bg': d_s_bg.to(dev), 'trg_gt_disp_bg': d_t_bg.to(dev),
             'src_gt_tex_bg': img_s_bg.to(dev), 'trg_gt_tex_bg': img_t_bg.to(dev)}
-    elif o.dataset == 'kitti' and len(batch) - n_px == 8:
+    elif o.dataset == 'kitti' and len(batch) - n_tail == 8:
       kitti_disp = {'src': batch[6].to(dev), 'trg': batch[7].to(dev)}
-    elif len(batch) - n_px != 6:
+    elif len(batch) - n_tail != 6:
       raise ValueError('unexpected batch layout: %d outputs for dataset %r' %
                        (len(batch), o.dataset))
-    if n_px:  # --kitti_dl_disparities_px: the last two outputs
+    if n_tail == 2:  # --kitti_dl_disparities_px: the last two outputs
       kitti_px = {'src': batch[-2].to(dev), 'trg': batch[-1].to(dev)}
     out, views = [], {}
     for ldi, k_a, k_b, r, t, target, key in (
@@ -280,12 +302,14 @@ class Tester(object):
         out.append(eval_metrics.layer_prediction_metrics(
             ldi_src, ldi_trg, imgs_src, imgs_trg, gt, o))
     if getattr(o, 'eval_depth', False):
-      out += self.eval_depth(acc, ldi_src, ldi_trg, k_s, k_t, trans, gt, kitti_px)
+      out += self.eval_depth(acc, ldi_src, ldi_trg, k_s, k_t, trans, gt, kitti_px,
+                             kitti_velo)
     if visuals is not None:
       visuals.save(imgs_src, imgs_trg, ldi_src, ldi_trg, views, gt)
     return out
 
-  def eval_depth(self, acc, ldi_src, ldi_trg, k_s, k_t, trans, gt, kitti_px):
+  def eval_depth(self, acc, ldi_src, ldi_trg, k_s, k_t, trans, gt, kitti_px,
+                 kitti_velo=None):
     """--eval_depth: the predicted inverse depth of each input view (layer 0 of
     its LDI's disparities) against that view's ground truth; with `acc` through
     the fused kernels, else the op route's dicts."""
@@ -300,10 +324,23 @@ class Tester(object):
       maps = {'src': (kitti_px['src'], (1.0 / (k_s[:, 0, 0] * t_x)).float().to(dev)),
               'trg': (kitti_px['trg'], (1.0 / (k_t[:, 0, 0] * t_x)).float().to(dev))}
       valid_above = 0.
+    elif kitti_velo is not None:
+      # the scans rasterised into both views as inverse depths, 0 = no return
+      # (the HIP rasteriser on either metric route)
+      from lsi.geometry import lidar  # pylint: disable=g-import-not-at-top
+      pts, counts, mats = kitti_velo
+      inv = lidar.rasterize_points(
+          pts.float(), None, counts, mats.float(), o.img_height, o.img_width,
+          z_min=o.depth_min, z_max=o.depth_max,
+          occl_window=tuple(getattr(o, 'lidar_occl_window', (0, 0))),
+          occl_ratio=getattr(o, 'lidar_occl_ratio', 1.0), inverse=True)
+      maps = {'src': (inv[:, 0].contiguous(), None), 'trg': (inv[:, 1].contiguous(), None)}
+      valid_above = 0.
     else:
       raise ValueError(
           '--eval_depth needs ground-truth depth: --synth_scene planes, or KITTI '
-          'raw_city (val / test) with --kitti_dl_disparities_px true')
+          'raw_city (val / test) with --kitti_dl_velodyne true (Velodyne scans) or '
+          '--kitti_dl_disparities_px true (stereo disparities)')
     kw = dict(crop=(eval_metrics.garg_crop(o.img_height, o.img_width)
                     if o.depth_crop == 'garg' else None),
               valid_above=valid_above, depth_min=o.depth_min, depth_max=o.depth_max,

@@ -29,6 +29,8 @@ LSI_FC_BN, LSI_FC_X_F32, LSI_FC_OUT_F32 = 1, 2, 4
 LSI_IMAGE_MAX_PIXELS = 16843009
 LSI_VIS_SKIP, LSI_VIS_RGB, LSI_VIS_GRAY, LSI_VIS_LUT, LSI_VIS_ABSDIFF = 0, 1, 2, 3, 4
 LSI_VIS_MAX_ITEMS = 256
+LSI_LIDAR_INVERSE = 1
+LSI_LIDAR_TILE_H, LSI_LIDAR_TILE_W = 16, 64
 PATH_NAMES = {1: 'atomic', 2: 'rowband', 3: 'stream', 4: 'tile'}
 
 _c_f = ctypes.POINTER(ctypes.c_float)
@@ -126,6 +128,11 @@ class LsiVisSheet(ctypes.Structure):
                                              'gutter', 'n_items')] +
               [('bg', ctypes.c_uint8 * 3), ('nan', ctypes.c_uint8 * 3),
                ('reserved', ctypes.c_uint8 * 2)])
+
+
+class LsiScanDesc(ctypes.Structure):
+  _fields_ = [('first', ctypes.c_int64), ('n', ctypes.c_int32),
+              ('reserved', ctypes.c_int32)]
 
 
 class LsiVisItem(ctypes.Structure):
@@ -269,6 +276,11 @@ SIGNATURES = {
     'lsi_disparity_filter_workspace_bytes': (_SZ, [_I32] * 5),
     'lsi_disparity_filter_u16': (ctypes.c_int, [_I32] * 3 + [_VP] * 2 + [_I32] * 3 +
                                  [_VP, _SZ, _VP]),
+    'lsi_lidar_workspace_bytes': (_SZ, [_I32] * 6),
+    'lsi_lidar_rasterize': (ctypes.c_int, [_I32] * 4 + [_VP] * 3 + [_I64, _VP, _F32, _F32,
+                                                                  _I32, _I32, _F32,
+                                                                  ctypes.c_uint32] +
+                            [_VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

@@ -174,7 +174,8 @@ class DataLoader(object):
 
   opts needs: batch_size, kitti_data_root, kitti_dataset_variant ('raw_city',
   'mview' or 'odom'), data_split ('train' | 'val' | 'test'), img_height,
-  img_width[, kitti_dl_disparities, kitti_dl_disparities_px]."""
+  img_width[, kitti_dl_disparities, kitti_dl_disparities_px, kitti_dl_velodyne,
+  lidar_origin]."""
 
   def __init__(self, opts):
     self.opts = opts
@@ -190,6 +191,13 @@ class DataLoader(object):
         self.dataset_variant == 'raw_city' and
         bool(getattr(opts, 'kitti_dl_disparities_px', False)) and
         opts.data_split != 'train')
+    # the Velodyne scan of every pair with its two projections (velodyne.py):
+    # three more outputs after everything else
+    self.output_velodyne = (
+        self.dataset_variant == 'raw_city' and
+        bool(getattr(opts, 'kitti_dl_velodyne', False)) and
+        opts.data_split != 'train')
+    self.lidar_origin = float(getattr(opts, 'lidar_origin', 0.0))
     self.root_dir = opts.kitti_data_root
     if self.dataset_variant == 'odom':
       self.root_dir = os.path.join(self.root_dir, 'odometry', 'dataset',
@@ -205,6 +213,7 @@ class DataLoader(object):
     self.w = opts.img_width
     self.init_img_names_seq_list()
     self.cam_calibration = None
+    self.velo_calibration = None
     self._order, self._cursor = None, 0
     self._rng = np.random.RandomState(0)
     self.src_image_names = []
@@ -273,6 +282,13 @@ class DataLoader(object):
               parts[-1][:-4] + '_left_initial_disparity.png'))
         self.img_list_disp_trg = [f.replace('left', 'right')
                                   for f in self.img_list_disp_src]
+      if self.output_velodyne:
+        # .../image_02/data/N.png -> .../velodyne_points/data/N.bin
+        self.scan_list = [
+            os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(f))),
+                         'velodyne_points', 'data',
+                         os.path.basename(f)[:-4] + '.bin')
+            for f in self.img_list_src]
     else:
       self.img_list_trg = [f.replace('image_2', 'image_3')
                            for f in self.img_list_src]
@@ -299,6 +315,12 @@ class DataLoader(object):
       for seq_date in sorted(set(self.seq_id_list)):
         self.cam_calibration[seq_date] = read_calib_file(os.path.join(
             self.root_dir, seq_date, 'calib_cam_to_cam.txt'))
+        if self.output_velodyne:
+          from lsi.data.kitti import velodyne  # pylint: disable=g-import-not-at-top
+          if self.velo_calibration is None:
+            self.velo_calibration = {}
+          self.velo_calibration[seq_date] = velodyne.read_velo_calib(os.path.join(
+              self.root_dir, seq_date, 'calib_velo_to_cam.txt'))
 
   # -- batches ----------------------------------------------------------------
   def forward_instance(self, img_src, img_trg, src_shape, trg_shape, calib_data):
@@ -319,13 +341,19 @@ class DataLoader(object):
 
   def forward(self, bs):
     """bs instances: [img_s, img_t, k_s, k_t, rot, trans(, disp_s, disp_t)
-    (, disp_px_s, disp_px_t)], each stacked along the batch axis (reference
-    :344-385)."""
+    (, disp_px_s, disp_px_t)(, velo_pts, velo_n, velo_mats)], each stacked along
+    the batch axis (reference :344-385).  velo_pts [bs, Nmax, 4] float32: the
+    scans, rows past a scan's count NaN, Nmax the longest count rounded up to a
+    multiple of 4 (at least 4); velo_n [bs] int32: the counts, 0 for a frame
+    whose scan file is missing (KITTI raw lacks a few); velo_mats [bs, 2, 12]
+    float32: velodyne.velo_to_image into view 0 = camera 2 / source and view 1 =
+    camera 3 / target."""
     if self.cam_calibration is None:
       self.preload_calib_files()
     ids = [self._next_index() for _ in range(bs)]
     self.src_image_names = [self.img_list_src[i] for i in ids]
     instances, disps_s, disps_t, px_s, px_t = [], [], [], [], []
+    scans, velo_mats = [], []
     for i in ids:
       img_src, src_shape = _load_image(self.img_list_src[i], self.h, self.w)
       img_trg, trg_shape = _load_image(self.img_list_trg[i], self.h, self.w)
@@ -338,6 +366,16 @@ class DataLoader(object):
       if self.output_disparities_px:
         px_s.append(load_disparity_px(self.img_list_disp_src[i], self.h, self.w))
         px_t.append(load_disparity_px(self.img_list_disp_trg[i], self.h, self.w))
+      if self.output_velodyne:
+        from lsi.data.kitti import velodyne  # pylint: disable=g-import-not-at-top
+        scans.append(velodyne.load_scan(self.scan_list[i])
+                     if os.path.exists(self.scan_list[i]) else
+                     np.zeros((0, 4), np.float32))
+        seq = self.seq_id_list[i]
+        velo_mats.append(np.stack([
+            velodyne.velo_to_image(self.cam_calibration[seq], self.velo_calibration[seq],
+                                   cam, shape, self.h, self.w, self.lidar_origin).reshape(12)
+            for cam, shape in ((2, src_shape), (3, trg_shape))]))
     out = [np.stack([inst[k] for inst in instances]) for k in range(6)]
     if self.output_disparities:
       out.append(np.stack(disps_s))
@@ -345,4 +383,11 @@ class DataLoader(object):
     if self.output_disparities_px:
       out.append(np.stack(px_s))
       out.append(np.stack(px_t))
+    if self.output_velodyne:
+      counts = np.array([len(s) for s in scans], np.int32)
+      n_max = max(4, (int(counts.max()) + 3) // 4 * 4)
+      pts = np.full((bs, n_max, 4), np.nan, np.float32)
+      for k, scan in enumerate(scans):
+        pts[k, :len(scan)] = scan
+      out += [pts, counts, np.stack(velo_mats)]
     return out

@@ -174,6 +174,11 @@ class PrefetchLoader(object):
           'kitti_dl_disparities_px (the pixel disparities --eval_depth scores '
           'against) is served by the synchronous loader only: run with '
           '--data_workers 0 --kitti_resize host')
+    if getattr(loader, 'output_velodyne', False):
+      raise ValueError(
+          'kitti_dl_velodyne (the Velodyne scans --eval_depth scores against) is '
+          'served by the synchronous loader only: run with --data_workers 0 '
+          '--kitti_resize host')
     self.loader = loader
     self.resize = resize
     self.depth = max(1, int(prefetch_depth))

@@ -609,6 +609,68 @@ int lsi_edge_smooth_loss_bwd(const LsiEdgeSmoothDesc* desc, const float* disp,
                              lsi_stream_t stream);
 
 /*
+ * Sparse depth-supervision loss (csrc/lsi_depth_sup.hip; no reference
+ * counterpart, the definition is DESIGN.md section 4.20): the scale-invariant
+ * log error of Eigen et al. 2014, or a plain L1, of predicted inverse depths
+ * against a ground-truth map that is mostly holes.  pred [P,H,W] with the
+ * element strides p_s*, gt [P,H,W] with the element strides g_s*, gt_scale P
+ * device floats or NULL: g = gt * gt_scale[p] (one fp32 product; gt itself when
+ * NULL) is the ground truth as inverse depth -- the convention of
+ * lsi_eval_depth_metrics.  Pixel i of plane p is scored, a function of the
+ * ground truth alone, when gt > valid_above and g_min <= g <= g_max (the caller
+ * computes g_min = 1 / depth_max, g_max = 1 / depth_min once, in fp32); a NaN
+ * ground truth fails every comparison.  n_p = scored pixels of plane p, S =
+ * planes with n_p > 0.  q = fmaxf(pred, eps): a NaN prediction becomes eps.
+ *   LSI_DEPTH_SUP_SILOG  d_i = logf(q_i) - logf(g_i) in fp32; in fp64
+ *                        A_p = sum d_i, Q_p = sum d_i d_i (d_i widened, then
+ *                        squared), D_p = Q_p / n_p - lambda (A_p / n_p)^2
+ *                        loss = 1 / S sum_{n_p > 0} D_p
+ *                        dloss/dpred_i = 1 / S (2 d_i / n_p - 2 lambda A_p /
+ *                                        n_p^2) / q_i
+ *   LSI_DEPTH_SUP_L1     e_i = q_i - g_i in fp32, A_p = sum |e_i| in fp64, Q_p = 0
+ *                        loss = 1 / S sum_{n_p > 0} A_p / n_p
+ *                        dloss/dpred_i = sign(e_i) / (n_p S), sign(0) = 0
+ * The gradient is that where i is scored and pred_i > eps, 0 elsewhere; the
+ * ground truth is data.  S = 0: loss 0, gradient all zeros.  No Inf or NaN
+ * leaves either direction for finite or NaN inputs.  A pixel that is not scored
+ * costs no read of pred, in either direction.
+ * LSI_EINVAL for an unknown mode, non-positive dimensions (H W < 2^31),
+ * g_min <= 0, g_max < g_min, valid_above < 0, eps <= 0, lambda outside [0, 1]
+ * or a non-finite scalar; then LSI_ENULL (only gt_scale may be NULL); then
+ * LSI_EWORKSPACE -- all before any launch.  No atomics, no host
+ * synchronisation, no allocation: the same inputs give the same bits, and both
+ * directions can be captured in a HIP graph.
+ */
+#define LSI_DEPTH_SUP_SILOG 0
+#define LSI_DEPTH_SUP_L1 1
+typedef struct LsiDepthSupDesc {
+  int32_t P, H, W, mode;
+  int64_t p_sp, p_sy, p_sx;
+  int64_t g_sp, g_sy, g_sx;
+  float valid_above, g_min, g_max, eps, lam; /* lam: lambda above */
+  int32_t reserved;
+} LsiDepthSupDesc;
+
+/* (3 P bpp + P) doubles: a block covers r = max(ceil(1024 / W), ceil(H / 256))
+ * rows of a plane, bpp = ceil(H / r) blocks per plane; 0 for a descriptor the
+ * entries below refuse. */
+size_t lsi_depth_sup_workspace_bytes(const LsiDepthSupDesc* desc);
+/* 2 launches.  out_loss (one device float) = the loss; plane_sums (3 P device
+ * doubles, the caller's) = n_p, A_p, Q_p at [3 p .. 3 p + 2]: written by the
+ * finishing kernel, read by the backward.  The library keeps no state. */
+int lsi_depth_sup_loss_fwd(const LsiDepthSupDesc* desc, const float* pred,
+                           const float* gt, const float* gt_scale,
+                           float* out_loss, double* plane_sums, void* workspace,
+                           size_t workspace_bytes, lsi_stream_t stream);
+/* 1 launch.  g_pred [P,H,W] contiguous, scaled by the device scalar g_loss;
+ * validity and d_i are recomputed from the inputs, S from plane_sums.  Every
+ * element is written. */
+int lsi_depth_sup_loss_bwd(const LsiDepthSupDesc* desc, const float* pred,
+                           const float* gt, const float* gt_scale,
+                           const double* plane_sums, const float* g_loss,
+                           float* g_pred, lsi_stream_t stream);
+
+/*
  * layers.compose, lsi/geometry/layers.py:29-70 with helpers.soft_z_buffering
  * (lsi/nnutils/helpers.py:140-160): white background layer at min_disp,
  * per-pixel softmax of log(mask + 1e-8) - depth / temp over the L + 1 layers,

@@ -39,6 +39,27 @@ def _bool(v):
   return str(v).lower() in ('1', 'true', 'yes')
 
 
+DEPTH_SUP_SOURCES = (
+    "--dataset synthetic with --synth_scene planes or planes_batched (the scenes' "
+    'foreground disparities), KITTI files with --kitti_dl_disparities_px true '
+    '(stereo disparities) or KITTI files with --kitti_dl_velodyne true (Velodyne '
+    'scans, rasterised on the device)')
+
+
+def depth_sup_source(opts):
+  """Where --depth_sup_wt > 0 takes its ground truth from: 'planes', 'px' or
+  'velodyne'; ValueError for a configuration that has none."""
+  if opts.dataset == 'synthetic' and opts.synth_scene in ('planes', 'planes_batched'):
+    return 'planes'
+  if opts.dataset == 'kitti' and not opts.kitti_procedural:
+    px = bool(getattr(opts, 'kitti_dl_disparities_px', False))
+    velodyne = bool(getattr(opts, 'kitti_dl_velodyne', False))
+    if px != velodyne:
+      return 'px' if px else 'velodyne'
+  raise ValueError('--depth_sup_wt > 0 needs ground-truth depth from exactly one of: '
+                   + DEPTH_SUP_SOURCES)
+
+
 def build_parser():
   p = argparse.ArgumentParser(description=__doc__)
   train_utils.define_default_flags(p)
@@ -103,6 +124,20 @@ def build_parser():
   a('--edge_smooth_guide', default='image', choices=['image', 'texture'],
     help="'image': every layer is guided by the view's input image; 'texture': "
     'each layer by its own predicted texture, detached')
+  a('--depth_sup_wt', type=float, default=0.0,
+    help='weight of the depth-supervision term against sparse ground truth '
+    '(csrc/lsi_depth_sup.hip, DESIGN.md 4.20): depth_sup_wt * depth_sup_loss is '
+    'added to the total; it supervises layer 0 of each view\'s disparities.  '
+    'Ground truth: ' + DEPTH_SUP_SOURCES + '.  0 = no such term, no extra '
+    'loader output')
+  a('--depth_sup_mode', default='silog', choices=['silog', 'l1'],
+    help='the scale-invariant log error of Eigen et al. 2014, or a plain L1')
+  a('--depth_sup_lambda', type=float, default=0.5,
+    help='silog: mean(d^2) - lambda mean(d)^2, 0 <= lambda <= 1')
+  a('--depth_sup_min', type=float, default=1e-3,
+    help='ground truth nearer than this depth is not scored')
+  a('--depth_sup_max', type=float, default=80.,
+    help='ground truth beyond this depth is not scored')
   a('--zbuf_scale', type=float, default=50)
   a('--trg_splat_downsampling', type=float, default=0.5)
   a('--disp_smoothness_wt', type=float, default=0.1)
@@ -301,6 +336,9 @@ class Trainer(train_utils.Trainer):
 
   def define_data_loader(self):
     opts = self.opts
+    # (decided before a loader is built: a loader emits ground truth on request)
+    self.depth_sup_source = (depth_sup_source(opts)
+                             if getattr(opts, 'depth_sup_wt', 0.0) > 0 else None)
     if opts.dataset == 'synthetic' and (opts.synth_scene in ('planes',
                                                              'planes_batched') or
                                         opts.debug_synth_texture):
@@ -309,6 +347,7 @@ class Trainer(train_utils.Trainer):
         raise ValueError('debug_synth_texture feeds (fg, bg) disparities: '
                          'n_layers must be 2')
       opts.synth_dl_eval_data = (bool(opts.debug_synth_texture) or
+                                 self.depth_sup_source == 'planes' or
                                  bool(getattr(opts, 'synth_dl_eval_data', False)))
       loader = (synthetic_planes.BatchedDataLoader
                 if opts.synth_scene == 'planes_batched' else
@@ -345,23 +384,40 @@ class Trainer(train_utils.Trainer):
   def build_model(self):
     return LdiNet(self.opts)
 
+  def _depth_sup_outputs(self, batch):
+    """The loader outputs --depth_sup_wt > 0 builds its ground truth from."""
+    src = self.depth_sup_source
+    if src == 'planes' and len(batch) >= 14:
+      return (src, batch[8], batch[10])        # disp_s_fg, disp_t_fg
+    if src == 'px' and len(batch) >= 8:
+      return (src, batch[-2], batch[-1])
+    if src == 'velodyne' and len(batch) >= 9:
+      return (src, batch[-3], batch[-2], batch[-1])  # points, counts, matrices
+    raise ValueError(
+        '--depth_sup_wt > 0: the loader emitted %d outputs, none of them ground '
+        'truth (the KITTI loader emits it on the val / test splits only).  The '
+        'term takes it from: %s' % (len(batch), DEPTH_SUP_SOURCES))
+
   def feed(self):
     """One batch: (img_src, img_trg, k_s, k_t, rot, trans); with
     debug_synth_texture also the ground-truth LDI disparities (reference
-    ldi_enc_dec.py:230-263)."""
+    ldi_enc_dec.py:230-263); with --depth_sup_wt > 0 a seventh entry, the loader
+    outputs `stage` makes the term's ground truth from."""
     batch = self.data_loader.forward(self.opts.batch_size)
     self.gt_disps = None
     if self.opts.debug_synth_texture:
       (_, _, _, _, _, _, _, _, d_s_fg, d_s_bg, d_t_fg, d_t_bg, _, _) = batch
       self.gt_disps = (torch.stack([d_s_fg, d_s_bg], 0),
                        torch.stack([d_t_fg, d_t_bg], 0))
+    if getattr(self, 'depth_sup_source', None) is not None:
+      return tuple(batch[:6]) + (self._depth_sup_outputs(batch),)
     return tuple(batch[:6])
 
   def stage(self, batch):
     """Images to the device; the two src->trg projection matrices are built on
     the host (tiny), kept there for the kernel-family choice and copied to the
     device.  plan = what the renderer would choose for these cameras."""
-    imgs_src, imgs_trg, k_s, k_t, rot_mat, trans_mat = batch
+    imgs_src, imgs_trg, k_s, k_t, rot_mat, trans_mat = batch[:6]
     f32 = lambda t: t.detach().to('cpu', torch.float32)
     k_s, k_t, rot_mat, trans_mat = f32(k_s), f32(k_t), f32(rot_mat), f32(trans_mat)
     inv_rot_mat = nn_helpers.transpose(rot_mat)
@@ -392,7 +448,30 @@ class Trainer(train_utils.Trainer):
     if getattr(self, 'gt_disps', None) is not None:
       # (part of the staged batch: a captured HIP graph replays on static copies)
       staged += [self.gt_disps[0].to(dev), self.gt_disps[1].to(dev)]
+    if len(batch) > 6:
+      staged += self._stage_depth_sup(batch[6], k_s, k_t, trans_mat, up)
     return staged, plan
+
+  def _stage_depth_sup(self, outputs, k_s, k_t, trans_mat, up):
+    """The depth-supervision ground truth of a batch, on the device: [gt] or
+    [gt, gt_scale], gt 2 B x H x W x 1 -- the source views', then the target
+    views' -- in the conventions of Evaluator.eval_depth."""
+    o = self.opts
+    if outputs[0] == 'planes':   # inverse depths already
+      return [torch.cat([up(outputs[1].float()), up(outputs[2].float())], dim=0)]
+    if outputs[0] == 'px':
+      # pixel disparities d = f_x |t_x| / depth, each view with its own intrinsics
+      t_x = trans_mat[:, 0, 0].abs()
+      scale = torch.cat([1.0 / (k_s[:, 0, 0] * t_x), 1.0 / (k_t[:, 0, 0] * t_x)])
+      return [torch.cat([up(outputs[1].float()), up(outputs[2].float())], dim=0),
+              up(scale.float())]
+    # the scans rasterised into both views as inverse depths, 0 = no return
+    from lsi.geometry import lidar  # pylint: disable=g-import-not-at-top
+    pts, counts, mats = outputs[1:]
+    inv = lidar.rasterize_points(
+        up(pts.float()), None, counts, up(mats.float()), o.img_height, o.img_width,
+        z_min=o.depth_sup_min, z_max=o.depth_sup_max, inverse=True)
+    return [torch.cat([inv[:, 0], inv[:, 1]], dim=0)]
 
   def compute_losses(self, staged):
     opts = self.opts
@@ -538,6 +617,28 @@ class Trainer(train_utils.Trainer):
         edge_smooth_loss = (edge_loss(ldi_src, imgs_src) +
                             edge_loss(ldi_trg, imgs_trg))
 
+    # depth supervision of layer 0 (no reference counterpart)
+    dsup_wt = getattr(opts, 'depth_sup_wt', 0.0)
+    if dsup_wt > 0:
+      source = getattr(self, 'depth_sup_source', None)
+      if source is None:
+        raise ValueError('--depth_sup_wt > 0 needs ground-truth depth from: ' +
+                         DEPTH_SUP_SOURCES)
+      gt2, scale2 = (staged[-2:] if source == 'px' else (staged[-1], None))
+
+      def depth_loss(disps, gt, scale):
+        return loss.depth_supervision_loss(
+            disps[0], gt, scale, mode=opts.depth_sup_mode, lam=opts.depth_sup_lambda,
+            valid_above=opts.bg_layer_disp if source == 'planes' else 0.,
+            depth_min=opts.depth_sup_min, depth_max=opts.depth_sup_max)
+      if paired:
+        depth_sup_loss = 2.0 * depth_loss(pair[2], gt2, scale2)
+      else:
+        b = imgs_src.shape[0]
+        half = lambda t, k: None if t is None else t[k * b:(k + 1) * b]
+        depth_sup_loss = (depth_loss(ldi_src[2], half(gt2, 0), half(scale2, 0)) +
+                          depth_loss(ldi_trg[2], half(gt2, 1), half(scale2, 1)))
+
     total = zero
     if opts.self_cons_wt > 0:
       total = total + opts.self_cons_wt * self_cons_loss
@@ -558,6 +659,8 @@ class Trainer(train_utils.Trainer):
       # normalised, the term is scale-free; else both orders are linear in d
       total = total + (edge_wt if opts.edge_smooth_norm
                        else edge_wt / opts.max_disp) * edge_smooth_loss
+    if dsup_wt > 0:
+      total = total + dsup_wt * depth_sup_loss
     scalars = {
         'self_cons_loss': self_cons_loss,
         'compose_splat_loss': compose_splat_loss,
@@ -571,6 +674,8 @@ class Trainer(train_utils.Trainer):
       scalars['indep_ssim_loss'] = indep_ssim_loss
     if edge_wt > 0:
       scalars['edge_smooth_loss'] = edge_smooth_loss
+    if dsup_wt > 0:
+      scalars['depth_sup_loss'] = depth_sup_loss
     return total, scalars
 
 

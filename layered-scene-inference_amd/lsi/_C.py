@@ -30,6 +30,7 @@ LSI_IMAGE_MAX_PIXELS = 16843009
 LSI_VIS_SKIP, LSI_VIS_RGB, LSI_VIS_GRAY, LSI_VIS_LUT, LSI_VIS_ABSDIFF = 0, 1, 2, 3, 4
 LSI_VIS_MAX_ITEMS = 256
 LSI_LIDAR_INVERSE = 1
+LSI_DEPTH_SUP_SILOG, LSI_DEPTH_SUP_L1 = 0, 1
 LSI_LIDAR_TILE_H, LSI_LIDAR_TILE_W = 16, 64
 PATH_NAMES = {1: 'atomic', 2: 'rowband', 3: 'stream', 4: 'tile'}
 
@@ -84,6 +85,14 @@ class LsiEdgeSmoothDesc(ctypes.Structure):
       [(n, ctypes.c_int64) for n in ('d_sl', 'd_sb', 'd_sy', 'd_sx',
                                      'g_sl', 'g_sb', 'g_sy', 'g_sx', 'g_sc')] +
       [(n, ctypes.c_float) for n in ('alpha', 'eps')])
+
+
+class LsiDepthSupDesc(ctypes.Structure):
+  _fields_ = (
+      [(n, ctypes.c_int32) for n in ('P', 'H', 'W', 'mode')] +
+      [(n, ctypes.c_int64) for n in ('p_sp', 'p_sy', 'p_sx', 'g_sp', 'g_sy', 'g_sx')] +
+      [(n, ctypes.c_float) for n in ('valid_above', 'g_min', 'g_max', 'eps', 'lam')] +
+      [('reserved', ctypes.c_int32)])
 
 
 class LsiConvDesc(ctypes.Structure):
@@ -200,6 +209,11 @@ SIGNATURES = {
                                  [_VP] * 5 + [_SZ, _VP]),
     'lsi_edge_smooth_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiEdgeSmoothDesc)] +
                                  [_VP] * 6),
+    'lsi_depth_sup_workspace_bytes': (_SZ, [ctypes.POINTER(LsiDepthSupDesc)]),
+    'lsi_depth_sup_loss_fwd': (ctypes.c_int, [ctypes.POINTER(LsiDepthSupDesc)] +
+                               [_VP] * 6 + [_SZ, _VP]),
+    'lsi_depth_sup_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiDepthSupDesc)] +
+                               [_VP] * 7),
     'lsi_compose_fwd': (ctypes.c_int, [_I32, _I64, _I32] + [_VP] * 3 +
                         [_I32, _F32, _F32, _VP, _VP]),
     'lsi_compose_depth_fwd': (ctypes.c_int, [_I32, _I64] + [_VP] * 2 +

@@ -332,6 +332,110 @@ def edge_smoothness_loss(disp, guide, alpha, order, normalise):
                            bool(normalise))
 
 
+# launches of the depth-supervision kernels through this binding
+CALLS.update({'depth_sup_fwd': 0, 'depth_sup_bwd': 0})
+DEPTH_SUP_MODES = {'silog': _C.LSI_DEPTH_SUP_SILOG, 'l1': _C.LSI_DEPTH_SUP_L1}
+
+
+def depth_sup_desc(pred, gt, gt_scale, mode, lam, valid_above, g_min, g_max, eps,
+                   what):
+  """The LsiDepthSupDesc of pred P x H x W against gt P x H x W (any strides) and
+  gt_scale (P floats or None); RuntimeError for a wrong shape or dtype,
+  ValueError for what the kernels would refuse with LSI_EINVAL."""
+  for name, t in (('pred', pred), ('gt', gt), ('gt_scale', gt_scale)):
+    if t is not None and t.dtype != torch.float32:
+      raise RuntimeError('%s: %s is fp32 (got %s)' % (what, name, t.dtype))
+  if pred.dim() != 3 or tuple(gt.shape) != tuple(pred.shape):
+    raise RuntimeError('%s: pred and gt are P x H x W, of one shape (got %s and %s)'
+                       % (what, tuple(pred.shape), tuple(gt.shape)))
+  p, h, w = pred.shape
+  if gt_scale is not None and tuple(gt_scale.shape) != (p,):
+    raise RuntimeError('%s: gt_scale holds one float per plane, %s (got %s)' %
+                       (what, (p,), tuple(gt_scale.shape)))
+  if mode not in DEPTH_SUP_MODES:
+    raise ValueError("%s: the mode is 'silog' or 'l1' (got %r)" % (what, mode))
+  if min(p, h, w) < 1:
+    raise ValueError('%s: empty maps (%s)' % (what, tuple(pred.shape)))
+  lam, valid_above, g_min, g_max, eps = (float(lam), float(valid_above),
+                                         float(g_min), float(g_max), float(eps))
+  inf = float('inf')
+  if not 0.0 <= lam <= 1.0:
+    raise ValueError('%s: lambda lies in [0, 1] (got %r)' % (what, lam))
+  if not 0.0 <= valid_above < inf:
+    raise ValueError('%s: valid_above is finite and >= 0 (got %r)' %
+                     (what, valid_above))
+  if not 0.0 < g_min <= g_max < inf:
+    raise ValueError('%s: 0 < 1 / depth_max <= 1 / depth_min < inf (got %r, %r)' %
+                     (what, g_min, g_max))
+  if not 0.0 < eps < inf:
+    raise ValueError('%s: eps is finite and > 0 (got %r)' % (what, eps))
+  d = _C.LsiDepthSupDesc()
+  d.P, d.H, d.W, d.mode = p, h, w, DEPTH_SUP_MODES[mode]
+  d.p_sp, d.p_sy, d.p_sx = pred.stride()
+  d.g_sp, d.g_sy, d.g_sx = gt.stride()
+  d.valid_above, d.g_min, d.g_max, d.eps, d.lam = valid_above, g_min, g_max, eps, lam
+  return d
+
+
+class _DepthSup(torch.autograd.Function):
+  """lsi_depth_sup_loss_fwd / _bwd."""
+
+  @staticmethod
+  def forward(ctx, pred, gt, gt_scale, mode, lam, valid_above, g_min, g_max, eps):
+    d = depth_sup_desc(pred, gt, gt_scale, mode, lam, valid_above, g_min, g_max,
+                       eps, 'depth_supervision_loss')
+    dev = _C.require_device(pred, gt, gt_scale)
+    if gt_scale is not None:
+      gt_scale = gt_scale.contiguous()
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    sums = torch.empty((3 * d.P,), dtype=torch.float64, device=dev)
+    n = int(_C.lib().lsi_depth_sup_workspace_bytes(ctypes.byref(d)))
+    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+    CALLS['depth_sup_fwd'] += 1
+    rc = _C.lib().lsi_depth_sup_loss_fwd(ctypes.byref(d), _C.ptr(pred), _C.ptr(gt),
+                                         _C.ptr(gt_scale), _C.ptr(out),
+                                         _C.ptr(sums), _C.ptr(ws), n,
+                                         _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_depth_sup_loss_fwd')
+    ctx.save_for_backward(pred, gt, sums,
+                          gt_scale if gt_scale is not None else pred.new_empty(0))
+    ctx.has_scale = gt_scale is not None
+    ctx.desc = d
+    ctx.mark_non_differentiable(sums)
+    return out, sums
+
+  @staticmethod
+  def backward(ctx, g, _):
+    pred, gt, sums, gt_scale = ctx.saved_tensors
+    gt_scale = gt_scale if ctx.has_scale else None
+    dev = pred.device
+    g = g.contiguous().float()
+    g_pred = torch.empty(tuple(pred.shape), dtype=torch.float32, device=dev)
+    CALLS['depth_sup_bwd'] += 1
+    rc = _C.lib().lsi_depth_sup_loss_bwd(ctypes.byref(ctx.desc), _C.ptr(pred),
+                                         _C.ptr(gt), _C.ptr(gt_scale), _C.ptr(sums),
+                                         _C.ptr(g), _C.ptr(g_pred),
+                                         _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_depth_sup_loss_bwd')
+    return (g_pred,) + (None,) * 8
+
+
+def depth_supervision_loss(pred, gt, gt_scale, mode, lam, valid_above, g_min, g_max,
+                           eps, return_plane_sums=False):
+  """Depth supervision of pred P x H x W (any strides, never copied) against the
+  sparse ground truth gt P x H x W, gt_scale P floats or None; the gradient is
+  w.r.t. pred only.  return_plane_sums: also the 3 P doubles (n_p, A_p, Q_p)
+  the forward left for the backward."""
+  # the ground truth is data, as the target of zbuffer_composition_loss
+  for name, t in (('gt', gt), ('gt_scale', gt_scale)):
+    if torch.is_tensor(t) and t.requires_grad:
+      raise RuntimeError('depth_supervision_loss: %s is not differentiable on the '
+                         'HIP path (pass %s.detach())' % (name, name))
+  out, sums = _DepthSup.apply(pred, gt, gt_scale, mode, lam, valid_above, g_min,
+                              g_max, eps)
+  return (out, sums) if return_plane_sums else out
+
+
 class _Compose(torch.autograd.Function):
   """lsi_compose_fwd / lsi_compose_bwd on imgs [L,N,C], masks [L,N], dmaps
   [L,N] (contiguous fp32)."""

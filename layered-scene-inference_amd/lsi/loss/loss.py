@@ -100,3 +100,49 @@ def edge_aware_smoothness_loss(pred_disp, guide_imgs, alpha=1.0, order=1,
   (lsi_edge_smooth_loss_fwd / _bwd); the gradient is w.r.t. pred_disp only."""
   from lsi.loss import _hip  # pylint: disable=g-import-not-at-top
   return _hip.edge_smoothness_loss(pred_disp, guide_imgs, alpha, order, normalise)
+
+
+def _planes(t, name):
+  """[..., H, W, 1] or [..., H, W] as a P x H x W view (never a copy).  A last
+  dimension of 1 is the channel from four dimensions on; three are P x H x W."""
+  if t.dim() >= 4 and t.shape[-1] == 1:
+    t = t[..., 0]
+  if t.dim() < 2:
+    raise RuntimeError('depth_supervision_loss: %s is [..., H, W, 1] or [..., H, W] '
+                       '(got %s)' % (name, tuple(t.shape)))
+  h, w = t.shape[-2:]
+  try:
+    return t.view(-1, h, w)
+  except RuntimeError:
+    raise RuntimeError('depth_supervision_loss: the leading dimensions of %s (%s, '
+                       'strides %s) do not flatten without a copy' %
+                       (name, tuple(t.shape), t.stride())) from None
+
+
+def depth_supervision_loss(pred_disp, gt, gt_scale=None, mode='silog', lam=0.5,
+                           valid_above=0., depth_min=1e-3, depth_max=80., eps=1e-6):
+  """Depth supervision against sparse ground truth (the
+  reference has none): predicted inverse depths pred_disp and a ground-truth
+  map gt, both [..., H, W, 1] or [..., H, W] with equal leading dimensions
+  (flattened to P planes as views; a last dimension of 1 is the channel from four
+  dimensions on); g = gt * gt_scale[p] (P floats, or gt itself)
+  is the ground truth as inverse depth, the convention of
+  eval_metrics.depth_accuracy_metrics.  A pixel is scored -- by the ground truth
+  alone -- when gt > valid_above and 1 / depth_max <= g <= 1 / depth_min (both in
+  fp32); a NaN is a hole.  q = max(pred, eps), a NaN prediction is eps.
+  mode 'silog' (Eigen et al. 2014): d = log q - log g, per plane mean(d^2) -
+  lam mean(d)^2 over its scored pixels; 'l1': per plane mean |q - g|; the loss is
+  the mean over the planes that hold a scored pixel, 0 if none does.  One fused
+  HIP launch each way plus a one-block finish (lsi_depth_sup_loss_fwd / _bwd);
+  the gradient is w.r.t. pred_disp only, 0 at pixels that are not scored or are
+  clamped at eps."""
+  import numpy as np  # pylint: disable=g-import-not-at-top
+  from lsi.loss import _hip  # pylint: disable=g-import-not-at-top
+  pred, gt = _planes(pred_disp, 'pred_disp'), _planes(gt, 'gt')
+  if not (depth_min > 0 and depth_max >= depth_min):
+    raise ValueError('depth_supervision_loss: 0 < depth_min <= depth_max (got %r, '
+                     '%r)' % (depth_min, depth_max))
+  one = np.float32(1.0)
+  g_min, g_max = float(one / np.float32(depth_max)), float(one / np.float32(depth_min))
+  return _hip.depth_supervision_loss(pred, gt, gt_scale, mode, lam, valid_above,
+                                     g_min, g_max, eps)

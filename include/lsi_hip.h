@@ -1420,6 +1420,44 @@ int lsi_area_resize_u8(int32_t n, const LsiImageDesc* desc_host,
                        float* out, lsi_stream_t stream);
 
 /*
+ * lsi_area_resize_u8 with a per-image crop window, horizontal flip, tone
+ * table and channel gains, still one launch: with
+ * win = img[y0 : y0 + ch, x0 : x0 + cw] and tone(v, c) = table[c][v] (or v),
+ *   acc[i, k, c] = sum_yx oy ox tone(win[y, x, c], c)   (uint32, exact; the
+ *                  integer overlaps of lsi_area_resize_u8 with ch, cw for H, W)
+ *   val          = min(fl(fl((float)acc * fl(1 / (255 ch cw))) * gain[c]), 1)
+ *   out[m, i, flip ? Wo - 1 - k : k, c] = val
+ * A full window, no flip, table -1 and gains of 1 give the bits of
+ * lsi_area_resize_u8 (wherever those do not exceed 1).
+ *   packed    as for lsi_area_resize_u8; image rows stay W C bytes apart.  It
+ *             also holds the tone tables: n_tables records of uint8[Co][256]
+ *             from byte tables_offset (a multiple of 16), so descriptors,
+ *             tables and pixels travel in one upload.  n_tables may be 0.
+ *   desc_*    as for lsi_area_resize_u8, of LsiAugmentDesc
+ * Refused like lsi_area_resize_u8 (with the int32 bounds on (Ho + 1)(ch + 1),
+ * (Wo + 1)(cw + 1)); LSI_EINVAL as well for a window that is empty or leaves
+ * the image, flags other than LSI_AUG_FLIP, a table outside [-1, n_tables),
+ * n_tables outside [0, 65535], tables that are misaligned or leave the buffer,
+ * a gain[c < Co] that is negative, infinite or NaN -- all before any launch.
+ */
+#define LSI_AUG_FLIP 1u
+typedef struct LsiAugmentDesc {
+  int64_t offset;         /* bytes from `packed`, a multiple of 16           */
+  int32_t H, W, C;        /* the image's own size; C == Co                   */
+  uint32_t flags;         /* LSI_AUG_FLIP or 0                               */
+  int32_t y0, x0, ch, cw; /* the crop window, in source pixels               */
+  int32_t table;          /* index of the image's tone table; -1 = identity  */
+  int32_t reserved;       /* 0                                               */
+  float gain[3];          /* per channel, finite and >= 0; gain[0] for C = 1 */
+  int32_t reserved2;      /* 0                                               */
+} LsiAugmentDesc;          /* 64 bytes                                        */
+int lsi_augment_resize_u8(int32_t n, const LsiAugmentDesc* desc_host,
+                          const LsiAugmentDesc* desc_dev, const uint8_t* packed,
+                          size_t packed_bytes, int64_t tables_offset,
+                          int32_t n_tables, int32_t Ho, int32_t Wo, int32_t Co,
+                          float* out, lsi_stream_t stream);
+
+/*
  * Contact sheet of visuals, one launch: n_items fp32 device
  * tensors, each with its own size, strides and value range, are quantised to
  * bytes and laid out on a grid of rows x cols cells of cell_h x cell_w pixels

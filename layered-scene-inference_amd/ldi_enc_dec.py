@@ -97,6 +97,23 @@ def build_parser():
     help="KITTI files: the AREA resize in NumPy ('host') or as one HIP launch "
     "per batch on the decoded uint8 pixels ('device': csrc/lsi_image.hip; "
     'needs a ROCm device)')
+  a('--kitti_augment', type=_bool, default=False,
+    help='KITTI files, training: augment every stereo pair -- random crop, '
+    'horizontal flip and colour, images and cameras together (lsi/data/kitti/'
+    'augment.py, DESIGN.md 4.12b); fused into the resize launch with '
+    '--kitti_resize device.  false: the --aug_* values are not read')
+  a('--aug_flip_prob', type=float, default=0.5)
+  a('--aug_zoom_max', type=float, default=1.15,
+    help='the crop window is the image divided by a zoom in [1, this] per '
+    'axis, placed at random; 1 = no crop')
+  a('--aug_color_prob', type=float, default=0.5,
+    help='probability of a colour change: gamma, brightness and per-channel '
+    'factors from the three ranges below')
+  a('--aug_gamma', type=float, nargs=2, default=[0.8, 1.2], metavar=('LO', 'HI'))
+  a('--aug_brightness', type=float, nargs=2, default=[0.5, 2.0], metavar=('LO', 'HI'))
+  a('--aug_color', type=float, nargs=2, default=[0.8, 1.2], metavar=('LO', 'HI'))
+  a('--aug_seed', type=int, default=0,
+    help='seed of the augmentation draws (every rank draws its own sequence)')
   a('--self_cons_wt', type=float, default=1.0)
   a('--l0_self_cons', type=_bool, default=False)
   a('--indep_splat_wt', type=float, default=1.0)
@@ -312,6 +329,9 @@ class KittiBatches(object):
     self.loader = loader
     # every rank walks the data in its own order
     loader._rng = __import__('numpy').random.RandomState(rank)
+    if getattr(loader, 'augment', None) is not None:   # --kitti_augment
+      loader._aug_rng = __import__('numpy').random.RandomState(
+          [int(loader.aug_seed), rank])
 
   @property
   def src_image_names(self):
@@ -339,6 +359,12 @@ class Trainer(train_utils.Trainer):
     # (decided before a loader is built: a loader emits ground truth on request)
     self.depth_sup_source = (depth_sup_source(opts)
                              if getattr(opts, 'depth_sup_wt', 0.0) > 0 else None)
+    if getattr(opts, 'kitti_augment', False) and (
+        opts.dataset != 'kitti' or opts.kitti_procedural):
+      raise ValueError(
+          '--kitti_augment true augments KITTI files (--dataset kitti without '
+          '--kitti_procedural): the synthetic and procedural generators are not '
+          'augmented')
     if opts.dataset == 'synthetic' and (opts.synth_scene in ('planes',
                                                              'planes_batched') or
                                         opts.debug_synth_texture):

@@ -184,6 +184,10 @@ class Tester(object):
           '--kitti_dl_velodyne and --kitti_dl_disparities_px both name a ground '
           'truth for --eval_depth: pick the Velodyne scans (the standard '
           'protocol) or the stereo disparities, not both')
+    if getattr(opts, 'kitti_augment', False):
+      raise ValueError(
+          '--kitti_augment true is a training switch: an evaluation scores the '
+          'images and cameras of the data set as they are')
     self.opts = opts
     self.device = torch.device('cpu' if opts.cpu or not torch.cuda.is_available()
                                else 'cuda')

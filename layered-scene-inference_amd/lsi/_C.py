@@ -27,6 +27,7 @@ LSI_SCENE_IMG, LSI_SCENE_DISP, LSI_SCENE_IMG_ROOM, LSI_SCENE_DISP_ROOM = 1, 2, 4
 LSI_SCENE_MAX_PLANES = 16
 LSI_FC_BN, LSI_FC_X_F32, LSI_FC_OUT_F32 = 1, 2, 4
 LSI_IMAGE_MAX_PIXELS = 16843009
+LSI_AUG_FLIP = 1
 LSI_VIS_SKIP, LSI_VIS_RGB, LSI_VIS_GRAY, LSI_VIS_LUT, LSI_VIS_ABSDIFF = 0, 1, 2, 3, 4
 LSI_VIS_MAX_ITEMS = 256
 LSI_LIDAR_INVERSE = 1
@@ -130,6 +131,15 @@ class LsiConvIO(ctypes.Structure):
 class LsiImageDesc(ctypes.Structure):
   _fields_ = ([('offset', ctypes.c_int64)] +
               [(n, ctypes.c_int32) for n in ('H', 'W', 'C', 'reserved')])
+
+
+class LsiAugmentDesc(ctypes.Structure):
+  _fields_ = ([('offset', ctypes.c_int64)] +
+              [(n, ctypes.c_int32) for n in ('H', 'W', 'C')] +
+              [('flags', ctypes.c_uint32)] +
+              [(n, ctypes.c_int32) for n in ('y0', 'x0', 'ch', 'cw', 'table',
+                                             'reserved')] +
+              [('gain', ctypes.c_float * 3), ('reserved2', ctypes.c_int32)])
 
 
 class LsiVisSheet(ctypes.Structure):
@@ -280,6 +290,8 @@ SIGNATURES = {
     'lsi_fc_bwd': (ctypes.c_int, [ctypes.POINTER(LsiFcDesc)] + [_VP] * 10 + [_SZ, _VP]),
     'lsi_area_resize_u8': (ctypes.c_int, [_I32, _VP, _VP, _VP, _SZ] + [_I32] * 3 +
                            [_VP, _VP]),
+    'lsi_augment_resize_u8': (ctypes.c_int, [_I32, _VP, _VP, _VP, _SZ, _I64, _I32] +
+                              [_I32] * 3 + [_VP, _VP]),
     'lsi_visual_sheet_size': (ctypes.c_int, [ctypes.POINTER(LsiVisSheet),
                                              ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     'lsi_visual_pack_u8': (ctypes.c_int, [ctypes.POINTER(LsiVisSheet), _VP, _VP, _VP, _VP,

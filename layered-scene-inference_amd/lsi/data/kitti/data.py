@@ -217,6 +217,21 @@ class DataLoader(object):
     self._order, self._cursor = None, 0
     self._rng = np.random.RandomState(0)
     self.src_image_names = []
+    # --kitti_augment (augment.py): off, nothing below exists and no extra
+    # random number is drawn
+    self.augment = None
+    if bool(getattr(opts, 'kitti_augment', False)):
+      from lsi.data.kitti import augment  # pylint: disable=g-import-not-at-top
+      if (self.output_disparities or self.output_disparities_px or
+          self.output_velodyne):
+        raise ValueError(
+            '--kitti_augment transforms the images and the cameras, not ground '
+            'truth: a loader that emits disparities or Velodyne scans '
+            '(--kitti_dl_disparities, --kitti_dl_disparities_px, '
+            '--kitti_dl_velodyne) cannot augment')
+      self.augment = augment.options_from(opts)
+      self.aug_seed = int(getattr(opts, 'aug_seed', 0))
+      self._aug_rng = np.random.RandomState(self.aug_seed)
 
   # -- file lists -------------------------------------------------------------
   @staticmethod
@@ -339,6 +354,35 @@ class DataLoader(object):
     self._cursor += 1
     return i
 
+  def augmented_cameras(self, aug, src_shape, trg_shape, calib_data):
+    """(k_s, k_t, rot, trans) of a pair augmented by `aug`."""
+    from lsi.data.kitti import augment  # pylint: disable=g-import-not-at-top
+    k_s, k_t, rot, trans = pair_cameras(calib_data, src_shape, trg_shape,
+                                        self.h, self.w)
+    return augment.augment_cameras(
+        k_s, k_t, rot, trans, src_shape, trg_shape,
+        augment.window(aug, src_shape[0], src_shape[1]),
+        augment.window(aug, trg_shape[0], trg_shape[1]), aug.flip, self.h, self.w)
+
+  def _forward_augmented(self, ids):
+    """forward() with --kitti_augment: one PairAugment per sample from
+    _aug_rng, in sample order; uint8 decode, augment.augment_area_resize."""
+    from lsi.data.kitti import augment, pipeline  # pylint: disable=g-import-not-at-top
+    instances = []
+    for i in ids:
+      aug = augment.sample(self._aug_rng, self.augment)
+      imgs, shapes = [], []
+      for path in (self.img_list_src[i], self.img_list_trg[i]):
+        arr = pipeline.decode_u8(path, 3)
+        table, gains = augment.image_params(aug, 3)
+        imgs.append(augment.augment_area_resize(
+            arr, augment.window(aug, arr.shape[0], arr.shape[1]), aug.flip,
+            table, gains, self.h, self.w))
+        shapes.append(arr.shape)
+      instances.append(tuple(imgs) + self.augmented_cameras(
+          aug, shapes[0], shapes[1], self.cam_calibration[self.seq_id_list[i]]))
+    return [np.stack([inst[k] for inst in instances]) for k in range(6)]
+
   def forward(self, bs):
     """bs instances: [img_s, img_t, k_s, k_t, rot, trans(, disp_s, disp_t)
     (, disp_px_s, disp_px_t)(, velo_pts, velo_n, velo_mats)], each stacked along
@@ -352,6 +396,8 @@ class DataLoader(object):
       self.preload_calib_files()
     ids = [self._next_index() for _ in range(bs)]
     self.src_image_names = [self.img_list_src[i] for i in ids]
+    if self.augment is not None:
+      return self._forward_augmented(ids)
     instances, disps_s, disps_t, px_s, px_t = [], [], [], [], []
     scans, velo_mats = [], []
     for i in ids:

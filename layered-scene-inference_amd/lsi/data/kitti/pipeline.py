@@ -21,6 +21,14 @@ thread, in the sequence the synchronous loader draws them.
                       cameras (data.pair_cameras, untouched).
   prefetch_depth  batches decoded ahead of the one being returned.
 
+With the wrapped loader's --kitti_augment on (augment.py), the parameters of
+every pair are drawn in _schedule, in batch order, from the wrapped loader's
+_aug_rng: the results do not depend on the thread count, the depth or timing.
+The host route runs augment.augment_area_resize in the workers; on the device
+route the workers write pixels as before and forward() fills the augmented
+descriptors and the tone tables into the same staging buffer: still one upload
+and one launch (lsi_augment_resize_u8) per output tensor.
+
 A staging buffer goes back to the pool only when an event recorded behind its
 upload has completed.  A decode error is raised from the forward() that owns the
 sample and names the file.  close() stops the workers; a collected loader or an
@@ -39,6 +47,14 @@ from lsi.data.kitti import data as kitti_data
 MAX_THREADS = 16
 DESC_DTYPE = np.dtype([('offset', '<i8'), ('H', '<i4'), ('W', '<i4'),
                        ('C', '<i4'), ('reserved', '<i4')])  # _C.LsiImageDesc
+AUG_DESC_DTYPE = np.dtype([('offset', '<i8'), ('H', '<i4'), ('W', '<i4'),
+                           ('C', '<i4'), ('flags', '<u4'), ('y0', '<i4'),
+                           ('x0', '<i4'), ('ch', '<i4'), ('cw', '<i4'),
+                           ('table', '<i4'), ('reserved', '<i4'),
+                           ('gain', '<f4', (3,)),
+                           ('reserved2', '<i4')])  # _C.LsiAugmentDesc
+AUG_FLIP = 1
+TABLE_BYTES = 3 * 256
 
 
 def pool_size(workers, world_size=1):
@@ -92,20 +108,67 @@ def area_resize_u8(packed, desc_host, desc_dev, n, h, w, nc, out=None):
   return out
 
 
+def augment_desc(images_hwc, offsets, windows=None, flips=None, tables=None,
+                 gains=None):
+  """AUG_DESC_DTYPE records of n images: shapes (H, W, C), byte offsets, and
+  per image a window (default: the whole image), a flip bit, a table index
+  (default -1: identity) and C gains (default 1)."""
+  n = len(images_hwc)
+  desc = np.zeros(n, AUG_DESC_DTYPE)
+  for m, (h, w, c) in enumerate(images_hwc):
+    y0, x0, ch, cw = windows[m] if windows is not None else (0, 0, h, w)
+    g = np.ones(3, np.float32)
+    if gains is not None:
+      g[:c] = np.asarray(gains[m], np.float32).reshape(-1)[:c]
+    desc[m] = (offsets[m], h, w, c, AUG_FLIP if flips is not None and flips[m] else 0,
+               y0, x0, ch, cw, tables[m] if tables is not None else -1, 0, g, 0)
+  return desc
+
+
+def augment_resize_u8(packed, desc_host, desc_dev, n, h, w, nc, tables_offset=0,
+                      n_tables=0, out=None):
+  """lsi_augment_resize_u8 on the current stream: area_resize_u8 with
+  AUG_DESC_DTYPE records; the n_tables tone tables (uint8[nc][256] each) lie
+  in `packed` from byte tables_offset.  Returns float32 [n, h, w, nc]."""
+  import torch  # pylint: disable=g-import-not-at-top
+  from lsi import _C  # pylint: disable=g-import-not-at-top
+  if not packed.is_cuda:
+    raise RuntimeError('the device AREA resize needs a ROCm GPU (got device %s); '
+                       'there is no CPU fallback' % packed.device)
+  if packed.dtype != torch.uint8 or not packed.is_contiguous():
+    raise RuntimeError('packed must be a contiguous uint8 tensor')
+  desc_host = np.ascontiguousarray(desc_host, AUG_DESC_DTYPE)
+  if desc_host.shape != (n,):
+    raise ValueError('%d descriptors for %d images' % (desc_host.size, n))
+  if out is None:
+    out = torch.empty((n, h, w, nc), dtype=torch.float32, device=packed.device)
+  _C.check(_C.lib().lsi_augment_resize_u8(
+      n, desc_host.ctypes.data, int(desc_dev), packed.data_ptr(), packed.numel(),
+      int(tables_offset), int(n_tables), h, w, nc, out.data_ptr(),
+      _C.stream_ptr(packed.device)), 'lsi_augment_resize_u8')
+  return out
+
+
 class _Staging(object):
   """One pinned buffer: [descriptors | pixel bytes], filled by the workers of
   one batch.  alloc() hands out 16-byte aligned ranges; a range that does not
   fit is refused and the image travels as its own array (the batch is then
-  re-packed into a larger buffer)."""
+  re-packed into a larger buffer).  An augmenting loader's buffer holds
+  AUG_DESC_DTYPE records and, behind them, n_tables tone tables:
+  [descriptors | tables | pixel bytes]."""
 
-  def __init__(self, n_desc, capacity):
+  def __init__(self, n_desc, capacity, n_tables=0, dtype=DESC_DTYPE):
     import torch  # pylint: disable=g-import-not-at-top
-    self.header = _round16(n_desc * DESC_DTYPE.itemsize)
+    self.tables_offset = _round16(n_desc * dtype.itemsize)
+    self.n_tables = n_tables
+    self.header = self.tables_offset + _round16(n_tables * TABLE_BYTES)
     self.capacity = _round16(capacity)
     self.tensor = torch.empty(self.header + self.capacity + 16, dtype=torch.uint8,
                               pin_memory=True)
     self.bytes = self.tensor.numpy()
-    self.desc = self.bytes[:n_desc * DESC_DTYPE.itemsize].view(DESC_DTYPE)
+    self.desc = self.bytes[:n_desc * dtype.itemsize].view(dtype)
+    self.tables = self.bytes[self.tables_offset:self.tables_offset +
+                             n_tables * TABLE_BYTES].reshape(n_tables, 3, 256)
     self.lock = threading.Lock()
     self.reset()
 
@@ -130,6 +193,23 @@ def _host_task(stop, path, h, w, nc):
   return kitti_data._load_image(path, h, w, nc)  # pylint: disable=protected-access
 
 
+def _host_augment_task(stop, path, h, w, aug):
+  from lsi.data.kitti import augment  # pylint: disable=g-import-not-at-top
+  if stop.is_set():
+    raise RuntimeError('the loader was closed')
+  arr = decode_u8(path, 3)
+  table, gains = augment.image_params(aug, 3)
+  return augment.augment_area_resize(
+      arr, augment.window(aug, arr.shape[0], arr.shape[1]), aug.flip, table, gains,
+      h, w), arr.shape
+
+
+def _set_image(desc, slot, off, h, w, nc):
+  """The image fields of record `slot` (either descriptor layout)."""
+  rec = desc[slot:slot + 1]
+  rec['offset'], rec['H'], rec['W'], rec['C'], rec['reserved'] = off, h, w, nc, 0
+
+
 def _device_task(stop, path, nc, staging, slot):
   """Decodes `path` into `staging` and fills descriptor `slot`.  Returns
   (original shape, None) or, when the buffer is full, (shape, pixel array)."""
@@ -144,7 +224,7 @@ def _device_task(stop, path, nc, staging, slot):
   if off is None:
     return (h, w, nc), np.ascontiguousarray(arr)
   staging.bytes[off:off + arr.size].reshape(arr.shape)[...] = arr
-  staging.desc[slot] = (off, h, w, nc, 0)
+  _set_image(staging.desc, slot, off, h, w, nc)
   return (h, w, nc), None
 
 
@@ -214,6 +294,16 @@ class PrefetchLoader(object):
     self.loader._rng = rng  # pylint: disable=protected-access
 
   @property
+  def _aug_rng(self):
+    return self.loader._aug_rng  # pylint: disable=protected-access
+
+  @_aug_rng.setter
+  def _aug_rng(self, rng):
+    if self._pending:
+      raise RuntimeError('the RNG must be set before the first forward()')
+    self.loader._aug_rng = rng  # pylint: disable=protected-access
+
+  @property
   def output_disparities(self):
     return self.loader.output_disparities
 
@@ -251,7 +341,13 @@ class PrefetchLoader(object):
           self._capacity = _round16(im.size[0] * im.size[1] * 3) * n_desc
       except Exception:  # pylint: disable=broad-except
         self._capacity = 1 << 20  # (the decode task reports the file)
-    return _Staging(n_desc, self._capacity)
+    return self._new_staging(n_desc, self._capacity)
+
+  def _new_staging(self, n_desc, capacity):
+    if getattr(self.loader, 'augment', None) is None:
+      return _Staging(n_desc, capacity)
+    # one tone table per pair: the two views share it
+    return _Staging(n_desc, capacity, n_tables=n_desc // 2, dtype=AUG_DESC_DTYPE)
 
   # -- scheduling -------------------------------------------------------------
   def _schedule(self, bs):
@@ -265,14 +361,22 @@ class PrefetchLoader(object):
     # descriptor / result order: per list, the bs samples
     paths = [(lst[i], nc) for lst, nc in lists for i in ids]
     staging = None
-    if self.resize == 'device':
+    augs = None
+    if getattr(ld, 'augment', None) is not None:
+      from lsi.data.kitti import augment  # pylint: disable=g-import-not-at-top
+      augs = [augment.sample(ld._aug_rng, ld.augment)  # pylint: disable=protected-access
+              for _ in ids]
+    if augs is not None and self.resize == 'host':
+      futs = [self._pool.submit(_host_augment_task, self._stop, p, ld.h, ld.w,
+                                augs[n % bs]) for n, (p, _) in enumerate(paths)]
+    elif self.resize == 'device':
       staging = self._acquire(len(paths), paths[0][0])
       futs = [self._pool.submit(_device_task, self._stop, p, nc, staging, slot)
               for slot, (p, nc) in enumerate(paths)]
     else:
       futs = [self._pool.submit(_host_task, self._stop, p, ld.h, ld.w, nc)
               for p, nc in paths]
-    self._pending.append((ids, paths, futs, staging))
+    self._pending.append((ids, paths, futs, staging, augs))
 
   def forward(self, bs):
     """The next batch of the wrapped loader's sequence (module doc)."""
@@ -284,7 +388,7 @@ class PrefetchLoader(object):
     self._bs = bs
     while len(self._pending) < self.depth + 1:
       self._schedule(bs)
-    ids, paths, futs, staging = self._pending.popleft()
+    ids, paths, futs, staging, augs = self._pending.popleft()
     ld = self.loader
     results, error = [], None
     for (path, _), fut in zip(paths, futs):  # every task of the batch ends here
@@ -301,18 +405,41 @@ class PrefetchLoader(object):
         self._free.append(staging)  # never uploaded: free at once
       raise error
     shapes = [r[0] if self.resize == 'device' else r[1] for r in results]
-    cams = [kitti_data.pair_cameras(ld.cam_calibration[ld.seq_id_list[i]],
-                                    shapes[j], shapes[bs + j], ld.h, ld.w)
-            for j, i in enumerate(ids)]
+    if augs is None:
+      cams = [kitti_data.pair_cameras(ld.cam_calibration[ld.seq_id_list[i]],
+                                      shapes[j], shapes[bs + j], ld.h, ld.w)
+              for j, i in enumerate(ids)]
+    else:
+      cams = [ld.augmented_cameras(augs[j], shapes[j], shapes[bs + j],
+                                   ld.cam_calibration[ld.seq_id_list[i]])
+              for j, i in enumerate(ids)]
     out_cams = [np.stack([c[k] for c in cams]) for k in range(4)]
     if self.resize == 'host':
       imgs = [np.stack([r[0] for r in results[g * bs:(g + 1) * bs]])
               for g in range(len(paths) // bs)]
       return imgs[:2] + out_cams + imgs[2:]
-    imgs = self._upload_and_resize(staging, results, bs)
+    imgs = self._upload_and_resize(staging, results, bs, augs)
     return imgs[:2] + out_cams + imgs[2:]
 
-  def _upload_and_resize(self, staging, results, bs):
+  def _fill_augment(self, staging, augs, bs):
+    """The windows, flip bits, table indices and gains of the 2 bs images, and
+    the tables themselves, into the staging buffer (pair j: slots j, bs + j)."""
+    from lsi.data.kitti import augment  # pylint: disable=g-import-not-at-top
+    desc = staging.desc
+    for j, aug in enumerate(augs):
+      table, gains = augment.image_params(aug, 3)
+      if table is not None:
+        staging.tables[j] = table
+      for slot in (j, bs + j):
+        rec = desc[slot:slot + 1]
+        rec['y0'], rec['x0'], rec['ch'], rec['cw'] = augment.window(
+            aug, int(desc['H'][slot]), int(desc['W'][slot]))
+        rec['flags'] = AUG_FLIP if aug.flip else 0
+        rec['table'] = j if table is not None else -1
+        rec['gain'] = gains
+        rec['reserved'] = rec['reserved2'] = 0
+
+  def _upload_and_resize(self, staging, results, bs, augs=None):
     import torch  # pylint: disable=g-import-not-at-top
     ld = self.loader
     spilled = [(slot, r[1]) for slot, r in enumerate(results) if r[1] is not None]
@@ -320,7 +447,7 @@ class PrefetchLoader(object):
       # the buffer was too small: a larger one takes the whole batch (and sets
       # the size of the buffers made from now on)
       self._capacity = _round16(staging.wanted - staging.header) * 5 // 4
-      big = _Staging(staging.desc.shape[0], self._capacity)
+      big = self._new_staging(staging.desc.shape[0], self._capacity)
       n_fit = staging.used
       big.bytes[big.header:n_fit] = staging.bytes[staging.header:n_fit]
       big.desc[...] = staging.desc
@@ -328,8 +455,10 @@ class PrefetchLoader(object):
       for slot, arr in spilled:
         off = big.alloc(arr.size)
         big.bytes[off:off + arr.size].reshape(arr.shape)[...] = arr
-        big.desc[slot] = (off, arr.shape[0], arr.shape[1], arr.shape[2], 0)
+        _set_image(big.desc, slot, off, arr.shape[0], arr.shape[1], arr.shape[2])
       staging = big
+    if augs is not None:
+      self._fill_augment(staging, augs, bs)
     used = staging.used + 16  # the pad behind the last image
     with torch.cuda.device(self.device):
       packed = torch.empty(used, dtype=torch.uint8, device=self.device)
@@ -338,6 +467,11 @@ class PrefetchLoader(object):
       event.record()
       self._uploading.append((event, staging))
       out = []
+      if augs is not None:  # (an augmenting loader emits the two images only)
+        both = augment_resize_u8(packed, staging.desc, packed.data_ptr(), 2 * bs,
+                                 ld.h, ld.w, 3, staging.tables_offset,
+                                 staging.n_tables)
+        return [both[:bs], both[bs:]]
       for g, nc in enumerate((3, 1) if ld.output_disparities else (3,)):
         n = 2 * bs
         first = g * n

@@ -12,6 +12,15 @@ at 256 x 768 on this host, in this run:
     measurement), and the 2-layer step fed from the tree by both loaders, eager
     and as a captured HIP graph.
   python tools/data_bench.py [--out FILE] [--batches N] [--skip_steps] [--kernel_only]
+
+--augment [--parent_lib SO] measures the augmenting launch instead
+(lsi_augment_resize_u8): the plain launch, the augmenting launch
+at identity parameters and at a typical draw (zoom 1.1, flip, tone table,
+gains), alternated in one process over --rounds rounds of HIP-event medians;
+with --parent_lib also the lsi_area_resize_u8 of another build (a shared
+library made from an earlier csrc/lsi_image.hip), whose range over the rounds is
+the run-to-run spread the others are read against.  Then the device-route loader
+at 16 threads with --kitti_augment off and on.
 """
 import argparse
 import json
@@ -70,10 +79,11 @@ def write_tree(root):
   return n_bytes / (2.0 * PAIRS_PER_SEQ * len(SIZES))
 
 
-def loader_opts(root):
+def loader_opts(root, **more):
   return types.SimpleNamespace(
       batch_size=BS, kitti_data_root=root, kitti_dataset_variant='raw_city',
-      data_split='train', img_height=H, img_width=W, kitti_dl_disparities=False)
+      data_split='train', img_height=H, img_width=W, kitti_dl_disparities=False,
+      **more)
 
 
 def time_loader(make, batches, warm=2):
@@ -126,6 +136,114 @@ def time_kernel(root, reps=20):
   return float(np.median(times)), float(min(times)), moved, used
 
 
+def _event_median(run, reps):
+  times = []
+  for _ in range(reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    run()
+    e1.record()
+    e1.synchronize()
+    times.append(e0.elapsed_time(e1) * 1e3)
+  return float(np.median(times))
+
+
+def time_augment_launches(root, parent_lib='', rounds=7, reps=40):
+  """us per launch on 8 images of the tree, HIP events: {variant: [median of
+  `reps` launches, one per round]}; the variants alternate inside a round."""
+  import ctypes
+  from lsi import _C
+  from lsi.data.kitti import augment
+  ld = kitti_data.DataLoader(loader_opts(root))
+  paths = [p for i in range(0, len(ld.img_list_src), PAIRS_PER_SEQ)
+           for p in (ld.img_list_src[i], ld.img_list_trg[i])][:2 * BS]
+  n = len(paths)
+  cap = sum(pipeline._round16(h * w * 3) for h, w in SIZES) * 2
+  stop = __import__('threading').Event()
+  # one buffer per descriptor layout, the same pixels in both
+  plain = pipeline._Staging(n, cap)
+  aug = {k: pipeline._Staging(n, cap, n_tables=n // 2, dtype=pipeline.AUG_DESC_DTYPE)
+         for k in ('identity', 'typical')}
+  for st in [plain] + list(aug.values()):
+    for slot, p in enumerate(paths):
+      pipeline._device_task(stop, p, 3, st, slot)
+  draw = augment.IDENTITY._replace(flip=True, zoom_y=1.1, zoom_x=1.1, off_y=0.5,
+                                   off_x=0.5, gamma=0.9, brightness=1.2,
+                                   color=(0.9, 1.0, 1.1))
+  for key, st in aug.items():
+    d = st.desc
+    d['flags'], d['table'], d['gain'] = 0, -1, 1.0
+    d['y0'], d['x0'], d['ch'], d['cw'] = 0, 0, d['H'], d['W']
+    d['reserved'], d['reserved2'] = 0, 0
+    if key == 'typical':
+      table, gains = augment.image_params(draw, 3)
+      st.tables[...] = table
+      for m in range(n):
+        rec = d[m:m + 1]
+        rec['y0'], rec['x0'], rec['ch'], rec['cw'] = augment.window(
+            draw, int(d['H'][m]), int(d['W'][m]))
+        rec['flags'], rec['table'], rec['gain'] = pipeline.AUG_FLIP, m // 2, gains
+
+  def upload(st):
+    used = st.used + 16
+    packed = torch.empty(used, dtype=torch.uint8, device='cuda')
+    packed.copy_(st.tensor[:used])
+    return packed
+  out = torch.empty((n, H, W, 3), device='cuda')
+  runs = {}
+  pk = upload(plain)
+  if parent_lib:
+    parent = ctypes.CDLL(os.path.abspath(parent_lib))
+    parent.lsi_area_resize_u8.restype = ctypes.c_int
+    parent.lsi_area_resize_u8.argtypes = (
+        [ctypes.c_int32] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t] +
+        [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 2)
+  # (every variant is one bare ctypes call on prepared arguments: the same
+  # host work inside the timed window)
+  stream = _C.stream_ptr(pk.device)
+  hosts = []
+
+  def call(fn, st, packed, *extra):
+    host = np.ascontiguousarray(st.desc)
+    hosts.append(host)
+    args = (n, host.ctypes.data, packed.data_ptr(), packed.data_ptr(),
+            packed.numel()) + extra + (H, W, 3, out.data_ptr(), stream)
+
+    def run():
+      rc = fn(*args)
+      assert rc == 0, rc
+    return run
+  if parent_lib:
+    runs['parent_plain'] = call(parent.lsi_area_resize_u8, plain, pk)
+  runs['plain'] = call(_C.lib().lsi_area_resize_u8, plain, pk)
+  packed = {k: upload(st) for k, st in aug.items()}
+  for key, st in aug.items():
+    runs['augment_' + key] = call(_C.lib().lsi_augment_resize_u8, st, packed[key],
+                                  st.tables_offset, st.n_tables)
+  # the same seeded inputs, the same bits: parent = plain = augment at identity
+  ref = None
+  for key in ('parent_plain', 'plain', 'augment_identity'):
+    if key in runs:
+      runs[key]()
+      got = out.clone()
+      assert ref is None or torch.equal(got, ref), key
+      ref = got
+  for run in runs.values():
+    for _ in range(5):
+      run()
+  torch.cuda.synchronize()
+  times = {k: [] for k in runs}
+  for _ in range(rounds):
+    for key, run in runs.items():
+      times[key].append(_event_median(run, reps))
+  px = {'plain': int(plain.desc['H'].astype(np.int64) @ plain.desc['W'])}
+  for key, st in aug.items():
+    px['augment_' + key] = int(st.desc['ch'].astype(np.int64) @ st.desc['cw'])
+  px['parent_plain'] = px['plain']
+  moved = {k: px[k] * 3 + out.numel() * 4 for k in runs}
+  return times, moved
+
+
 def time_host_parts(root, reps=8):
   ld = kitti_data.DataLoader(loader_opts(root))
   paths = ld.img_list_src[:reps]
@@ -173,6 +291,11 @@ def main():
   ap.add_argument('--skip_steps', action='store_true')
   ap.add_argument('--kernel_only', action='store_true',
                   help='only the resize launch (for a rocprofv3 --kernel-trace run)')
+  ap.add_argument('--augment', action='store_true',
+                  help='the augmenting launch and loader instead (module doc)')
+  ap.add_argument('--parent_lib', default='',
+                  help='--augment: a library with another build\'s lsi_area_resize_u8')
+  ap.add_argument('--rounds', type=int, default=7)
   args = ap.parse_args()
   assert torch.cuda.is_available(), 'data_bench needs a ROCm device'
   lines, rec = [], {}
@@ -189,6 +312,37 @@ def main():
       med, best, moved, _ = time_kernel(root, reps=50)
       say('resize launch alone: median %.1f us, min %.1f us by HIP events, %.1f MB'
           % (med, best, moved / 1e6))
+      return
+    if args.augment:
+      times, moved = time_augment_launches(root, args.parent_lib, max(5, args.rounds))
+      say('launch on 8 RGB images -> 8 x %d x %d x 3 fp32, HIP events, us: median '
+          'of the %d round medians [min .. max over the rounds]'
+          % (H, W, max(5, args.rounds)))
+      for key, t in times.items():
+        say('  %-18s %6.1f  [%5.1f .. %5.1f]  %.1f MB' % (
+            key, float(np.median(t)), min(t), max(t), moved[key] / 1e6))
+      base = times.get('parent_plain', times['plain'])
+      spread = max(base) - min(base)
+      say('  spread of %s over the rounds: %.1f us; bar = its median + spread = %.1f us'
+          % ('parent_plain' if 'parent_plain' in times else 'plain', spread,
+             float(np.median(base)) + spread))
+      rec['augment_launch_us'] = times
+      import ldi_enc_dec as script
+      rec['augment_loader_ms_per_batch'] = {}
+      for _ in range(2):
+        for on in (False, True):
+          ms = time_loader(lambda: script.KittiBatches(pipeline.PrefetchLoader(
+              kitti_data.DataLoader(loader_opts(root, kitti_augment=on)), workers=16,
+              resize='device', device=torch.device('cuda', 0))), args.batches)
+          say('16 threads, resize on the device, --kitti_augment %-5s %8.1f ms/batch'
+              % (str(on).lower(), ms))
+          rec['augment_loader_ms_per_batch'].setdefault(
+              'on' if on else 'off', []).append(ms)
+      say(json.dumps(rec))
+      if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+          f.write('\n'.join(lines) + '\n')
       return
     dec, rsz, whole = time_host_parts(root)
     say('one image on one thread: decode %.1f ms, host AREA resize %.1f ms, '

@@ -1034,8 +1034,12 @@ __global__ __launch_bounds__(MAXT) void splat_stream_kernel(SplatArgs a,
             cl0 = (int)(x0v[0] - wlo_f);
             int dl[4];
             dl[0] = 0;
+            // (a NaN x0v[0] converts to offset 0 and to dl[i] = 0: the lane's
+            // other pixels would land in window cell 0.  The comparison with
+            // the lane below refuses it, except where lane 0 is the segment's
+            // only lane inside the image -- W % 256 = 4 -- hence the self-test)
             unsigned long long regA =
-                __ballot((unsigned)cl0 <= wspanA) &
+                __ballot((unsigned)cl0 <= wspanA && x0v[0] == x0v[0]) &
                 (__ballot(x0v[0] > lane_below(x0v[0])) | edge_mask);
 #pragma unroll
             for (int i = 1; i < 4; ++i) {

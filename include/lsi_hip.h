@@ -961,6 +961,11 @@ int lsi_render_planes_bwd(const LsiSceneDesc* desc, const float* tex_rgba,
  *   (summed over the groups).
  */
 size_t lsi_bn_workspace_floats(int64_t npix, int32_t C, int32_t bf16, int32_t groups);
+/* Host only: the workgroups per group (grid.x; grid.y = groups) that every pass
+ * of lsi_bn_relu_fwd / _norm / _bwd launches for these arguments, 0 for a shape
+ * they refuse.  A workgroup of 256 threads covers rows = 256 / (C / vector)
+ * pixels per step and advances by workgroups * rows. */
+int32_t lsi_bn_launch_workgroups(int64_t npix, int32_t C, int32_t bf16, int32_t groups);
 int lsi_bn_relu_fwd(const void* x, void* y, const float* beta, float* workspace,
                     float* mean_rstd, int64_t npix, int32_t C, int32_t bf16,
                     int32_t relu, float eps, int32_t groups, lsi_stream_t stream);

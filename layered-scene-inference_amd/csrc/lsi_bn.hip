@@ -541,6 +541,15 @@ extern "C" size_t lsi_bn_workspace_floats(int64_t npix, int32_t C, int32_t bf16,
   return (size_t)WS_STRIDE * groups;
 }
 
+// the workgroups per group every pass of a call with these arguments launches
+// (grid.x; grid.y = groups) -- for tests that have to place a shape on a loop
+// boundary of the kernels; 0 for what the entry points refuse
+extern "C" int32_t lsi_bn_launch_workgroups(int64_t npix, int32_t C, int32_t bf16,
+                                            int32_t groups) {
+  if (!bn_shape_ok(npix, C, bf16) || groups < 1 || groups > 65535) return 0;
+  return bn_grid(npix, C, bf16, groups);
+}
+
 extern "C" int lsi_bn_relu_fwd(const void* x, void* y, const float* beta,
                                float* workspace, float* mean_rstd, int64_t npix,
                                int32_t C, int32_t bf16, int32_t relu, float eps,

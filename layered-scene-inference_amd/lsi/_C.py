@@ -279,6 +279,7 @@ SIGNATURES = {
     'lsi_conv2d_wgrad_f32': (ctypes.c_int, [_CP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _SZ,
                                             _VP]),
     'lsi_bn_workspace_floats': (_SZ, [_I64, _I32, _I32, _I32]),
+    'lsi_bn_launch_workgroups': (_I32, [_I64, _I32, _I32, _I32]),
     'lsi_bn_relu_fwd': (ctypes.c_int, [_VP] * 5 + [_I64, _I32, _I32, _I32, _F32, _I32, _VP]),
     'lsi_bn_relu_bwd': (ctypes.c_int, [_VP] * 7 + [_I64, _I32, _I32, _I32, _I32, _VP]),
     'lsi_bn_relu_norm': (ctypes.c_int, [_VP] * 5 + [_I64, _I32, _I32, _I32, _F32, _I32, _VP]),

@@ -175,6 +175,29 @@ def test_sampling_entry_points_refuse_before_any_launch(built_lib):
     assert sa(1, 8, 4, [None if k == miss else one for k in range(3)]) == -2, miss
 
 
+def test_bn_entry_points_answer_on_the_host(built_lib):
+  """lsi_bn_workspace_floats and lsi_bn_launch_workgroups: host only.  A shape
+  the batch-norm entry points refuse gets 0 from both; one they take, the
+  workspace of 16 + 4096 + 3 * 2048 floats per group and 1 ... 2048 workgroups
+  per group that cover the group's pixels in whole steps."""
+  from lsi import _C
+  lib = _C.lib()
+  for npix, c, bf16, groups in ((15, 12, 0, 1), (15, 4, 1, 1), (15, 2048, 0, 1),
+                                (15, 4096, 1, 1), (0, 32, 0, 1), (15, 32, 0, 0),
+                                (15, 32, 1, 65536)):
+    assert lib.lsi_bn_launch_workgroups(npix, c, bf16, groups) == 0, (npix, c, bf16, groups)
+  assert lib.lsi_bn_workspace_floats(15, 12, 0, 1) == 0
+  for npix, c, bf16, groups in ((1, 4, 0, 1), (4, 8, 1, 3), (10007, 64, 0, 2),
+                                (2048, 1024, 0, 1), (2052, 1024, 0, 1), (38916, 2048, 1, 1),
+                                (1 << 22, 32, 1, 2)):
+    wg = lib.lsi_bn_launch_workgroups(npix, c, bf16, groups)
+    rows = 256 // (c // (8 if bf16 else 4))
+    assert 1 <= wg <= 2048 and (wg - 1) * rows < npix, (npix, c, bf16, groups, wg)
+    assert lib.lsi_bn_workspace_floats(npix, c, bf16, groups) == groups * (16 + 4096 + 3 * 2048)
+  # (which shapes land where in the launch rule: test_bn_lattice_gpu.py)
+  assert lib.lsi_bn_launch_workgroups(1 << 22, 32, 0, 1) == 2048     # the cap
+
+
 def test_no_cpu_fallback(built_lib):
   from lsi.geometry import ldi, sampling
   tex = torch.rand(1, 1, 8, 8, 3)

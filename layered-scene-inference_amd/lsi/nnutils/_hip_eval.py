@@ -50,6 +50,15 @@ def _check_acc(acc, dev):
                        (SLOT_COUNT, dev))
 
 
+def _require_fp32(fn, **tensors):
+  """_C.require_device lets int32 through (the index tensors of other entry
+  points); every array the metric kernels read is fp32, and an int32 one would
+  be read as float bits."""
+  for name, t in tensors.items():
+    if t is not None and t.dtype != torch.float32:
+      raise RuntimeError('%s: %s must be fp32 (got %s)' % (fn, name, t.dtype))
+
+
 def _map(t, shape, what):
   """A contiguous B x H x W (x 1) map; no copy when it already is one."""
   if t is None:
@@ -67,6 +76,8 @@ def view_metrics(acc, ws, ws_bytes, recons, recons_disp, target, x_min, y_min,
   disocc fp32 or bool.  With valid_above, `valid` is a map and a pixel is valid
   where it exceeds that value."""
   dev = _C.require_device(recons, recons_disp, target, valid, gt_disp)
+  _require_fp32('view_metrics', recons=recons, recons_disp=recons_disp, target=target,
+                valid_mask=valid, gt_disp_trg=gt_disp)
   _check_acc(acc, dev)
   nl, b, ht, wt, c = recons.shape
   if c != 3 or tuple(target.shape[:1] + target.shape[3:]) != (b, 3):
@@ -224,6 +235,9 @@ def layer_metrics(acc, ws, ws_bytes, ldi_src, ldi_trg, imgs_src, imgs_trg, gt,
     if n_bg and tuple(views[-1][5].shape) != (b, h, w, 3):
       raise ValueError('layer_metrics: %s_gt_tex_bg must be %s' % (side, (b, h, w, 3)))
   dev = _C.require_device(*[t for v in views for t in v])
+  for v, side in zip(views, ('src', 'trg')):
+    _require_fp32('layer_metrics', **{'%s %s' % (side, k): t for k, t in zip(
+        ('tex', 'disps', 'image', 'gt_disp', 'gt_disp_bg', 'gt_tex_bg'), v)})
   _check_acc(acc, dev)
   args = []
   for v in views:
@@ -238,6 +252,8 @@ def disocclusion_mask(disps_src, disps_trg, src2trg_mat, thresh):
   """lsi_disocclusion_mask: disps B x H x W x 1, src2trg_mat B x 4 x 4; the source
   points are the pixel centres.  Returns the B x Hs x Ws x 1 fp32 mask."""
   dev = _C.require_device(disps_src, disps_trg, src2trg_mat)
+  _require_fp32('disocclusion_mask', disps_src=disps_src, disps_trg=disps_trg,
+                src2trg_mat=src2trg_mat)
   b, hs, ws_, _ = disps_src.shape
   _, ht, wt, _ = disps_trg.shape
   if tuple(src2trg_mat.shape) != (b, 4, 4) or disps_trg.shape[0] != b:

@@ -1463,6 +1463,37 @@ int lsi_augment_resize_u8(int32_t n, const LsiAugmentDesc* desc_host,
                           float* out, lsi_stream_t stream);
 
 /*
+ * Nearest-neighbour samples of a ragged batch of 16-bit disparity maps (value
+ * = disparity * 256, 0 = no match) through the crop window and flip of
+ * lsi_augment_resize_u8's descriptors, one launch (DESIGN.md 4.12c;
+ * lsi/data/kitti/augment.py:sample_disparity_px): with (y0, x0, ch, cw) the
+ * window of map m,
+ *   y   = y0 + min(((2 i + 1) ch) / (2 Ho), ch - 1)      (integer division:
+ *   x   = x0 + min(((2 k + 1) cw) / (2 Wo), cw - 1)       the pixel under the
+ *                                                         output pixel's centre)
+ *   val = (float)(((double)map[y, x] / 256) * ((double)Wo / (double)cw))
+ *   out[m, i, flip ? Wo - 1 - k : k, 0] = val
+ * in pixels of the Ho x Wo image: one fp64 division, one fp64 product (the
+ * division by 256 is exact) and one rounding to fp32, so the values are bit
+ * for bit the host's.  Zeros stay zeros; a flip does not change the sign.  The
+ * full window without flip gives the bits of data.load_disparity_px.
+ *   packed    as for lsi_augment_resize_u8; map m is H x W host-order uint16
+ *             at packed + offset, rows 2 W bytes apart
+ *   desc_*    LsiAugmentDesc with C == 1 and table == -1; gain is not read
+ *   out       device, float32 [n, Ho, Wo, 1], written fully
+ * LSI_ENULL for a NULL pointer; LSI_EINVAL for n outside [1, 65535], C != 1,
+ * H or W <= 0, a window that is empty or leaves the map, flags other than
+ * LSI_AUG_FLIP, table != -1, an offset that is negative or not a multiple of
+ * 16, offset + 2 H W > packed_bytes, (2 Ho + 1)(ch + 1) or (2 Wo + 1)(cw + 1)
+ * >= 2^31, or a misaligned pointer -- all before any launch.  No workspace, no
+ * allocation, no synchronisation, no state.
+ */
+int lsi_augment_sample_u16(int32_t n, const LsiAugmentDesc* desc_host,
+                           const LsiAugmentDesc* desc_dev, const uint8_t* packed,
+                           size_t packed_bytes, int32_t Ho, int32_t Wo,
+                           float* out, lsi_stream_t stream);
+
+/*
  * Contact sheet of visuals, one launch: n_items fp32 device
  * tensors, each with its own size, strides and value range, are quantised to
  * bytes and laid out on a grid of rows x cols cells of cell_h x cell_w pixels

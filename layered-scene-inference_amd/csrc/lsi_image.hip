@@ -46,6 +46,10 @@
 //           kb .. kb + 3 goes, reversed, to columns Wo - 4 - kb .. (a multiple
 //           of 4 when Wo and kb are).
 // The plain instances compile to the code they were before the template.
+//
+// lsi_augment_sample_u16 (a kernel of its own, below the template) samples
+// 16-bit disparity maps by nearest neighbour through the same descriptors and
+// packed buffer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -280,9 +284,102 @@ int launch(const Args& a, int32_t n, int32_t Ho, int32_t Wo, int32_t Co,
   return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
 }
 
+// lsi_augment_sample_u16: nearest-neighbour samples of 16-bit
+// disparity maps through the same descriptors.  Output pixel (i, k) of map m
+// reads window row min(((2 i + 1) ch) / (2 Ho), ch - 1), column alike -- the
+// pixel under the output pixel's centre -- and stores
+//   (float)(((double)raw * (1 / 256)) * ((double)Wo / (double)cw))
+// (the first product is exact; one fp64 division, one fp64 product, one
+// rounding to fp32: augment.sample_disparity_px's bits) at column k, or
+// Wo - 1 - k under LSI_AUG_FLIP.
+// Bound: 4 output bytes written per 2-byte gather, nothing shared between
+// threads, so there is no LDS: a thread gathers four adjacent columns of one
+// row and stores them as one float4 (reversed, at Wo - 4 - kb, when mirrored);
+// the lanes of a wave write 1 KiB of one output row.
+constexpr int SAMPLE_COLS = 64;   // threads along a row, four columns each
+constexpr int SAMPLE_ROWS = 4;    // output rows per workgroup
+
+struct SampleArgs {
+  int Ho, Wo;
+  int vec_store;  // Wo is a multiple of 4 and out is 16-byte aligned
+  const LsiAugmentDesc* desc;
+  const uint8_t* packed;
+  float* out;
+};
+
+__global__ __launch_bounds__(SAMPLE_COLS * SAMPLE_ROWS) void augment_sample_u16_kernel(
+    SampleArgs a) {
+  const int i = blockIdx.y * SAMPLE_ROWS + (int)threadIdx.x / SAMPLE_COLS;
+  const int kb = 4 * (blockIdx.x * SAMPLE_COLS + (int)threadIdx.x % SAMPLE_COLS);
+  const int Ho = a.Ho, Wo = a.Wo;
+  if (i >= Ho || kb >= Wo) return;
+  const LsiAugmentDesc d = a.desc[blockIdx.z];
+  const bool flip = (d.flags & LSI_AUG_FLIP) != 0;
+  // (2 i + 1) ch <= (2 Ho + 1)(ch + 1) < 2^31 (validated), columns alike
+  const int y = d.y0 + min(((2 * i + 1) * d.ch) / (2 * Ho), d.ch - 1);
+  const uint16_t* row = reinterpret_cast<const uint16_t*>(a.packed + d.offset) +
+                        (int64_t)y * d.W + d.x0;
+  const double scale = (double)Wo / (double)d.cw;
+  float v[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    // (past the row's end the last column is read again and not stored)
+    const int k = min(kb + p, Wo - 1);
+    const int x = min(((2 * k + 1) * d.cw) / (2 * Wo), d.cw - 1);
+    v[p] = (float)(((double)row[x] * (1.0 / 256.0)) * scale);
+  }
+  float* o = a.out + ((int64_t)blockIdx.z * Ho + i) * Wo;
+  if (a.vec_store) {  // kb + 4 <= Wo: both are multiples of 4
+    if (flip)
+      *reinterpret_cast<float4*>(o + (Wo - 4 - kb)) = make_float4(v[3], v[2], v[1], v[0]);
+    else
+      *reinterpret_cast<float4*>(o + kb) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      if (kb + p < Wo) o[flip ? Wo - 1 - (kb + p) : kb + p] = v[p];
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int lsi_augment_sample_u16(int32_t n, const LsiAugmentDesc* desc_host,
+                           const LsiAugmentDesc* desc_dev, const uint8_t* packed,
+                           size_t packed_bytes, int32_t Ho, int32_t Wo, float* out,
+                           lsi_stream_t stream) {
+  if (!desc_host || !desc_dev || !packed || !out) return LSI_ENULL;
+  if (bad_call(n, Ho, Wo, 1, packed, packed_bytes, out, desc_dev)) return LSI_EINVAL;
+  for (int32_t m = 0; m < n; ++m) {
+    const LsiAugmentDesc& d = desc_host[m];
+    if (d.H <= 0 || d.W <= 0 || d.C != 1) return LSI_EINVAL;
+    if (d.y0 < 0 || d.x0 < 0 || d.ch < 1 || d.cw < 1 ||
+        (int64_t)d.y0 + d.ch > d.H || (int64_t)d.x0 + d.cw > d.W)
+      return LSI_EINVAL;
+    // the kernel's int32 products (2 i + 1) ch, (2 k + 1) cw
+    if ((int64_t)(2 * (int64_t)Ho + 1) * ((int64_t)d.ch + 1) > INT32_MAX ||
+        (int64_t)(2 * (int64_t)Wo + 1) * ((int64_t)d.cw + 1) > INT32_MAX)
+      return LSI_EINVAL;
+    if (d.flags & ~(uint32_t)LSI_AUG_FLIP) return LSI_EINVAL;
+    if (d.table != -1) return LSI_EINVAL;
+    const uint64_t bytes = 2 * (uint64_t)d.H * (uint64_t)d.W;   // < 2^63
+    if (d.offset < 0 || (d.offset & 15) || (uint64_t)d.offset > packed_bytes ||
+        bytes > packed_bytes - (uint64_t)d.offset)
+      return LSI_EINVAL;
+  }
+  SampleArgs a;
+  a.Ho = Ho; a.Wo = Wo;
+  a.vec_store = (Wo % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
+  a.desc = desc_dev; a.packed = packed; a.out = out;
+  const int quads = (Wo + 3) / 4;
+  const dim3 grid((quads + SAMPLE_COLS - 1) / SAMPLE_COLS,
+                  (Ho + SAMPLE_ROWS - 1) / SAMPLE_ROWS, n);
+  if (grid.y > 65535u) return LSI_EINVAL;
+  hipLaunchKernelGGL(augment_sample_u16_kernel, grid, dim3(SAMPLE_COLS * SAMPLE_ROWS), 0,
+                     (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+}
 
 int lsi_area_resize_u8(int32_t n, const LsiImageDesc* desc_host,
                        const LsiImageDesc* desc_dev, const uint8_t* packed,

@@ -43,7 +43,8 @@ DEPTH_SUP_SOURCES = (
     "--dataset synthetic with --synth_scene planes or planes_batched (the scenes' "
     'foreground disparities), KITTI files with --kitti_dl_disparities_px true '
     '(stereo disparities) or KITTI files with --kitti_dl_velodyne true (Velodyne '
-    'scans, rasterised on the device)')
+    'scans, rasterised on the device); KITTI files emit either on the val / '
+    'test splits, and on the train split with --kitti_gt_everywhere true')
 
 
 def depth_sup_source(opts):
@@ -79,12 +80,19 @@ def build_parser():
     help='under the conditions of --kitti_dl_disparities: append the SPS-stereo '
     'disparities of both views in pixels of the resized image, both bytes of the '
     '16-bit PNG, nearest-neighbour sampled (the ground truth of --eval_depth; '
-    'the synchronous loader only)')
+    'the synchronous loader only, unless --kitti_gt_everywhere)')
   a('--kitti_dl_velodyne', type=_bool, default=False,
     help='under the conditions of --kitti_dl_disparities: append the Velodyne '
     'scan of every pair (velodyne_points/data/N.bin, NaN-padded), its point '
     'count and the two 3 x 4 projections into the resized views (the standard '
-    'ground truth of --eval_depth; the synchronous loader only)')
+    'ground truth of --eval_depth; the synchronous loader only, unless '
+    '--kitti_gt_everywhere)')
+  a('--kitti_gt_everywhere', type=_bool, default=False,
+    help='--kitti_dl_disparities_px and --kitti_dl_velodyne take effect on the '
+    'train split too, are served by the prefetching loader (--data_workers, '
+    '--kitti_resize host or device) and are cropped, flipped and scaled with '
+    'their pair under --kitti_augment (DESIGN.md 4.12c).  false: both stay with '
+    'the synchronous loader on val / test, unaugmented')
   a('--kitti_procedural', type=_bool, default=False,
     help='no KITTI files: procedural stereo pairs seen through the KITTI camera '
     'model and constants (throughput runs, tests).  Without this switch a '
@@ -321,6 +329,20 @@ class SyntheticPairs(object):
     return (src, trg, k, k.clone(), rot, t)
 
 
+def _halves_of(a, b):
+  """The tensor whose two halves along the batch axis `a` and `b` are -- as the
+  prefetching loader's device route returns its disparity maps -- or None."""
+  base = getattr(a, '_base', None)
+  if (base is None or base is not getattr(b, '_base', None) or
+      base.dtype != torch.float32 or a.dtype != base.dtype or b.dtype != base.dtype or
+      not (base.is_contiguous() and a.is_contiguous() and b.is_contiguous()) or
+      base.dim() != a.dim() or a.shape != b.shape or a.shape[1:] != base.shape[1:] or
+      base.shape[0] != 2 * a.shape[0] or a.data_ptr() != base.data_ptr() or
+      b.data_ptr() != base.data_ptr() + a.numel() * a.element_size()):
+    return None
+  return base
+
+
 class KittiBatches(object):
   """lsi.data.kitti.DataLoader batches (NumPy) as float32 torch tensors:
   (img_s, img_t, k_s, k_t, rot, trans[, disp_s, disp_t])."""
@@ -421,8 +443,9 @@ class Trainer(train_utils.Trainer):
       return (src, batch[-3], batch[-2], batch[-1])  # points, counts, matrices
     raise ValueError(
         '--depth_sup_wt > 0: the loader emitted %d outputs, none of them ground '
-        'truth (the KITTI loader emits it on the val / test splits only).  The '
-        'term takes it from: %s' % (len(batch), DEPTH_SUP_SOURCES))
+        'truth (the KITTI loader emits it on the val / test splits only; on '
+        'train with --kitti_gt_everywhere true).  The term takes it from: %s'
+        % (len(batch), DEPTH_SUP_SOURCES))
 
   def feed(self):
     """One batch: (img_src, img_trg, k_s, k_t, rot, trans); with
@@ -489,8 +512,11 @@ class Trainer(train_utils.Trainer):
       # pixel disparities d = f_x |t_x| / depth, each view with its own intrinsics
       t_x = trans_mat[:, 0, 0].abs()
       scale = torch.cat([1.0 / (k_s[:, 0, 0] * t_x), 1.0 / (k_t[:, 0, 0] * t_x)])
-      return [torch.cat([up(outputs[1].float()), up(outputs[2].float())], dim=0),
-              up(scale.float())]
+      # (the device route's sampling launch wrote [gt_src; gt_trg] as one tensor)
+      both = _halves_of(outputs[1], outputs[2])
+      if both is None:
+        both = torch.cat([up(outputs[1].float()), up(outputs[2].float())], dim=0)
+      return [up(both), up(scale.float())]
     # the scans rasterised into both views as inverse depths, 0 = no return
     from lsi.geometry import lidar  # pylint: disable=g-import-not-at-top
     pts, counts, mats = outputs[1:]

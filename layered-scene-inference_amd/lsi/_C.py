@@ -293,6 +293,8 @@ SIGNATURES = {
                            [_VP, _VP]),
     'lsi_augment_resize_u8': (ctypes.c_int, [_I32, _VP, _VP, _VP, _SZ, _I64, _I32] +
                               [_I32] * 3 + [_VP, _VP]),
+    'lsi_augment_sample_u16': (ctypes.c_int, [_I32, _VP, _VP, _VP, _SZ, _I32, _I32,
+                                              _VP, _VP]),
     'lsi_visual_sheet_size': (ctypes.c_int, [ctypes.POINTER(LsiVisSheet),
                                              ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     'lsi_visual_pack_u8': (ctypes.c_int, [ctypes.POINTER(LsiVisSheet), _VP, _VP, _VP, _VP,

@@ -5,6 +5,9 @@ One `PairAugment` is drawn per stereo pair and shared by its two views.  The
 images go through `augment_area_resize`, the restatement of the HIP kernel
 lsi_augment_resize_u8 (csrc/lsi_image.hip) and the host route of the loaders:
 the two return the same bits.  The cameras go through `augment_cameras`.
+Ground truth (--kitti_gt_everywhere): 16-bit disparity maps
+go through `sample_disparity_px`, the restatement of lsi_augment_sample_u16,
+and the Velodyne projections through `augment_projection`.
 
   crop    window(aug, H, W) of each view, from its own shape; the output is the
           exact AREA resize of the window
@@ -147,6 +150,52 @@ def augment_area_resize(img_u8, window, flip, table, gains, ho, wo):  # pylint: 
   if flip:
     out = out[:, ::-1]
   return np.ascontiguousarray(out, np.float32)
+
+
+def sample_disparity_px(raw_u16, window, flip, ho, wo):  # pylint: disable=redefined-outer-name
+  """The arithmetic of lsi_augment_sample_u16 on one H x W map of 16-bit
+  disparities (value = disparity * 256, 0 = no match), and the host route of
+  the loaders: output pixel (i, k) takes the pixel of the
+  window under its centre, row y0 + min(((2 i + 1) ch) // (2 ho), ch - 1),
+  columns alike, as float32((raw / 256.0) * (wo / float(cw))) -- pixels of the
+  ho x wo image; float64, rounded once -- and lands at column wo - 1 - k under
+  a flip.  Zeros stay zeros and the sign does not change: the flipped pair's
+  baseline changes sign in t and the loss uses |t_x|.  The full window without
+  flip gives the bits of data.load_disparity_px.  Returns float32 ho x wo x 1."""
+  raw = np.asarray(raw_u16)
+  if raw.ndim != 2 or raw.dtype.kind not in 'iu':
+    raise ValueError('an H x W integer map is needed')
+  y0, x0, ch, cw = (int(v) for v in window)
+  if not (0 <= y0 and ch >= 1 and y0 + ch <= raw.shape[0] and
+          0 <= x0 and cw >= 1 and x0 + cw <= raw.shape[1]):
+    raise ValueError('window %r leaves the %d x %d map' % (window, raw.shape[0], raw.shape[1]))
+  raw = raw.astype(np.int64)
+  ys = y0 + np.minimum(((2 * np.arange(ho, dtype=np.int64) + 1) * ch) // (2 * ho), ch - 1)
+  xs = x0 + np.minimum(((2 * np.arange(wo, dtype=np.int64) + 1) * cw) // (2 * wo), cw - 1)
+  out = (raw[ys][:, xs] / 256.0 * (wo / float(cw))).astype(np.float32)
+  if flip:
+    out = out[:, ::-1]
+  return np.ascontiguousarray(out[:, :, None], np.float32)
+
+
+def augment_projection(mat_3x4, shape, win, flip, h, w, dtype=np.float32):
+  """velodyne.velo_to_image's 3 x 4 matrix (scanner -> pixel areas of the whole
+  image resized to w x h) for the augmented view, row for row what
+  augment_cameras does to the intrinsics: with (y0, x0, ch, cw) = win and
+  (H, W) = shape,
+    row0' = row0 (W / cw) - (x0 w / cw) row2,  row1' alike with H, ch, y0, h;
+    flip: row0'' = w row2 - row0'
+  in float64, rounded to `dtype` once.  Row 2 -- every depth -- is untouched,
+  and so are the scans: view 0 stays camera 2 = source.  The full window
+  without flip returns the input bits."""
+  y0, x0, ch, cw = (int(v) for v in win)
+  m = np.array(mat_3x4, np.float64).reshape(3, 4)
+  # (x - 0 * r is x but for the sign of a zero: an offset of 0 subtracts nothing)
+  m[0] = m[0] * (shape[1] / float(cw)) - ((x0 * (w / float(cw))) * m[2] if x0 else 0.0)
+  m[1] = m[1] * (shape[0] / float(ch)) - ((y0 * (h / float(ch))) * m[2] if y0 else 0.0)
+  if flip:
+    m[0] = w * m[2] - m[0]
+  return m.astype(dtype)
 
 
 def augment_cameras(k_s, k_t, rot, t, src_shape, trg_shape, win_s, win_t, flip, h, w):

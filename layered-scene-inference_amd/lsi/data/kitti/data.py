@@ -169,18 +169,46 @@ def load_disparity_px(path, h, w):
   return disp[:, :, None]
 
 
+def decode_u16(path):
+  """The H x W uint16 values of a 16-bit disparity PNG (load_disparity_px's
+  decode and its refusal of any other mode)."""
+  from PIL import Image  # pylint: disable=g-import-not-at-top
+  with Image.open(path) as im:
+    if im.mode not in ('I;16', 'I;16B', 'I;16L', 'I'):
+      raise ValueError('%s is no 16-bit disparity map (mode %s)' % (path, im.mode))
+    raw = np.asarray(im)
+  if raw.ndim != 2 or raw.min() < 0 or raw.max() > 65535:
+    raise ValueError('%s is no 16-bit disparity map (shape %r)' % (path, raw.shape))
+  return raw.astype(np.uint16)
+
+
+def pad_scans(scans):
+  """(velo_pts [bs, Nmax, 4] float32, velo_n [bs] int32) of a batch's scans:
+  rows past a scan's count NaN, Nmax the longest count rounded up to a multiple
+  of 4 (at least 4)."""
+  counts = np.array([len(s) for s in scans], np.int32)
+  n_max = max(4, (int(counts.max()) + 3) // 4 * 4)
+  pts = np.full((len(scans), n_max, 4), np.nan, np.float32)
+  for k, scan in enumerate(scans):
+    pts[k, :len(scan)] = scan
+  return pts, counts
+
+
 class DataLoader(object):
   """KITTI data loading class (reference :78-385).
 
   opts needs: batch_size, kitti_data_root, kitti_dataset_variant ('raw_city',
   'mview' or 'odom'), data_split ('train' | 'val' | 'test'), img_height,
   img_width[, kitti_dl_disparities, kitti_dl_disparities_px, kitti_dl_velodyne,
-  lidar_origin]."""
+  lidar_origin, kitti_gt_everywhere]."""
 
   def __init__(self, opts):
     self.opts = opts
     self.batch_size = opts.batch_size
     self.dataset_variant = opts.kitti_dataset_variant
+    # --kitti_gt_everywhere: the pixel disparities and the scans are emitted on
+    # the train split too, augmented with their pair, by either loader
+    self.gt_everywhere = bool(getattr(opts, 'kitti_gt_everywhere', False))
     self.output_disparities = (
         self.dataset_variant == 'raw_city' and
         bool(getattr(opts, 'kitti_dl_disparities', False)) and
@@ -190,13 +218,13 @@ class DataLoader(object):
     self.output_disparities_px = (
         self.dataset_variant == 'raw_city' and
         bool(getattr(opts, 'kitti_dl_disparities_px', False)) and
-        opts.data_split != 'train')
+        (opts.data_split != 'train' or self.gt_everywhere))
     # the Velodyne scan of every pair with its two projections (velodyne.py):
     # three more outputs after everything else
     self.output_velodyne = (
         self.dataset_variant == 'raw_city' and
         bool(getattr(opts, 'kitti_dl_velodyne', False)) and
-        opts.data_split != 'train')
+        (opts.data_split != 'train' or self.gt_everywhere))
     self.lidar_origin = float(getattr(opts, 'lidar_origin', 0.0))
     self.root_dir = opts.kitti_data_root
     if self.dataset_variant == 'odom':
@@ -222,13 +250,19 @@ class DataLoader(object):
     self.augment = None
     if bool(getattr(opts, 'kitti_augment', False)):
       from lsi.data.kitti import augment  # pylint: disable=g-import-not-at-top
-      if (self.output_disparities or self.output_disparities_px or
-          self.output_velodyne):
+      if self.output_disparities or (
+          (self.output_disparities_px or self.output_velodyne) and
+          not self.gt_everywhere):
         raise ValueError(
             '--kitti_augment transforms the images and the cameras, not ground '
             'truth: a loader that emits disparities or Velodyne scans '
             '(--kitti_dl_disparities, --kitti_dl_disparities_px, '
-            '--kitti_dl_velodyne) cannot augment')
+            '--kitti_dl_velodyne) cannot augment'
+            + (' (--kitti_gt_everywhere true augments the last two; the 8-bit '
+               '--kitti_dl_disparities maps stay as they are)'
+               if not self.gt_everywhere else
+               ': --kitti_gt_everywhere covers --kitti_dl_disparities_px and '
+               '--kitti_dl_velodyne, not the 8-bit --kitti_dl_disparities maps'))
       self.augment = augment.options_from(opts)
       self.aug_seed = int(getattr(opts, 'aug_seed', 0))
       self._aug_rng = np.random.RandomState(self.aug_seed)
@@ -364,11 +398,39 @@ class DataLoader(object):
         augment.window(aug, src_shape[0], src_shape[1]),
         augment.window(aug, trg_shape[0], trg_shape[1]), aug.flip, self.h, self.w)
 
+  def load_scan_or_empty(self, i):
+    """The scan of sample i; a frame whose file is missing has 0 points."""
+    from lsi.data.kitti import velodyne  # pylint: disable=g-import-not-at-top
+    if not os.path.exists(self.scan_list[i]):
+      return np.zeros((0, 4), np.float32)
+    return velodyne.load_scan(self.scan_list[i])
+
+  def velodyne_matrices(self, i, src_shape, trg_shape, aug=None):
+    """[2, 12] float32: velodyne.velo_to_image of sample i into view 0 = camera
+    2 / source and view 1 = camera 3 / target, through augment.augment_projection
+    when the pair is augmented by `aug`."""
+    from lsi.data.kitti import velodyne  # pylint: disable=g-import-not-at-top
+    seq = self.seq_id_list[i]
+    mats = []
+    for cam, shape in ((2, src_shape), (3, trg_shape)):
+      m = velodyne.velo_to_image(self.cam_calibration[seq], self.velo_calibration[seq],
+                                 cam, shape, self.h, self.w, self.lidar_origin)
+      if aug is not None:
+        from lsi.data.kitti import augment  # pylint: disable=g-import-not-at-top
+        m = augment.augment_projection(
+            m, shape, augment.window(aug, shape[0], shape[1]), aug.flip, self.h, self.w)
+      mats.append(m.reshape(12))
+    return np.stack(mats)
+
   def _forward_augmented(self, ids):
     """forward() with --kitti_augment: one PairAugment per sample from
-    _aug_rng, in sample order; uint8 decode, augment.augment_area_resize."""
+    _aug_rng, in sample order; uint8 decode, augment.augment_area_resize.  With
+    --kitti_gt_everywhere the pair's ground truth goes through the same
+    PairAugment: augment.sample_disparity_px over the map's own window,
+    augment.augment_projection over each view's."""
     from lsi.data.kitti import augment, pipeline  # pylint: disable=g-import-not-at-top
     instances = []
+    px, scans, velo_mats = ([], []), [], []
     for i in ids:
       aug = augment.sample(self._aug_rng, self.augment)
       imgs, shapes = [], []
@@ -381,7 +443,21 @@ class DataLoader(object):
         shapes.append(arr.shape)
       instances.append(tuple(imgs) + self.augmented_cameras(
           aug, shapes[0], shapes[1], self.cam_calibration[self.seq_id_list[i]]))
-    return [np.stack([inst[k] for inst in instances]) for k in range(6)]
+      if self.output_disparities_px:
+        for view, lst in enumerate((self.img_list_disp_src, self.img_list_disp_trg)):
+          raw = decode_u16(lst[i])
+          px[view].append(augment.sample_disparity_px(
+              raw, augment.window(aug, raw.shape[0], raw.shape[1]), aug.flip,
+              self.h, self.w))
+      if self.output_velodyne:
+        scans.append(self.load_scan_or_empty(i))
+        velo_mats.append(self.velodyne_matrices(i, shapes[0], shapes[1], aug))
+    out = [np.stack([inst[k] for inst in instances]) for k in range(6)]
+    if self.output_disparities_px:
+      out += [np.stack(px[0]), np.stack(px[1])]
+    if self.output_velodyne:
+      out += list(pad_scans(scans)) + [np.stack(velo_mats)]
+    return out
 
   def forward(self, bs):
     """bs instances: [img_s, img_t, k_s, k_t, rot, trans(, disp_s, disp_t)
@@ -413,15 +489,8 @@ class DataLoader(object):
         px_s.append(load_disparity_px(self.img_list_disp_src[i], self.h, self.w))
         px_t.append(load_disparity_px(self.img_list_disp_trg[i], self.h, self.w))
       if self.output_velodyne:
-        from lsi.data.kitti import velodyne  # pylint: disable=g-import-not-at-top
-        scans.append(velodyne.load_scan(self.scan_list[i])
-                     if os.path.exists(self.scan_list[i]) else
-                     np.zeros((0, 4), np.float32))
-        seq = self.seq_id_list[i]
-        velo_mats.append(np.stack([
-            velodyne.velo_to_image(self.cam_calibration[seq], self.velo_calibration[seq],
-                                   cam, shape, self.h, self.w, self.lidar_origin).reshape(12)
-            for cam, shape in ((2, src_shape), (3, trg_shape))]))
+        scans.append(self.load_scan_or_empty(i))
+        velo_mats.append(self.velodyne_matrices(i, src_shape, trg_shape))
     out = [np.stack([inst[k] for inst in instances]) for k in range(6)]
     if self.output_disparities:
       out.append(np.stack(disps_s))
@@ -430,10 +499,5 @@ class DataLoader(object):
       out.append(np.stack(px_s))
       out.append(np.stack(px_t))
     if self.output_velodyne:
-      counts = np.array([len(s) for s in scans], np.int32)
-      n_max = max(4, (int(counts.max()) + 3) // 4 * 4)
-      pts = np.full((bs, n_max, 4), np.nan, np.float32)
-      for k, scan in enumerate(scans):
-        pts[k, :len(scan)] = scan
-      out += [pts, counts, np.stack(velo_mats)]
+      out += list(pad_scans(scans)) + [np.stack(velo_mats)]
     return out

@@ -29,12 +29,23 @@ route the workers write pixels as before and forward() fills the augmented
 descriptors and the tone tables into the same staging buffer: still one upload
 and one launch (lsi_augment_resize_u8) per output tensor.
 
+With the wrapped loader's --kitti_gt_everywhere on, its pixel disparities and
+Velodyne scans go through the same pool, behind the images of their batch.  The
+host route runs augment.sample_disparity_px / velodyne.load_scan in the workers:
+the synchronous loader's batch, bit for bit.  On the device route a worker
+decodes a 16-bit map to uint16 into the staging buffer and reads a scan's bytes
+into it; forward() fills the map descriptors and issues one
+lsi_augment_sample_u16 launch for the 2 bs maps behind the one upload, and
+returns device tensors for the maps (the two halves of that launch's output) and
+for velo_pts (NaN-padded on the device), NumPy arrays for velo_n and velo_mats.
+
 A staging buffer goes back to the pool only when an event recorded behind its
 upload has completed.  A decode error is raised from the forward() that owns the
 sample and names the file.  close() stops the workers; a collected loader or an
 exiting interpreter does not wait on more than the decodes already running.
 """
 import collections
+import os
 import threading
 import time
 import weakref
@@ -149,19 +160,45 @@ def augment_resize_u8(packed, desc_host, desc_dev, n, h, w, nc, tables_offset=0,
   return out
 
 
+def augment_sample_u16(packed, desc_host, desc_dev, n, h, w, out=None):
+  """lsi_augment_sample_u16 on the current stream: nearest-neighbour samples of
+  the n 16-bit disparity maps in `packed` through the windows and flips of
+  their AUG_DESC_DTYPE records (C = 1, table -1), in pixels of the h x w image
+  (augment.sample_disparity_px's bits).  Returns float32 [n, h, w, 1]."""
+  import torch  # pylint: disable=g-import-not-at-top
+  from lsi import _C  # pylint: disable=g-import-not-at-top
+  if not packed.is_cuda:
+    raise RuntimeError('the device disparity sampling needs a ROCm GPU (got device '
+                       '%s); there is no CPU fallback' % packed.device)
+  if packed.dtype != torch.uint8 or not packed.is_contiguous():
+    raise RuntimeError('packed must be a contiguous uint8 tensor')
+  desc_host = np.ascontiguousarray(desc_host, AUG_DESC_DTYPE)
+  if desc_host.shape != (n,):
+    raise ValueError('%d descriptors for %d maps' % (desc_host.size, n))
+  if out is None:
+    out = torch.empty((n, h, w, 1), dtype=torch.float32, device=packed.device)
+  _C.check(_C.lib().lsi_augment_sample_u16(
+      n, desc_host.ctypes.data, int(desc_dev), packed.data_ptr(), packed.numel(),
+      h, w, out.data_ptr(), _C.stream_ptr(packed.device)), 'lsi_augment_sample_u16')
+  return out
+
+
 class _Staging(object):
   """One pinned buffer: [descriptors | pixel bytes], filled by the workers of
   one batch.  alloc() hands out 16-byte aligned ranges; a range that does not
   fit is refused and the image travels as its own array (the batch is then
   re-packed into a larger buffer).  An augmenting loader's buffer holds
-  AUG_DESC_DTYPE records and, behind them, n_tables tone tables:
-  [descriptors | tables | pixel bytes]."""
+  AUG_DESC_DTYPE records and, behind them, n_tables tone tables; a loader that
+  emits pixel disparities adds n_maps AUG_DESC_DTYPE records for the 16-bit
+  maps, whose pixels (and the bytes of Velodyne scans) lie among the images':
+  [descriptors | tables | map descriptors | pixel bytes]."""
 
-  def __init__(self, n_desc, capacity, n_tables=0, dtype=DESC_DTYPE):
+  def __init__(self, n_desc, capacity, n_tables=0, dtype=DESC_DTYPE, n_maps=0):
     import torch  # pylint: disable=g-import-not-at-top
     self.tables_offset = _round16(n_desc * dtype.itemsize)
     self.n_tables = n_tables
-    self.header = self.tables_offset + _round16(n_tables * TABLE_BYTES)
+    self.maps_offset = self.tables_offset + _round16(n_tables * TABLE_BYTES)
+    self.header = self.maps_offset + _round16(n_maps * AUG_DESC_DTYPE.itemsize)
     self.capacity = _round16(capacity)
     self.tensor = torch.empty(self.header + self.capacity + 16, dtype=torch.uint8,
                               pin_memory=True)
@@ -169,6 +206,8 @@ class _Staging(object):
     self.desc = self.bytes[:n_desc * dtype.itemsize].view(dtype)
     self.tables = self.bytes[self.tables_offset:self.tables_offset +
                              n_tables * TABLE_BYTES].reshape(n_tables, 3, 256)
+    self.map_desc = self.bytes[self.maps_offset:self.maps_offset +
+                               n_maps * AUG_DESC_DTYPE.itemsize].view(AUG_DESC_DTYPE)
     self.lock = threading.Lock()
     self.reset()
 
@@ -228,6 +267,75 @@ def _device_task(stop, path, nc, staging, slot):
   return (h, w, nc), None
 
 
+def _host_px_task(stop, path, h, w, aug):
+  """The h x w x 1 pixel disparities of one map, as the synchronous loader
+  makes them."""
+  from lsi.data.kitti import augment  # pylint: disable=g-import-not-at-top
+  if stop.is_set():
+    raise RuntimeError('the loader was closed')
+  if aug is None:
+    return kitti_data.load_disparity_px(path, h, w)
+  raw = kitti_data.decode_u16(path)
+  return augment.sample_disparity_px(
+      raw, augment.window(aug, raw.shape[0], raw.shape[1]), aug.flip, h, w)
+
+
+def _scan_path_points(path):
+  """Points of the scan file, 0 for a missing one; the refusal of
+  velodyne.load_scan for a length that is no multiple of a point."""
+  if not os.path.exists(path):
+    return 0
+  size = os.path.getsize(path)
+  if size % 16 != 0:
+    raise ValueError('%s is no Velodyne scan: %d bytes is not a multiple of the '
+                     '16 bytes of a point' % (path, size))
+  return size // 16
+
+
+def _host_scan_task(stop, path):
+  from lsi.data.kitti import velodyne  # pylint: disable=g-import-not-at-top
+  if stop.is_set():
+    raise RuntimeError('the loader was closed')
+  if not _scan_path_points(path):
+    return np.zeros((0, 4), np.float32)
+  return velodyne.load_scan(path)
+
+
+def _device_px_task(stop, path, staging, slot):
+  """Decodes the 16-bit map `path` into `staging` as host-order uint16 and
+  fills the image fields of map descriptor `slot`.  Returns (shape, None) or,
+  when the buffer is full, (shape, uint16 array)."""
+  if stop.is_set():
+    raise RuntimeError('the loader was closed')
+  raw = kitti_data.decode_u16(path)
+  h, w = raw.shape
+  off = staging.alloc(raw.nbytes)
+  if off is None:
+    return (h, w, 1), np.ascontiguousarray(raw)
+  staging.bytes[off:off + raw.nbytes].view(np.uint16).reshape(h, w)[...] = raw
+  _set_image(staging.map_desc, slot, off, h, w, 1)
+  return (h, w, 1), None
+
+
+def _device_scan_task(stop, path, staging):
+  """Reads the scan `path` into `staging`.  Returns (points, byte offset, None)
+  or, when the buffer is full, (points, None, float32 [points, 4] array); a
+  missing file is a scan of 0 points."""
+  if stop.is_set():
+    raise RuntimeError('the loader was closed')
+  n = _scan_path_points(path)
+  if n == 0:
+    return 0, 0, None
+  off = staging.alloc(16 * n)
+  if off is None:
+    from lsi.data.kitti import velodyne  # pylint: disable=g-import-not-at-top
+    return n, None, velodyne.load_scan(path)[:n]
+  with open(path, 'rb') as f:
+    if f.readinto(memoryview(staging.bytes[off:off + 16 * n])) != 16 * n:
+      raise ValueError('%s: the scan changed while it was read' % path)
+  return n, off, None
+
+
 def _named(path, err):
   """`err` if it names the file, else an error of its type's family that does."""
   if path in str(err):
@@ -249,16 +357,22 @@ class PrefetchLoader(object):
                device=None, world_size=1):
     if resize not in ('host', 'device'):
       raise ValueError("resize must be 'host' or 'device', got %r" % (resize,))
-    if getattr(loader, 'output_disparities_px', False):
+    # (a loader without the attribute -- any object but data.DataLoader -- is
+    # refused as before)
+    gt_everywhere = bool(getattr(loader, 'gt_everywhere', False))
+    if getattr(loader, 'output_disparities_px', False) and not gt_everywhere:
       raise ValueError(
           'kitti_dl_disparities_px (the pixel disparities --eval_depth scores '
           'against) is served by the synchronous loader only: run with '
-          '--data_workers 0 --kitti_resize host')
-    if getattr(loader, 'output_velodyne', False):
+          '--data_workers 0 --kitti_resize host (or with --kitti_gt_everywhere '
+          'true)')
+    if getattr(loader, 'output_velodyne', False) and not gt_everywhere:
       raise ValueError(
           'kitti_dl_velodyne (the Velodyne scans --eval_depth scores against) is '
           'served by the synchronous loader only: run with --data_workers 0 '
-          '--kitti_resize host')
+          '--kitti_resize host (or with --kitti_gt_everywhere true)')
+    self._gt_px = gt_everywhere and bool(getattr(loader, 'output_disparities_px', False))
+    self._gt_velo = gt_everywhere and bool(getattr(loader, 'output_velodyne', False))
     self.loader = loader
     self.resize = resize
     self.depth = max(1, int(prefetch_depth))
@@ -339,15 +453,19 @@ class PrefetchLoader(object):
       try:
         with Image.open(first_path) as im:
           self._capacity = _round16(im.size[0] * im.size[1] * 3) * n_desc
+          if self._gt_px:  # two bytes per pixel of every map
+            self._capacity += _round16(im.size[0] * im.size[1] * 2) * 2 * self._bs
       except Exception:  # pylint: disable=broad-except
         self._capacity = 1 << 20  # (the decode task reports the file)
     return self._new_staging(n_desc, self._capacity)
 
   def _new_staging(self, n_desc, capacity):
+    n_maps = 2 * self._bs if self._gt_px else 0
     if getattr(self.loader, 'augment', None) is None:
-      return _Staging(n_desc, capacity)
+      return _Staging(n_desc, capacity, n_maps=n_maps)
     # one tone table per pair: the two views share it
-    return _Staging(n_desc, capacity, n_tables=n_desc // 2, dtype=AUG_DESC_DTYPE)
+    return _Staging(n_desc, capacity, n_tables=n_desc // 2, dtype=AUG_DESC_DTYPE,
+                    n_maps=n_maps)
 
   # -- scheduling -------------------------------------------------------------
   def _schedule(self, bs):
@@ -376,7 +494,33 @@ class PrefetchLoader(object):
     else:
       futs = [self._pool.submit(_host_task, self._stop, p, ld.h, ld.w, nc)
               for p, nc in paths]
+    if self._gt_px or self._gt_velo:
+      self._schedule_gt(ids, paths, futs, staging, augs)
     self._pending.append((ids, paths, futs, staging, augs))
+
+  def _schedule_gt(self, ids, paths, futs, staging, augs):
+    """--kitti_gt_everywhere: the tasks of the batch's 16-bit maps (source
+    views, then target views) and scans, behind those of its images."""
+    ld = self.loader
+    bs = len(ids)
+    device = self.resize == 'device'
+    if self._gt_px:
+      for slot, (lst, i) in enumerate(
+          (lst, i) for lst in (ld.img_list_disp_src, ld.img_list_disp_trg) for i in ids):
+        paths.append((lst[i], 'px'))
+        if device:
+          futs.append(self._pool.submit(_device_px_task, self._stop, lst[i], staging, slot))
+        else:
+          futs.append(self._pool.submit(_host_px_task, self._stop, lst[i], ld.h, ld.w,
+                                        augs[slot % bs] if augs is not None else None))
+    if self._gt_velo:
+      for i in ids:
+        paths.append((ld.scan_list[i], 'scan'))
+        if device:
+          futs.append(self._pool.submit(_device_scan_task, self._stop, ld.scan_list[i],
+                                        staging))
+        else:
+          futs.append(self._pool.submit(_host_scan_task, self._stop, ld.scan_list[i]))
 
   def forward(self, bs):
     """The next batch of the wrapped loader's sequence (module doc)."""
@@ -404,6 +548,12 @@ class PrefetchLoader(object):
       if staging is not None:
         self._free.append(staging)  # never uploaded: free at once
       raise error
+    gt = None
+    if self._gt_px or self._gt_velo:
+      # the tasks of _schedule_gt: 2 bs maps, then bs scans, behind the images
+      n_img = len(paths) - (2 * bs if self._gt_px else 0) - (bs if self._gt_velo else 0)
+      gt = results[n_img:]
+      paths, results = paths[:n_img], results[:n_img]
     shapes = [r[0] if self.resize == 'device' else r[1] for r in results]
     if augs is None:
       cams = [kitti_data.pair_cameras(ld.cam_calibration[ld.seq_id_list[i]],
@@ -417,9 +567,31 @@ class PrefetchLoader(object):
     if self.resize == 'host':
       imgs = [np.stack([r[0] for r in results[g * bs:(g + 1) * bs]])
               for g in range(len(paths) // bs)]
+      if gt is not None:
+        imgs += self._host_gt(gt, ids, shapes, augs)
       return imgs[:2] + out_cams + imgs[2:]
-    imgs = self._upload_and_resize(staging, results, bs, augs)
+    imgs = self._upload_and_resize(staging, results, bs, augs, gt)
+    if self._gt_velo:  # (the matrices stay on the host, like the cameras)
+      imgs.append(self._velo_mats(ids, shapes, augs))
     return imgs[:2] + out_cams + imgs[2:]
+
+  def _velo_mats(self, ids, shapes, augs):
+    bs = len(ids)
+    return np.stack([self.loader.velodyne_matrices(
+        i, shapes[j], shapes[bs + j], augs[j] if augs is not None else None)
+                     for j, i in enumerate(ids)])
+
+  def _host_gt(self, gt, ids, shapes, augs):
+    """The synchronous loader's ground-truth outputs from the workers' results:
+    [disp_px_s, disp_px_t][velo_pts, velo_n, velo_mats]."""
+    bs = len(ids)
+    out = []
+    if self._gt_px:
+      out += [np.stack(gt[:bs]), np.stack(gt[bs:2 * bs])]
+      gt = gt[2 * bs:]
+    if self._gt_velo:
+      out += list(kitti_data.pad_scans(gt)) + [self._velo_mats(ids, shapes, augs)]
+    return out
 
   def _fill_augment(self, staging, augs, bs):
     """The windows, flip bits, table indices and gains of the 2 bs images, and
@@ -439,11 +611,29 @@ class PrefetchLoader(object):
         rec['gain'] = gains
         rec['reserved'] = rec['reserved2'] = 0
 
-  def _upload_and_resize(self, staging, results, bs, augs=None):
+  def _fill_maps(self, staging, augs, bs):
+    """The windows and flip bits of the 2 bs disparity maps, each window from
+    the map's own shape (pair j: slots j, bs + j); no table, gains of 1."""
+    from lsi.data.kitti import augment  # pylint: disable=g-import-not-at-top
+    desc = staging.map_desc
+    for slot in range(2 * bs):
+      aug = augs[slot % bs] if augs is not None else None
+      rec = desc[slot:slot + 1]
+      h, w = int(desc['H'][slot]), int(desc['W'][slot])
+      rec['y0'], rec['x0'], rec['ch'], rec['cw'] = (
+          augment.window(aug, h, w) if aug is not None else (0, 0, h, w))
+      rec['flags'] = AUG_FLIP if aug is not None and aug.flip else 0
+      rec['table'], rec['gain'] = -1, 1.0
+      rec['reserved'] = rec['reserved2'] = 0
+
+  def _upload_and_resize(self, staging, results, bs, augs=None, gt=None):
     import torch  # pylint: disable=g-import-not-at-top
     ld = self.loader
     spilled = [(slot, r[1]) for slot, r in enumerate(results) if r[1] is not None]
-    if spilled:
+    maps = gt[:2 * bs] if self._gt_px else []
+    scans = list(gt[2 * bs if self._gt_px else 0:]) if self._gt_velo else []
+    gt_spilled = any(r[-1] is not None for r in maps + scans)
+    if spilled or gt_spilled:
       # the buffer was too small: a larger one takes the whole batch (and sets
       # the size of the buffers made from now on)
       self._capacity = _round16(staging.wanted - staging.header) * 5 // 4
@@ -456,9 +646,22 @@ class PrefetchLoader(object):
         off = big.alloc(arr.size)
         big.bytes[off:off + arr.size].reshape(arr.shape)[...] = arr
         _set_image(big.desc, slot, off, arr.shape[0], arr.shape[1], arr.shape[2])
+      big.map_desc[...] = staging.map_desc
+      for slot, (_, arr) in enumerate(maps):
+        if arr is not None:
+          off = big.alloc(arr.nbytes)
+          big.bytes[off:off + arr.nbytes].view(np.uint16).reshape(arr.shape)[...] = arr
+          _set_image(big.map_desc, slot, off, arr.shape[0], arr.shape[1], 1)
+      for k, (n, _, arr) in enumerate(scans):
+        if arr is not None:
+          off = big.alloc(arr.nbytes)
+          big.bytes[off:off + arr.nbytes].view(np.float32).reshape(arr.shape)[...] = arr
+          scans[k] = (n, off, None)
       staging = big
     if augs is not None:
       self._fill_augment(staging, augs, bs)
+    if self._gt_px:
+      self._fill_maps(staging, augs, bs)
     used = staging.used + 16  # the pad behind the last image
     with torch.cuda.device(self.device):
       packed = torch.empty(used, dtype=torch.uint8, device=self.device)
@@ -471,14 +674,33 @@ class PrefetchLoader(object):
         both = augment_resize_u8(packed, staging.desc, packed.data_ptr(), 2 * bs,
                                  ld.h, ld.w, 3, staging.tables_offset,
                                  staging.n_tables)
-        return [both[:bs], both[bs:]]
-      for g, nc in enumerate((3, 1) if ld.output_disparities else (3,)):
-        n = 2 * bs
-        first = g * n
-        both = area_resize_u8(
-            packed, staging.desc[first:first + n],
-            packed.data_ptr() + first * DESC_DTYPE.itemsize, n, ld.h, ld.w, nc)
+        out = [both[:bs], both[bs:]]
+        if gt is None:
+          return out
+      else:
+        for g, nc in enumerate((3, 1) if ld.output_disparities else (3,)):
+          n = 2 * bs
+          first = g * n
+          both = area_resize_u8(
+              packed, staging.desc[first:first + n],
+              packed.data_ptr() + first * DESC_DTYPE.itemsize, n, ld.h, ld.w, nc)
+          out += [both[:bs], both[bs:]]
+      if self._gt_px:
+        # one launch for the 2 bs maps, [source views; target views]: the halves
+        # are views of one tensor, which the trainer takes whole
+        both = augment_sample_u16(packed, staging.map_desc,
+                                  packed.data_ptr() + staging.maps_offset, 2 * bs,
+                                  ld.h, ld.w)
         out += [both[:bs], both[bs:]]
+      if self._gt_velo:
+        counts = np.array([s[0] for s in scans], np.int32)
+        n_max = max(4, (int(counts.max()) + 3) // 4 * 4)
+        pts = torch.full((bs, n_max, 4), float('nan'), dtype=torch.float32,
+                         device=self.device)
+        for k, (n, off, _) in enumerate(scans):
+          if n:
+            pts[k, :n] = packed[off:off + 16 * n].view(torch.float32).view(n, 4)
+        out += [pts, counts]
     return out
 
   # -- shutdown ---------------------------------------------------------------

@@ -50,8 +50,9 @@ def read_velo_calib(path):
   return calib['R'].reshape(3, 3), calib['T'].reshape(3)
 
 
-def velo_to_image(calib_cam, calib_velo, cam, src_shape, h, w, origin=0.0):
-  """The 3 x 4 float32 matrix from scanner coordinates to the h x w image of
+def velo_to_image(calib_cam, calib_velo, cam, src_shape, h, w, origin=0.0,
+                  dtype=np.float32):
+  """The 3 x 4 float32 (`dtype`) matrix from scanner coordinates to the h x w image of
   rectified camera `cam` (2 or 3), composed in float64 (module doc).
   calib_cam: read_calib_file of calib_cam_to_cam.txt; calib_velo: (R, T) of
   read_velo_calib; src_shape: (H0, W0, ...) of the camera's native image."""
@@ -65,4 +66,4 @@ def velo_to_image(calib_cam, calib_velo, cam, src_shape, h, w, origin=0.0):
   m = proj @ rect @ velo
   m[0] = (w / float(src_shape[1])) * (m[0] + (0.5 - origin) * m[2])
   m[1] = (h / float(src_shape[0])) * (m[1] + (0.5 - origin) * m[2])
-  return m.astype(np.float32)
+  return m.astype(dtype)

@@ -350,7 +350,7 @@ int lsi_eval_depth_metrics(int32_t B, int32_t H, int32_t W, const float* pred,
                      (const SelState*)st, part);
   hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(TPB), 0, s, (const double*)part,
                      bpi, (int)B, (const SelState*)st, acc, per_image);
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
+  return rc_of_launch();
 }
 
 }  // extern "C"

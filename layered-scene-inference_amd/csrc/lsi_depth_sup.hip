@@ -4,9 +4,9 @@
 //   forward   a block covers a fixed span of rows of ONE plane (the grid is
 //             plane-aligned: BPP blocks per plane), a thread four neighbouring
 //             pixels of a row at a time; three sums per plane -- n (scored
-//             pixels), A, Q -- in fp64 from the thread up; a one-block
-//             finishing kernel adds the blocks' partial sums in a fixed order
-//             (a wave per plane), writes the 3 P plane sums and the loss.
+//             pixels), A, Q -- in fp64 from the thread up; the shared one-block
+//             finish (lsi_reduce.h) writes the 3 P plane sums and the loss,
+//             the mean of DsupTerm over the planes with a scored pixel.
 //   backward  the same pass; validity and d_i are recomputed from the inputs,
 //             the plane's constants and S from the plane sums.
 //
@@ -26,8 +26,7 @@ using namespace lsi;
 
 namespace {
 
-constexpr int SPAN = 1024;   // pixels of a block's span, at least (whole rows)
-constexpr int MAXBPP = 256;  // blocks (partial sums) per plane, at most
+constexpr int SPAN = 1024;  // pixels of a block's span, at least (whole rows)
 
 inline int rows_per_block(int H, int W) {
   const int a = (SPAN + W - 1) / W, b = (H + MAXBPP - 1) / MAXBPP;
@@ -101,15 +100,6 @@ __device__ __forceinline__ Quad load_quad(const DArgs& a, int p, int y, int x, i
   return v;
 }
 
-__device__ __forceinline__ float sgn(float v) {
-  return (float)(v > 0.0f) - (float)(v < 0.0f);
-}
-
-__device__ __forceinline__ double wave_total(double t) {
-  for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
-  return t;  // lane 0 holds the total
-}
-
 template <int MODE>
 __global__ __launch_bounds__(TPB) void dsup_fwd_kernel(DArgs a, double* part) {
   const int p = blockIdx.x / a.bpp, bx = blockIdx.x - p * a.bpp;
@@ -135,75 +125,20 @@ __global__ __launch_bounds__(TPB) void dsup_fwd_kernel(DArgs a, double* part) {
       }
     }
   }
-  // block sums (fixed order) to part[(k * P + p) * bpp + bx]
-  __shared__ double sm[3][TPB / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double s = wave_total(acc[k]);
-    if (lane == 0) sm[k][wave] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int k = threadIdx.x;
-    double s = 0.0;
-    for (int w = 0; w < TPB / 64; ++w) s += sm[k][w];
-    part[((size_t)k * a.d.P + p) * a.bpp + bx] = s;
-  }
+  plane_store_partials(acc, part, a.d.P, p, a.bpp, bx);
 }
 
-// One block of FIN_TPB threads.  Wave w adds up the planes w, w + 16, ...: lane j
-// the partial sums j, j + 64, j + 128, j + 192 of each of the three scalars (12
-// independent loads, issued together), then a shuffle tree; lane 0 writes the
-// plane's three sums and its term D_p (0 for a plane without a scored pixel) to
-// terms[p].  Wave 0 then adds the terms and counts S the same way.
-constexpr int FIN_TPB = 1024;
-static_assert(MAXBPP <= 4 * 64, "dsup_finish_kernel reads four partial sums per lane");
-
-__global__ __launch_bounds__(FIN_TPB) void dsup_finish_kernel(DArgs a, const double* part,
-                                                              double* terms,
-                                                              double* plane_sums,
-                                                              float* out_loss) {
-  const int P = a.d.P;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int p = wave; p < P; p += FIN_TPB / 64) {
-    double v[3][4];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double* q = part + ((size_t)k * P + p) * a.bpp;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        v[k][j] = (lane + 64 * j < a.bpp) ? q[lane + 64 * j] : 0.0;
-    }
-    double s[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      s[k] = wave_total(((v[k][0] + v[k][1]) + v[k][2]) + v[k][3]);
-    if (lane == 0) {
-      plane_sums[3 * (size_t)p + 0] = s[0];
-      plane_sums[3 * (size_t)p + 1] = s[1];
-      plane_sums[3 * (size_t)p + 2] = s[2];
-      double t = 0.0;
-      if (s[0] > 0.0) {
-        const double m = s[1] / s[0];
-        t = a.d.mode == LSI_DEPTH_SUP_SILOG ? s[2] / s[0] - (double)a.d.lam * m * m
-                                            : m;
-      }
-      terms[p] = t;
-    }
+// A plane's term D_p of its sums n, A, Q; a plane without a scored pixel does
+// not enter the mean.
+struct DsupTerm {
+  int mode;
+  double lam;
+  __device__ bool counts(const double* s) const { return s[0] > 0.0; }
+  __device__ double term(const double* s) const {
+    const double m = s[1] / s[0];
+    return mode == LSI_DEPTH_SUP_SILOG ? s[2] / s[0] - lam * m * m : m;
   }
-  __syncthreads();  // terms[] and plane_sums[] of every wave are visible to wave 0
-  if (wave == 0) {
-    double t = 0.0, S = 0.0;
-    for (int i = lane; i < P; i += 64) {
-      t += terms[i];
-      S += plane_sums[3 * (size_t)i] > 0.0 ? 1.0 : 0.0;
-    }
-    t = wave_total(t);
-    S = wave_total(S);
-    if (lane == 0) *out_loss = S > 0.0 ? (float)(t / S) : 0.0f;
-  }
-}
+};
 
 template <int MODE>
 __global__ __launch_bounds__(TPB) void dsup_bwd_kernel(DArgs a, const double* plane_sums,
@@ -290,18 +225,13 @@ DArgs args_of(const LsiDepthSupDesc* d, const float* pred, const float* gt,
   return a;
 }
 
-int rc_of_launch() {
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t lsi_depth_sup_workspace_bytes(const LsiDepthSupDesc* d) {
   if (!desc_ok(d)) return 0;
-  const size_t P = (size_t)d->P;
-  return (3 * P * blocks_per_plane(d->H, d->W) + P) * sizeof(double);
+  return plane_ws_doubles((size_t)d->P, blocks_per_plane(d->H, d->W)) * sizeof(double);
 }
 
 int lsi_depth_sup_loss_fwd(const LsiDepthSupDesc* d, const float* pred,
@@ -313,15 +243,14 @@ int lsi_depth_sup_loss_fwd(const LsiDepthSupDesc* d, const float* pred,
   if (ws_bytes < lsi_depth_sup_workspace_bytes(d)) return LSI_EWORKSPACE;
   const DArgs a = args_of(d, pred, gt, gt_scale, nullptr);
   double* part = (double*)ws;
-  double* terms = part + 3 * (size_t)d->P * a.bpp;
   const dim3 grid((unsigned)(d->P * a.bpp)), block(TPB);
   hipStream_t s = (hipStream_t)stream;
   if (d->mode == LSI_DEPTH_SUP_SILOG)
     hipLaunchKernelGGL((dsup_fwd_kernel<LSI_DEPTH_SUP_SILOG>), grid, block, 0, s, a, part);
   else
     hipLaunchKernelGGL((dsup_fwd_kernel<LSI_DEPTH_SUP_L1>), grid, block, 0, s, a, part);
-  hipLaunchKernelGGL(dsup_finish_kernel, dim3(1), dim3(FIN_TPB), 0, s, a,
-                     (const double*)part, terms, plane_sums, out_loss);
+  const DsupTerm f = {d->mode, (double)d->lam};
+  plane_finish(f, d->P, a.bpp, ws, plane_sums, out_loss, s);
   return rc_of_launch();
 }
 

@@ -4,9 +4,9 @@
 //   forward   one thread per pixel, a grid-stride pass over ONE plane per block
 //             (the grid is plane-aligned: BPP blocks per plane), three sums per
 //             plane -- A = sum |sx| wx, B = sum |sy| wy, S = sum d -- as fp32
-//             per thread, fp64 per block; a one-block finishing kernel adds the
-//             blocks' partial sums in a fixed order (a wave per plane), writes
-//             the 3 L B plane sums and the loss.
+//             per thread, fp64 per block; the shared one-block finish
+//             (lsi_reduce.h) writes the 3 L B plane sums and the loss, the mean
+//             of the planes' EdgeTerm.
 //   backward  the same pass in gather form: a pixel collects sign(s) w of the
 //             stencils that touch it (2 per axis at order 1, 3 at order 2),
 //             recomputing the weights from the guide, and subtracts the plane's
@@ -29,8 +29,7 @@ using namespace lsi;
 
 namespace {
 
-constexpr int PPT = 4;       // pixels per thread the grid is sized for
-constexpr int MAXBPP = 256;  // blocks (partial sums) per plane, at most
+constexpr int PPT = 4;  // pixels per thread the grid is sized for
 
 inline int blocks_per_plane(long n) {
   long g = (n + (long)TPB * PPT - 1) / ((long)TPB * PPT);
@@ -74,10 +73,6 @@ __device__ __forceinline__ Plane<FAST> plane_of(const EArgs& a, int p) {
   v.dsy = a.d.d_sy; v.dsx = a.d.d_sx;
   v.gsy = a.d.g_sy; v.gsx = a.d.g_sx; v.gsc = a.d.g_sc;
   return v;
-}
-
-__device__ __forceinline__ float sgn(float v) {
-  return (float)(v > 0.0f) - (float)(v < 0.0f);
 }
 
 // |s| w of the stencil anchored at position `pos` of an axis of extent n.
@@ -133,77 +128,20 @@ __global__ __launch_bounds__(TPB) void edge_fwd_kernel(EArgs a, double* part) {
         [&](int i0, int i1) { return v.E(y + i0, x, y + i1, x); });
     acc[2] += v.D(y, x);
   }
-  // block sums (fp64, fixed order) to part[(k * planes + p) * bpp + bx]
-  __shared__ double sm[3][TPB / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    double s = (double)acc[k];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if (lane == 0) sm[k][wave] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int k = threadIdx.x;
-    double s = 0.0;
-    for (int w = 0; w < TPB / 64; ++w) s += sm[k][w];
-    part[((size_t)k * a.d.L * a.d.B + p) * a.bpp + bx] = s;
-  }
+  plane_store_partials(acc, part, a.d.L * a.d.B, p, a.bpp, bx);
 }
 
-// One block of FIN_TPB threads.  Wave w adds up the planes w, w + 16, ...: lane j
-// the partial sums j, j + 64, j + 128, j + 192 of each of the three scalars (12
-// independent loads, issued together: a chain of dependent loads across XCDs
-// costs a microsecond per link), then a shuffle tree; lane 0 writes the plane's
-// three sums and its term k_p [A_p / (H (W - o)) + B_p / ((H - o) W)] to
-// terms[p].  The loss is the mean of the terms, summed by wave 0 the same way.
-constexpr int FIN_TPB = 1024;
-static_assert(MAXBPP <= 4 * 64, "edge_finish_kernel reads four partial sums per lane");
-
-__device__ __forceinline__ double wave_total(double t) {
-  for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
-  return t;  // lane 0 holds the total
-}
-
-__global__ __launch_bounds__(FIN_TPB) void edge_finish_kernel(EArgs a,
-                                                              const double* part,
-                                                              double* terms,
-                                                              double* plane_sums,
-                                                              float* out_loss) {
-  const int planes = a.d.L * a.d.B;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double n = (double)a.d.H * a.d.W;
-  const double nx = (double)a.d.H * (a.d.W - a.d.order);
-  const double ny = (double)(a.d.H - a.d.order) * a.d.W;
-  for (int p = wave; p < planes; p += FIN_TPB / 64) {
-    double v[3][4];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double* q = part + ((size_t)k * planes + p) * a.bpp;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        v[k][j] = (lane + 64 * j < a.bpp) ? q[lane + 64 * j] : 0.0;
-    }
-    double s[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      s[k] = wave_total(((v[k][0] + v[k][1]) + v[k][2]) + v[k][3]);
-    if (lane == 0) {
-      plane_sums[3 * (size_t)p + 0] = s[0];
-      plane_sums[3 * (size_t)p + 1] = s[1];
-      plane_sums[3 * (size_t)p + 2] = s[2];
-      const double kp = a.d.normalise ? 1.0 / (s[2] / n + (double)a.d.eps) : 1.0;
-      terms[p] = kp * (s[0] / nx + s[1] / ny);
-    }
+// A plane's term k_p [A_p / (H (W - o)) + B_p / ((H - o) W)] of its sums A, B, S;
+// every plane enters the mean.
+struct EdgeTerm {
+  double n, nx, ny, eps;
+  int normalise;
+  __device__ bool counts(const double*) const { return true; }
+  __device__ double term(const double* s) const {
+    const double kp = normalise ? 1.0 / (s[2] / n + eps) : 1.0;
+    return kp * (s[0] / nx + s[1] / ny);
   }
-  __syncthreads();  // terms[] of every wave are visible to wave 0
-  if (wave == 0) {
-    double t = 0.0;
-    for (int i = lane; i < planes; i += 64) t += terms[i];
-    t = wave_total(t);
-    if (lane == 0) *out_loss = (float)(t / (double)planes);
-  }
-}
+};
 
 template <int ORDER, bool FAST>
 __global__ __launch_bounds__(TPB) void edge_bwd_kernel(EArgs a,
@@ -262,18 +200,14 @@ EArgs args_of(const LsiEdgeSmoothDesc* d, const float* disp, const float* guide)
   return a;
 }
 
-int rc_of_launch() {
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t lsi_edge_smooth_workspace_bytes(const LsiEdgeSmoothDesc* d) {
   if (!desc_ok(d)) return 0;
-  const size_t planes = (size_t)d->L * d->B;
-  return (3 * planes * blocks_per_plane((long)d->H * d->W) + planes) * sizeof(double);
+  return plane_ws_doubles((size_t)d->L * d->B, blocks_per_plane((long)d->H * d->W)) *
+         sizeof(double);
 }
 
 int lsi_edge_smooth_loss_fwd(const LsiEdgeSmoothDesc* d, const float* disp,
@@ -286,7 +220,6 @@ int lsi_edge_smooth_loss_fwd(const LsiEdgeSmoothDesc* d, const float* disp,
   const EArgs a = args_of(d, disp, guide);
   const int planes = d->L * d->B;
   double* part = (double*)ws;
-  double* terms = part + 3 * (size_t)planes * a.bpp;
   const dim3 grid((unsigned)(planes * a.bpp)), block(TPB);
   hipStream_t s = (hipStream_t)stream;
   const bool fast = fast_layout(d);
@@ -297,8 +230,9 @@ int lsi_edge_smooth_loss_fwd(const LsiEdgeSmoothDesc* d, const float* disp,
     if (fast) hipLaunchKernelGGL((edge_fwd_kernel<2, true>), grid, block, 0, s, a, part);
     else hipLaunchKernelGGL((edge_fwd_kernel<2, false>), grid, block, 0, s, a, part);
   }
-  hipLaunchKernelGGL(edge_finish_kernel, dim3(1), dim3(FIN_TPB), 0, s, a,
-                     (const double*)part, terms, plane_sums, out_loss);
+  const EdgeTerm f = {(double)d->H * d->W, (double)d->H * (d->W - d->order),
+                      (double)(d->H - d->order) * d->W, (double)d->eps, d->normalise};
+  plane_finish(f, planes, a.bpp, ws, plane_sums, out_loss, s);
   return rc_of_launch();
 }
 

@@ -247,10 +247,6 @@ __global__ __launch_bounds__(256) void disocclusion_kernel(
   mask[si] = (1.0f - (trunc ? 1.0f : 0.0f)) * dis;
 }
 
-int rc_of_launch() {
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
-}
-
 constexpr int EVAL_NSUM = V_NSUM > L_NSUM ? V_NSUM : L_NSUM;
 
 void layer_view_of(const LsiLossDesc* d, const float* tex, const float* disp,

@@ -145,10 +145,6 @@ struct DArgs {
   const float* disp;
 };
 
-__device__ __forceinline__ float sgn(float v) {
-  return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f);
-}
-
 // second differences anchored at (y, x): the reference's gradient() applied
 // twice (forward differences of forward differences, each rounded)
 struct Stencil {
@@ -489,10 +485,6 @@ __global__ __launch_bounds__(TPB) void compose_bwd_kernel(CArgs a, const float* 
       }
     }
   }
-}
-
-int rc_of_launch() {
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
 }
 
 bool loss_desc_ok(const LsiLossDesc* d) {

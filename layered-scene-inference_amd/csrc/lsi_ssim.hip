@@ -366,10 +366,6 @@ __global__ __launch_bounds__(TPB) void ssim_bwd_kernel(SArgs a, const float* g_l
   }
 }
 
-int rc_of_launch() {
-  return hipGetLastError() == hipSuccess ? LSI_OK : LSI_ELAUNCH;
-}
-
 // win weights in double, normalised, rounded to fp32; sigma <= 0: the box
 bool window_weights(int win, float sigma, float* out) {
   if (win < 3 || win > MAXWIN || win % 2 == 0) return false;

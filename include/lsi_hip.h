@@ -671,6 +671,76 @@ int lsi_depth_sup_loss_bwd(const LsiDepthSupDesc* desc, const float* pred,
                            float* g_pred, lsi_stream_t stream);
 
 /*
+ * Geometric-consistency loss between two views' inverse depths
+ * (csrc/lsi_geo_cons.hip; no reference counterpart, the definition is DESIGN.md
+ * section 4.21): the differentiable counterpart of lsi_disocclusion_mask.
+ * disp [P,H,W] with the element strides d_s*, partner [P,H,W] with the element
+ * strides e_s*, M [P,4,4] contiguous device floats.  Pixel (x, y) of plane p with
+ * d = disp[p,y,x] is projected by M[p] under the renderer's floating-point
+ * contract (every operation a separately rounded fp32 operation):
+ *   q_j = ((px M[j][0] + py M[j][1]) + M[j][2]) + d M[j][3], px = x + .5, py = y + .5
+ *   n = q_2, n' = n + 1e-8 [n == 0], u = q_0 / n', v = q_1 / n', dd = q_3 / n'
+ *   s = c0 E00 + c1 E01 + c2 E10 + c3 E11 in that order: the bilinear sample of
+ *       plane r = (p + shift) mod P of partner at (u, v), taps and weights as
+ *       lsi_bilinear_fwd forms them (E01 is the tap at x0, y1)
+ * The paired form is partner = disp with shift = P / 2; two tensors use shift 0.
+ * The pixel is scored when d, u, v, dd are finite, n > 0, dd > 0,
+ * 0.5 <= u <= W - 0.5, 0.5 <= v <= H - 0.5, s > 0 and, with occl_thresh > 0,
+ * not s - dd > occl_thresh (s + dd) (the point would lie behind the partner's
+ * visible surface).  With dd and s widened to fp64:
+ *   LSI_GEO_CONS_RATIO   e = |dd - s| / (dd + s)
+ *   LSI_GEO_CONS_L1      e = |dd - s|
+ *   loss = 1 / S sum_{N_p > 0} (sum e over plane p) / N_p, N_p = scored pixels
+ *   of plane p, S = planes with N_p > 0; 0 when S = 0.
+ * Gradient w.r.t. disp and partner; the scored set and M are constants,
+ * sign(dd - s) is that of the fp32 values, sign(0) = 0, g = g_loss / (S N_p):
+ *   partner[r, tap k] += g de/ds c_k                      (c_k != 0)
+ *   disp[p, y, x]     += g (de/ddd ddd/dd + de/ds (ds/du du/dd + ds/dv dv/dd))
+ *   d(q_j / n')/dd = (M[j][3] n' - q_j M[2][3]) / n'^2; ds/du, ds/dv with the
+ *   weights' derivatives those of x1 - x and x - x0 (floor has gradient 0)
+ *   ratio: de/ddd = sign 2 s / (dd + s)^2, de/ds = -sign 2 dd / (dd + s)^2;
+ *   l1: sign, -sign.
+ * LSI_EINVAL for an unknown mode, non-positive dimensions, P > 65535,
+ * H W >= 2^24, P H W > INT32_MAX, shift outside [0, P) or occl_thresh outside
+ * [0, 1); then LSI_ENULL; then LSI_EWORKSPACE -- all before any launch.  No
+ * host synchronisation, no allocation: both directions can be captured in a
+ * HIP graph.  The forward has no atomics: the same inputs give the same loss,
+ * plane sums and map bit for bit.  The backward adds with fp32 global atomics:
+ * its last bits depend on the order the adds arrive in.
+ */
+#define LSI_GEO_CONS_RATIO 0
+#define LSI_GEO_CONS_L1 1
+typedef struct LsiGeoConsDesc {
+  int32_t P, H, W, mode;
+  int64_t d_sp, d_sy, d_sx;
+  int64_t e_sp, e_sy, e_sx;
+  int32_t shift;
+  float occl_thresh;
+} LsiGeoConsDesc;
+
+/* (3 P bpp + P) doubles: a block covers r = max(ceil(1024 / W), ceil(H / 256))
+ * rows of a plane, bpp = ceil(H / r) blocks per plane; 0 for a descriptor the
+ * entries below refuse. */
+size_t lsi_geo_cons_workspace_bytes(const LsiGeoConsDesc* desc);
+/* 2 launches.  out_loss (one device float) = the loss; plane_sums (3 P device
+ * doubles, the caller's) = sum e, N_p, 0 at [3 p .. 3 p + 2]: written by the
+ * finishing kernel, read by the backward.  out_map [P,H,W] contiguous or NULL:
+ * the per-pixel e as fp32, -1 where the pixel is not scored.  The library keeps
+ * no state. */
+int lsi_geo_cons_loss_fwd(const LsiGeoConsDesc* desc, const float* disp,
+                          const float* partner, const float* M, float* out_loss,
+                          double* plane_sums, float* out_map, void* workspace,
+                          size_t workspace_bytes, lsi_stream_t stream);
+/* 1 launch after the zero-fill of the outputs on the stream.  g_disp and
+ * g_partner [P,H,W] contiguous, scaled by the device scalar g_loss.  g_partner
+ * NULL (or g_disp itself) is the paired form: the taps' contributions land in
+ * g_disp, at plane r, next to the pixels' own. */
+int lsi_geo_cons_loss_bwd(const LsiGeoConsDesc* desc, const float* disp,
+                          const float* partner, const float* M,
+                          const double* plane_sums, const float* g_loss,
+                          float* g_disp, float* g_partner, lsi_stream_t stream);
+
+/*
  * layers.compose, lsi/geometry/layers.py:29-70 with helpers.soft_z_buffering
  * (lsi/nnutils/helpers.py:140-160): white background layer at min_disp,
  * per-pixel softmax of log(mask + 1e-8) - depth / temp over the L + 1 layers,

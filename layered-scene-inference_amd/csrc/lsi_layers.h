@@ -47,20 +47,27 @@ __device__ __forceinline__ void tap_weights(const Taps& t, float (&c)[4]) {
   c[3] = t.vx1 * t.vy1 * t.wx1 * t.wy1;
 }
 
-// ... and channel ch of the sample of ib [Hs*Ws, C], summed in that order; 0 for
-// a non-finite point.  (The one gather of lsi_bilinear_fwd and
-// lsi_disocclusion_mask.)
+// ... and the sample, summed in that order; 0 for a non-finite point.  at(i) is
+// the image's value at the flat tap index i = x + y*Ws.  (The one gather of
+// lsi_bilinear_fwd, lsi_disocclusion_mask and lsi_geo_cons_loss_*.)
+template <class At>
+__device__ __forceinline__ float bilinear_gather_at(const Taps& t, const float (&c)[4],
+                                                    At at) {
+  float o = 0.0f;
+  if (t.ok) {
+    o = c[0] * at(t.i00);
+    o = o + c[1] * at(t.i01);
+    o = o + c[2] * at(t.i10);
+    o = o + c[3] * at(t.i11);
+  }
+  return o;
+}
+
+// Channel ch of the sample of ib [Hs*Ws, C].
 __device__ __forceinline__ float bilinear_gather(const Taps& t, const float (&c)[4],
                                                  const float* __restrict__ ib, int C,
                                                  int ch) {
-  float o = 0.0f;
-  if (t.ok) {
-    o = c[0] * ib[(size_t)t.i00 * C + ch];
-    o = o + c[1] * ib[(size_t)t.i01 * C + ch];
-    o = o + c[2] * ib[(size_t)t.i10 * C + ch];
-    o = o + c[3] * ib[(size_t)t.i11 * C + ch];
-  }
-  return o;
+  return bilinear_gather_at(t, c, [=](int i) { return ib[(size_t)i * C + ch]; });
 }
 
 // AREA resize for integer factors, one output cell: the box mean of the fy x fx

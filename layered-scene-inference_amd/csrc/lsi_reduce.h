@@ -8,9 +8,10 @@
 //   per-plane    a plane-aligned grid of bpp <= MAXBPP blocks per plane, three
 //                sums per plane (plane_store_partials), then ONE block
 //                (plane_finish_kernel) that writes the plane sums and the mean
-//                of the planes' terms: lsi_edge_smooth.hip, lsi_depth_sup.hip.
+//                of the planes' terms: lsi_edge_smooth.hip, lsi_depth_sup.hip,
+//                lsi_geo_cons.hip.
 //
-// rc_of_launch() is here for all six, sgn() for lsi_loss.hip and the two
+// rc_of_launch() is here for all seven, sgn() for lsi_loss.hip and the three
 // per-plane losses.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -163,6 +163,16 @@ def build_parser():
     help='ground truth nearer than this depth is not scored')
   a('--depth_sup_max', type=float, default=80.,
     help='ground truth beyond this depth is not scored')
+  a('--geo_cons_wt', type=float, default=0.0,
+    help='weight of the geometric-consistency term between the two views\' '
+    'layer-0 disparities (csrc/lsi_geo_cons.hip, DESIGN.md 4.21): geo_cons_wt * '
+    'geo_cons_loss is added to the total, divided by max_disp in l1 mode; 0 = no '
+    'such term, no extra launch')
+  a('--geo_cons_mode', default='ratio', choices=['ratio', 'l1'],
+    help='|dd - s| / (dd + s), scale-free, or a plain |dd - s|')
+  a('--geo_cons_occl', type=float, default=0.0,
+    help='a pixel whose projection lies behind the other view\'s surface, s - dd > '
+    'geo_cons_occl * (s + dd), is not scored; 0 = every pixel that lands is')
   a('--zbuf_scale', type=float, default=50)
   a('--trg_splat_downsampling', type=float, default=0.5)
   a('--disp_smoothness_wt', type=float, default=0.1)
@@ -592,6 +602,7 @@ class Trainer(train_utils.Trainer):
     # One sweep per direction renders the per-layer AND the composed view
     # (the reference makes four forward_splat calls whose per-layer splats
     # are identical pairwise).
+    mat2 = None
     if paired and (opts.indep_splat_wt > 0 or opts.compose_splat_wt > 0):
       # Both directions of the pair from ONE launch (and one in the backward):
       # the network's output is one buffer of 2 B LDIs -- the B source views'
@@ -691,6 +702,24 @@ class Trainer(train_utils.Trainer):
         depth_sup_loss = (depth_loss(ldi_src[2], half(gt2, 0), half(scale2, 0)) +
                           depth_loss(ldi_trg[2], half(gt2, 1), half(scale2, 1)))
 
+    # geometric consistency of the two views' layer 0 (no
+    # reference counterpart)
+    geo_wt = getattr(opts, 'geo_cons_wt', 0.0)
+    if geo_wt > 0:
+      geo_kw = dict(mode=opts.geo_cons_mode, occl_thresh=opts.geo_cons_occl)
+      if paired:
+        # one call on the 2 B views: plane b's partner is plane b +- B; the
+        # matrices are the paired splat's, built here when its weights are 0
+        if mat2 is None:
+          mat2 = torch.cat([mats['trg'], mats['src']], dim=0)
+        geo_cons_loss = 2.0 * loss.geometric_consistency_loss(pair[2][0], mat2, **geo_kw)
+      else:
+        geo_cons_loss = (
+            loss.geometric_consistency_loss(ldi_src[2][0], mats['trg'],
+                                            partner_disps=ldi_trg[2][0], **geo_kw) +
+            loss.geometric_consistency_loss(ldi_trg[2][0], mats['src'],
+                                            partner_disps=ldi_src[2][0], **geo_kw))
+
     total = zero
     if opts.self_cons_wt > 0:
       total = total + opts.self_cons_wt * self_cons_loss
@@ -713,6 +742,10 @@ class Trainer(train_utils.Trainer):
                        else edge_wt / opts.max_disp) * edge_smooth_loss
     if dsup_wt > 0:
       total = total + dsup_wt * depth_sup_loss
+    if geo_wt > 0:
+      # the ratio is scale-free; l1 is linear in d
+      total = total + (geo_wt / opts.max_disp if opts.geo_cons_mode == 'l1'
+                       else geo_wt) * geo_cons_loss
     scalars = {
         'self_cons_loss': self_cons_loss,
         'compose_splat_loss': compose_splat_loss,
@@ -728,6 +761,8 @@ class Trainer(train_utils.Trainer):
       scalars['edge_smooth_loss'] = edge_smooth_loss
     if dsup_wt > 0:
       scalars['depth_sup_loss'] = depth_sup_loss
+    if geo_wt > 0:
+      scalars['geo_cons_loss'] = geo_cons_loss
     return total, scalars
 
 

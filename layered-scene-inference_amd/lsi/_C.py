@@ -32,6 +32,7 @@ LSI_VIS_SKIP, LSI_VIS_RGB, LSI_VIS_GRAY, LSI_VIS_LUT, LSI_VIS_ABSDIFF = 0, 1, 2,
 LSI_VIS_MAX_ITEMS = 256
 LSI_LIDAR_INVERSE = 1
 LSI_DEPTH_SUP_SILOG, LSI_DEPTH_SUP_L1 = 0, 1
+LSI_GEO_CONS_RATIO, LSI_GEO_CONS_L1 = 0, 1
 LSI_LIDAR_TILE_H, LSI_LIDAR_TILE_W = 16, 64
 PATH_NAMES = {1: 'atomic', 2: 'rowband', 3: 'stream', 4: 'tile'}
 
@@ -94,6 +95,13 @@ class LsiDepthSupDesc(ctypes.Structure):
       [(n, ctypes.c_int64) for n in ('p_sp', 'p_sy', 'p_sx', 'g_sp', 'g_sy', 'g_sx')] +
       [(n, ctypes.c_float) for n in ('valid_above', 'g_min', 'g_max', 'eps', 'lam')] +
       [('reserved', ctypes.c_int32)])
+
+
+class LsiGeoConsDesc(ctypes.Structure):
+  _fields_ = (
+      [(n, ctypes.c_int32) for n in ('P', 'H', 'W', 'mode')] +
+      [(n, ctypes.c_int64) for n in ('d_sp', 'd_sy', 'd_sx', 'e_sp', 'e_sy', 'e_sx')] +
+      [('shift', ctypes.c_int32), ('occl_thresh', ctypes.c_float)])
 
 
 class LsiConvDesc(ctypes.Structure):
@@ -224,6 +232,11 @@ SIGNATURES = {
                                [_VP] * 6 + [_SZ, _VP]),
     'lsi_depth_sup_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiDepthSupDesc)] +
                                [_VP] * 7),
+    'lsi_geo_cons_workspace_bytes': (_SZ, [ctypes.POINTER(LsiGeoConsDesc)]),
+    'lsi_geo_cons_loss_fwd': (ctypes.c_int, [ctypes.POINTER(LsiGeoConsDesc)] +
+                              [_VP] * 7 + [_SZ, _VP]),
+    'lsi_geo_cons_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiGeoConsDesc)] +
+                              [_VP] * 8),
     'lsi_compose_fwd': (ctypes.c_int, [_I32, _I64, _I32] + [_VP] * 3 +
                         [_I32, _F32, _F32, _VP, _VP]),
     'lsi_compose_depth_fwd': (ctypes.c_int, [_I32, _I64] + [_VP] * 2 +

@@ -436,6 +436,118 @@ def depth_supervision_loss(pred, gt, gt_scale, mode, lam, valid_above, g_min, g_
   return (out, sums) if return_plane_sums else out
 
 
+# launches of the geometric-consistency kernels through this binding
+CALLS.update({'geo_cons_fwd': 0, 'geo_cons_bwd': 0})
+GEO_CONS_MODES = {'ratio': _C.LSI_GEO_CONS_RATIO, 'l1': _C.LSI_GEO_CONS_L1}
+
+
+def geo_cons_desc(disp, partner, mats, mode, occl_thresh, what):
+  """The LsiGeoConsDesc of disp P x H x W (any strides) against partner P x H x W
+  (any strides), or against its own other half when partner is None (P even,
+  shift P / 2), under mats P x 4 x 4; RuntimeError for a wrong shape or dtype,
+  ValueError for what the kernels would refuse with LSI_EINVAL."""
+  for name, t in (('disps', disp), ('partner_disps', partner), ('mats', mats)):
+    if t is not None and t.dtype != torch.float32:
+      raise RuntimeError('%s: %s is fp32 (got %s)' % (what, name, t.dtype))
+  if disp.dim() != 3:
+    raise RuntimeError('%s: disps are P x H x W (got %s)' % (what, tuple(disp.shape)))
+  p, h, w = disp.shape
+  if partner is not None and tuple(partner.shape) != (p, h, w):
+    raise RuntimeError('%s: disps and partner_disps are P x H x W, of one shape (got '
+                       '%s and %s)' % (what, (p, h, w), tuple(partner.shape)))
+  if tuple(mats.shape) != (p, 4, 4):
+    raise RuntimeError('%s: mats holds one 4 x 4 matrix per plane, %s (got %s)' %
+                       (what, (p, 4, 4), tuple(mats.shape)))
+  if mode not in GEO_CONS_MODES:
+    raise ValueError("%s: the mode is 'ratio' or 'l1' (got %r)" % (what, mode))
+  if min(p, h, w) < 1:
+    raise ValueError('%s: empty maps (%s)' % (what, (p, h, w)))
+  if partner is None and p % 2:
+    raise ValueError('%s: the paired form needs an even number of planes, the two '
+                     "views' halves (got %d)" % (what, p))
+  if p > 65535 or h * w >= 1 << 24 or p * h * w > 2 ** 31 - 1:
+    raise ValueError('%s: at most 65535 planes of fewer than 2^24 pixels, 2^31 - 1 '
+                     'pixels in all (got %s)' % (what, (p, h, w)))
+  occl_thresh = float(occl_thresh)
+  if not 0.0 <= occl_thresh < 1.0:
+    raise ValueError('%s: occl_thresh lies in [0, 1) (got %r)' % (what, occl_thresh))
+  d = _C.LsiGeoConsDesc()
+  d.P, d.H, d.W, d.mode = p, h, w, GEO_CONS_MODES[mode]
+  d.d_sp, d.d_sy, d.d_sx = disp.stride()
+  d.e_sp, d.e_sy, d.e_sx = (disp if partner is None else partner).stride()
+  d.shift, d.occl_thresh = (p // 2 if partner is None else 0), occl_thresh
+  return d
+
+
+class _GeoCons(torch.autograd.Function):
+  """lsi_geo_cons_loss_fwd / _bwd.  partner None: the paired
+  form, one gradient buffer."""
+
+  @staticmethod
+  def forward(ctx, disp, partner, mats, mode, occl_thresh, want_map):
+    d = geo_cons_desc(disp, partner, mats, mode, occl_thresh,
+                      'geometric_consistency_loss')
+    dev = _C.require_device(disp, partner, mats)
+    mats = mats.contiguous()
+    e = disp if partner is None else partner
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    sums = torch.empty((3 * d.P,), dtype=torch.float64, device=dev)
+    emap = (torch.empty((d.P, d.H, d.W), dtype=torch.float32, device=dev)
+            if want_map else None)
+    n = int(_C.lib().lsi_geo_cons_workspace_bytes(ctypes.byref(d)))
+    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+    CALLS['geo_cons_fwd'] += 1
+    rc = _C.lib().lsi_geo_cons_loss_fwd(ctypes.byref(d), _C.ptr(disp), _C.ptr(e),
+                                        _C.ptr(mats), _C.ptr(out), _C.ptr(sums),
+                                        _C.ptr(emap), _C.ptr(ws), n,
+                                        _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_geo_cons_loss_fwd')
+    ctx.save_for_backward(disp, mats, sums,
+                          partner if partner is not None else disp.new_empty(0))
+    ctx.paired = partner is None
+    ctx.desc = d
+    if emap is None:
+      emap = disp.new_empty(0)
+    ctx.mark_non_differentiable(sums, emap)
+    return out, sums, emap
+
+  @staticmethod
+  def backward(ctx, g, _s, _m):
+    disp, mats, sums, partner = ctx.saved_tensors
+    dev = disp.device
+    d = ctx.desc
+    g = g.contiguous().float()
+    shape = (d.P, d.H, d.W)
+    g_disp = torch.empty(shape, dtype=torch.float32, device=dev)
+    g_partner = (None if ctx.paired else
+                 torch.empty(shape, dtype=torch.float32, device=dev))
+    CALLS['geo_cons_bwd'] += 1
+    rc = _C.lib().lsi_geo_cons_loss_bwd(ctypes.byref(d), _C.ptr(disp),
+                                        _C.ptr(disp if ctx.paired else partner),
+                                        _C.ptr(mats), _C.ptr(sums), _C.ptr(g),
+                                        _C.ptr(g_disp), _C.ptr(g_partner),
+                                        _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_geo_cons_loss_bwd')
+    return g_disp, g_partner, None, None, None, None
+
+
+def geometric_consistency_loss(disp, partner, mats, mode, occl_thresh,
+                               return_map=False, return_plane_sums=False):
+  """Geometric consistency of disp P x H x W (any strides, never copied) with
+  partner P x H x W, or with its own other half (partner None), under mats
+  P x 4 x 4; the gradient is w.r.t. disp and partner.  return_map: also the
+  per-pixel term, -1 where unscored; return_plane_sums: also the 3 P doubles
+  (sum e, N_p, 0) the forward left for the backward."""
+  # the cameras are constants here
+  if torch.is_tensor(mats) and mats.requires_grad:
+    raise RuntimeError('geometric_consistency_loss: mats is not differentiable on '
+                       'the HIP path (pass mats.detach())')
+  out, sums, emap = _GeoCons.apply(disp, partner, mats, mode, occl_thresh,
+                                   bool(return_map))
+  res = (out,) + ((emap,) if return_map else ()) + ((sums,) if return_plane_sums else ())
+  return res if len(res) > 1 else out
+
+
 class _Compose(torch.autograd.Function):
   """lsi_compose_fwd / lsi_compose_bwd on imgs [L,N,C], masks [L,N], dmaps
   [L,N] (contiguous fp32)."""

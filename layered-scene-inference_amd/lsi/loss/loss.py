@@ -102,21 +102,21 @@ def edge_aware_smoothness_loss(pred_disp, guide_imgs, alpha=1.0, order=1,
   return _hip.edge_smoothness_loss(pred_disp, guide_imgs, alpha, order, normalise)
 
 
-def _planes(t, name):
+def _planes(t, name, what='depth_supervision_loss'):
   """[..., H, W, 1] or [..., H, W] as a P x H x W view (never a copy).  A last
   dimension of 1 is the channel from four dimensions on; three are P x H x W."""
   if t.dim() >= 4 and t.shape[-1] == 1:
     t = t[..., 0]
   if t.dim() < 2:
-    raise RuntimeError('depth_supervision_loss: %s is [..., H, W, 1] or [..., H, W] '
-                       '(got %s)' % (name, tuple(t.shape)))
+    raise RuntimeError('%s: %s is [..., H, W, 1] or [..., H, W] '
+                       '(got %s)' % (what, name, tuple(t.shape)))
   h, w = t.shape[-2:]
   try:
     return t.view(-1, h, w)
   except RuntimeError:
-    raise RuntimeError('depth_supervision_loss: the leading dimensions of %s (%s, '
+    raise RuntimeError('%s: the leading dimensions of %s (%s, '
                        'strides %s) do not flatten without a copy' %
-                       (name, tuple(t.shape), t.stride())) from None
+                       (what, name, tuple(t.shape), t.stride())) from None
 
 
 def depth_supervision_loss(pred_disp, gt, gt_scale=None, mode='silog', lam=0.5,
@@ -146,3 +146,32 @@ def depth_supervision_loss(pred_disp, gt, gt_scale=None, mode='silog', lam=0.5,
   g_min, g_max = float(one / np.float32(depth_max)), float(one / np.float32(depth_min))
   return _hip.depth_supervision_loss(pred, gt, gt_scale, mode, lam, valid_above,
                                      g_min, g_max, eps)
+
+
+def geometric_consistency_loss(disps, mats, partner_disps=None, mode='ratio',
+                               occl_thresh=0., return_map=False):
+  """Geometric consistency between two views' inverse depths (the
+  reference has none; Godard et al. 2017, Bian et al. 2019): the differentiable
+  counterpart of projection.disocclusion_mask.  disps is [..., H, W, 1] or
+  [..., H, W] (flattened to P planes as a view), mats P x 4 x 4 on the device:
+  mats[p] takes a pixel (x + .5, y + .5, 1, d) of plane p to its partner's frame.
+  partner_disps None is the paired form: P is even and the partner of plane p is
+  plane p +- P / 2 of disps itself (the trainer's buffer of 2 B views with
+  mats = [src -> trg; trg -> src]); else partner_disps has disps' shape and
+  plane p's partner is its plane p.  Each pixel's d is projected to (u, v, dd) in
+  fp32 as the renderer does and the partner is sampled bilinearly at (u, v): s.
+  The pixel is scored when everything is finite, the point lies in front of the
+  partner's camera (n > 0, dd > 0) and inside the hull of its pixel centres,
+  s > 0 and -- with occl_thresh > 0 -- it is not occluded: s - dd > occl_thresh
+  (s + dd).  mode 'ratio': e = |dd - s| / (dd + s), scale-free in [0, 1); 'l1':
+  e = |dd - s|.  Per plane the mean of e over its scored pixels; the loss is the
+  mean over the planes that hold one, 0 if none does.  One fused HIP launch each
+  way plus a one-block finish (lsi_geo_cons_loss_fwd / _bwd); the gradient is
+  w.r.t. disps and partner_disps, the scored set and mats are constants.
+  return_map: also the detached per-pixel e, P x H x W, -1 where unscored."""
+  from lsi.loss import _hip  # pylint: disable=g-import-not-at-top
+  what = 'geometric_consistency_loss'
+  d = _planes(disps, 'disps', what)
+  e = None if partner_disps is None else _planes(partner_disps, 'partner_disps', what)
+  return _hip.geometric_consistency_loss(d, e, mats, mode, occl_thresh,
+                                         return_map=return_map)

@@ -1773,6 +1773,58 @@ int lsi_lidar_rasterize(int32_t B, int32_t V, int32_t H, int32_t W,
                         float occl_ratio, uint32_t flags, float* out,
                         void* workspace, size_t workspace_bytes, lsi_stream_t stream);
 
+/*
+ * Push-pull (pyramid) hole filling of a rendered image (csrc/lsi_fill.hip;
+ * DESIGN.md 4.22).  Forward only.
+ *   img          [N, H, W, C] float, device, contiguous, C in 1 .. 4
+ *   w            [N, H, W] float, device: what `mode` says
+ *   out          [N, H, W, C] float, device, written fully; may not alias img
+ *   level 0      LSI_FILL_CONF:  c = (w > 0) ? min(w, 1) : 0 (NaN -> 0),
+ *                                p = img c.
+ *                LSI_FILL_SPLAT: img, w are forward_splat's normalised image
+ *                and weights over a canvas of value bg_value and weight bg_wt:
+ *                c = (w > bg_wt) ? (w - bg_wt) / w : 0, the share of the pixel
+ *                that came from the layers; p = img - (1 - c) bg_value.
+ *                Both: c < conf_min makes c = 0, and where c == 0, p is
+ *                selected to be 0 (a NaN or Inf of a hole pixel does not leak).
+ *   push         level l + 1 has ceil(H_l / 2) x ceil(W_l / 2) pixels, until
+ *                1 x 1 (level Lmax).  For c and each channel of p:
+ *                S = (v[2y, 2x] + v[2y, 2x+1]) + (v[2y+1, 2x] + v[2y+1, 2x+1]),
+ *                children out of range count as 0; S_c > 1: p' = S_p / S_c,
+ *                c' = 1; else p' = S_p, c' = S_c.
+ *   pull         coarsest level: F = (c > 0) ? p / c : bg_value.  Below it
+ *                F_l = p_l + (1 - c_l) U with U the 2 x bilinear up-sample of
+ *                F_{l+1} with clamped borders: cy = y >> 1,
+ *                ny = clamp(cy + ((y & 1) ? 1 : -1), 0, H_{l+1} - 1), the same
+ *                in x, U = ((9 F[cy,cx] + 3 F[cy,nx]) + (3 F[ny,cx] + F[ny,nx]))
+ *                * 0.0625.  out = F_0.
+ * All fp32, in this order, never contracted, divisions correctly rounded: the
+ * result is a function of the inputs alone, bit for bit.
+ * LSI_EINVAL for N outside [1, 65535], H or W < 1, C outside [1, 4],
+ * N H W > 2^28, a shape whose levels from 5 up hold more than
+ * LSI_FILL_MID_MAX_PIXELS pixels together (they are kept in the LDS of one
+ * workgroup; 1024 x 1024 holds 1365), an unknown mode, a non-finite bg_value,
+ * a conf_min that is negative or not finite, with LSI_FILL_SPLAT a bg_wt that
+ * is negative or not finite; then LSI_ENULL; then LSI_EWORKSPACE -- all before
+ * any launch.  Workspace: the pushed levels 1 .. 5 and F of the topmost of
+ * them.  3 launches on `stream` (1 for a 1 x 1 image) whatever the data: a
+ * workgroup per LSI_FILL_TILE x LSI_FILL_TILE tile pushes 5 levels in LDS, a
+ * workgroup per image pushes the rest to 1 x 1 and pulls back, a workgroup per
+ * tile pulls with a halo of one pixel per level.  No atomics, no host
+ * synchronisation, no allocation, no state.
+ */
+#define LSI_FILL_CONF 0  /* w is a confidence                                */
+#define LSI_FILL_SPLAT 1 /* w is forward_splat's weight sum over a canvas    */
+#define LSI_FILL_TILE 32
+#define LSI_FILL_MID_MAX_PIXELS 2560
+/* Bytes of device scratch lsi_fill_holes needs; 0 for a shape the call
+ * refuses. */
+size_t lsi_fill_holes_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C);
+int lsi_fill_holes(int32_t N, int32_t H, int32_t W, int32_t C, const float* img,
+                   const float* w, int32_t mode, float bg_wt, float bg_value,
+                   float conf_min, float* out, void* workspace, size_t workspace_bytes,
+                   lsi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

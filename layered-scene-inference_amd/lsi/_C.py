@@ -34,6 +34,8 @@ LSI_LIDAR_INVERSE = 1
 LSI_DEPTH_SUP_SILOG, LSI_DEPTH_SUP_L1 = 0, 1
 LSI_GEO_CONS_RATIO, LSI_GEO_CONS_L1 = 0, 1
 LSI_LIDAR_TILE_H, LSI_LIDAR_TILE_W = 16, 64
+LSI_FILL_CONF, LSI_FILL_SPLAT = 0, 1
+LSI_FILL_TILE, LSI_FILL_MID_MAX_PIXELS = 32, 2560
 PATH_NAMES = {1: 'atomic', 2: 'rowband', 3: 'stream', 4: 'tile'}
 
 _c_f = ctypes.POINTER(ctypes.c_float)
@@ -323,6 +325,9 @@ SIGNATURES = {
                                                                   _I32, _I32, _F32,
                                                                   ctypes.c_uint32] +
                             [_VP, _VP, _SZ, _VP]),
+    'lsi_fill_holes_workspace_bytes': (_SZ, [_I32] * 4),
+    'lsi_fill_holes': (ctypes.c_int, [_I32] * 4 + [_VP, _VP, _I32, _F32, _F32, _F32,
+                                                   _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

@@ -6,8 +6,22 @@
  * is the Python function surface of lsi.geometry.* / lsi.nnutils.helpers
  * (SURVEY.md section 8b).  Each entry point below names the reference
  * function(s) (paths relative to /root/reference) whose arithmetic it replaces;
- * the Python mirror in layered-scene-inference_amd/lsi/ binds them with ctypes
+ * the Python package in layered-scene-inference_amd/lsi/ binds them with ctypes
  * (binding shown in INTEGRATION.md).
+ *
+ * This file is the binding's only source: lsi/_C.py parses it at import and
+ * derives every LSI_* constant, struct layout and argument list from it, and
+ * refuses a declaration it cannot map.  Keep to the style below --
+ *   #define LSI_NAME <integer>[u]
+ *   typedef struct Name { <fixed-width scalars, T x[N], pointers> } Name;
+ *   one prototype per entry point, parameters of these kinds:
+ *     const Struct* d     ONE record, read on the host: the binding types it
+ *                         (ctypes.POINTER(Struct)) and refuses another class
+ *     const Struct d[]    an ARRAY of records, given by its address (a NumPy
+ *                         array's, a device copy's): c_void_p
+ *     any other T* p      a data pointer, given by its address: c_void_p
+ *     lsi_stream_t        c_void_p
+ * -- and tests/test_abi.py holds the derived layouts to the compiler's.
  *
  * Conventions
  *   - plain C: POD structs, raw device pointers, sizes; no C++/torch types.
@@ -1212,7 +1226,7 @@ typedef struct LsiPackJob {
 } LsiPackJob;
 int lsi_conv2d_pack_job(const LsiConvDesc* d, int32_t mode, const float* weight, void* packed,
                         size_t packed_bytes, LsiPackJob* job, int32_t* nblocks);
-int lsi_conv2d_pack_many(const LsiPackJob* jobs_device, int32_t njobs, int32_t total_blocks,
+int lsi_conv2d_pack_many(const LsiPackJob jobs_device[], int32_t njobs, int32_t total_blocks,
                          lsi_stream_t stream);
 int lsi_conv2d_fwd(const LsiConvDesc* d, const void* x, const void* packed, void* out,
                    lsi_stream_t stream);
@@ -1384,7 +1398,7 @@ int lsi_conv2d_f32_pack(const LsiConvDesc* d, int32_t mode, const float* weight,
 int lsi_conv2d_f32_pack_job(const LsiConvDesc* d, int32_t mode, const float* weight,
                             void* packed, size_t packed_bytes, LsiPackJob* job,
                             int32_t* nblocks);
-int lsi_conv2d_f32_pack_many(const LsiPackJob* jobs_device, int32_t njobs, int32_t total_blocks,
+int lsi_conv2d_f32_pack_many(const LsiPackJob jobs_device[], int32_t njobs, int32_t total_blocks,
                              lsi_stream_t stream);
 size_t lsi_conv2d_f32_workspace_bytes(const LsiConvDesc* d, int32_t mode);
 int lsi_conv2d_f32_run(const LsiConvDesc* d, int32_t mode, const LsiConvIO* io,
@@ -1489,8 +1503,8 @@ typedef struct LsiImageDesc {
   int32_t H, W, C;        /* the image's own size; C == Co                   */
   int32_t reserved;       /* 0                                               */
 } LsiImageDesc;
-int lsi_area_resize_u8(int32_t n, const LsiImageDesc* desc_host,
-                       const LsiImageDesc* desc_dev, const uint8_t* packed,
+int lsi_area_resize_u8(int32_t n, const LsiImageDesc desc_host[],
+                       const LsiImageDesc desc_dev[], const uint8_t* packed,
                        size_t packed_bytes, int32_t Ho, int32_t Wo, int32_t Co,
                        float* out, lsi_stream_t stream);
 
@@ -1526,8 +1540,8 @@ typedef struct LsiAugmentDesc {
   float gain[3];          /* per channel, finite and >= 0; gain[0] for C = 1 */
   int32_t reserved2;      /* 0                                               */
 } LsiAugmentDesc;          /* 64 bytes                                        */
-int lsi_augment_resize_u8(int32_t n, const LsiAugmentDesc* desc_host,
-                          const LsiAugmentDesc* desc_dev, const uint8_t* packed,
+int lsi_augment_resize_u8(int32_t n, const LsiAugmentDesc desc_host[],
+                          const LsiAugmentDesc desc_dev[], const uint8_t* packed,
                           size_t packed_bytes, int64_t tables_offset,
                           int32_t n_tables, int32_t Ho, int32_t Wo, int32_t Co,
                           float* out, lsi_stream_t stream);
@@ -1558,8 +1572,8 @@ int lsi_augment_resize_u8(int32_t n, const LsiAugmentDesc* desc_host,
  * >= 2^31, or a misaligned pointer -- all before any launch.  No workspace, no
  * allocation, no synchronisation, no state.
  */
-int lsi_augment_sample_u16(int32_t n, const LsiAugmentDesc* desc_host,
-                           const LsiAugmentDesc* desc_dev, const uint8_t* packed,
+int lsi_augment_sample_u16(int32_t n, const LsiAugmentDesc desc_host[],
+                           const LsiAugmentDesc desc_dev[], const uint8_t* packed,
                            size_t packed_bytes, int32_t Ho, int32_t Wo,
                            float* out, lsi_stream_t stream);
 
@@ -1624,8 +1638,8 @@ typedef struct LsiVisItem {
   float lo, inv;
 } LsiVisItem;
 int lsi_visual_sheet_size(const LsiVisSheet* sheet, int64_t* height, int64_t* width);
-int lsi_visual_pack_u8(const LsiVisSheet* sheet, const LsiVisItem* items_host,
-                       const LsiVisItem* items_dev, const uint8_t* lut_dev,
+int lsi_visual_pack_u8(const LsiVisSheet* sheet, const LsiVisItem items_host[],
+                       const LsiVisItem items_dev[], const uint8_t* lut_dev,
                        uint8_t* out, int64_t out_row_bytes, lsi_stream_t stream);
 
 /*
@@ -1767,7 +1781,7 @@ typedef struct LsiScanDesc { /* one scan of a batch */
 size_t lsi_lidar_workspace_bytes(int32_t B, int32_t V, int32_t H, int32_t W,
                                  int32_t win_y, int32_t win_x);
 int lsi_lidar_rasterize(int32_t B, int32_t V, int32_t H, int32_t W,
-                        const LsiScanDesc* desc_host, const LsiScanDesc* desc_dev,
+                        const LsiScanDesc desc_host[], const LsiScanDesc desc_dev[],
                         const float* pts, int64_t n_pts_total, const float* mats,
                         float z_min, float z_max, int32_t win_y, int32_t win_x,
                         float occl_ratio, uint32_t flags, float* out,

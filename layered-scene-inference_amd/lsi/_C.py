@@ -1,11 +1,15 @@
-"""ctypes binding of liblsi_hip.so (C ABI: include/lsi_hip.h).
+"""ctypes binding of liblsi_hip.so, derived at import from its C ABI,
+include/lsi_hip.h: every LSI_* constant, one ctypes.Structure per struct and
+SIGNATURES, the argument types of every prototype (the header's opening comment
+has the mapping).  Nothing is declared here a second time.
 
-There is NO fallback: if the shared library is missing, or an op is handed a
-tensor that does not live on a ROCm device, this module raises.  PyTorch is used
-only for device memory, streams and autograd bookkeeping.
+There is NO fallback: if the header or the shared library is missing, or an op
+is handed a tensor that does not live on a ROCm device, this module raises.
+PyTorch is used only for device memory, streams and autograd bookkeeping.
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -15,320 +19,110 @@ _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (any other value picks liblsi_hip_<value>.so: experiment builds)
 SO_PATH = os.path.join(_PKG, 'liblsi_hip_%s.so' % os.environ['LSI_HIP_LIB'] if
                        os.environ.get('LSI_HIP_LIB') else 'liblsi_hip.so')
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), 'include', 'lsi_hip.h')
 
-LSI_OK = 0
-LSI_COMPOSE, LSI_WANT_DISP, LSI_HAS_MASK, LSI_WS_KEEP = 1, 2, 4, 8
-LSI_DETERMINISTIC = 16
-LSI_PACKED_RGBD = 32
-LSI_GRAD_M = 64
-LSI_PATH_AUTO, LSI_PATH_ATOMIC, LSI_PATH_ROWBAND, LSI_PATH_STREAM = 0, 1, 2, 3
-LSI_PATH_TILE = 4
-LSI_SCENE_IMG, LSI_SCENE_DISP, LSI_SCENE_IMG_ROOM, LSI_SCENE_DISP_ROOM = 1, 2, 4, 8
-LSI_SCENE_MAX_PLANES = 16
-LSI_FC_BN, LSI_FC_X_F32, LSI_FC_OUT_F32 = 1, 2, 4
-LSI_IMAGE_MAX_PIXELS = 16843009
-LSI_AUG_FLIP = 1
-LSI_VIS_SKIP, LSI_VIS_RGB, LSI_VIS_GRAY, LSI_VIS_LUT, LSI_VIS_ABSDIFF = 0, 1, 2, 3, 4
-LSI_VIS_MAX_ITEMS = 256
-LSI_LIDAR_INVERSE = 1
-LSI_DEPTH_SUP_SILOG, LSI_DEPTH_SUP_L1 = 0, 1
-LSI_GEO_CONS_RATIO, LSI_GEO_CONS_L1 = 0, 1
-LSI_LIDAR_TILE_H, LSI_LIDAR_TILE_W = 16, 64
-LSI_FILL_CONF, LSI_FILL_SPLAT = 0, 1
-LSI_FILL_TILE, LSI_FILL_MID_MAX_PIXELS = 32, 2560
-PATH_NAMES = {1: 'atomic', 2: 'rowband', 3: 'stream', 4: 'tile'}
-
-_c_f = ctypes.POINTER(ctypes.c_float)
-_c_i = ctypes.POINTER(ctypes.c_int32)
-
-
-class LsiStreamAdapt(ctypes.Structure):
-  _fields_ = [('state', ctypes.c_int32), ('pending', ctypes.c_int32),
-              ('seq', ctypes.c_uint32), ('calls', ctypes.c_uint32),
-              ('ctr_dev', ctypes.c_void_p), ('ctr_host', ctypes.c_void_p)]
-
-
-class LsiSplatDesc(ctypes.Structure):
-  _fields_ = (
-      [(n, ctypes.c_int32) for n in ('L', 'B', 'H', 'W', 'Ht', 'Wt')] +
-      [(n, ctypes.c_int64) for n in (
-          'tex_sl', 'tex_sb', 'tex_sy', 'tex_sx', 'tex_sc',
-          'disp_sl', 'disp_sb', 'disp_sy', 'disp_sx',
-          'mask_sl', 'mask_sb', 'mask_sy', 'mask_sx')] +
-      [(n, ctypes.c_float) for n in (
-          'trg_downsampling', 'max_disp', 'zbuf_scale', 'bg_wt')] +
-      [('flags', ctypes.c_uint32), ('path', ctypes.c_int32),
-       ('tune_rows', ctypes.c_int32), ('tune_threads', ctypes.c_int32),
-       ('tune_window', ctypes.c_int32), ('reserved', ctypes.c_int32),
-       ('adapt', ctypes.c_void_p)])
-
-
-class LsiLossDesc(ctypes.Structure):
-  _fields_ = (
-      [(n, ctypes.c_int32) for n in ('L', 'B', 'H', 'W')] +
-      [(n, ctypes.c_int64) for n in (
-          'img_sl', 'img_sb', 'img_sy', 'img_sx', 'img_sc',
-          'mask_sl', 'mask_sb', 'mask_sy', 'mask_sx',
-          'disp_sl', 'disp_sb', 'disp_sy', 'disp_sx',
-          'trg_sb', 'trg_sy', 'trg_sx', 'trg_sc')] +
-      [(n, ctypes.c_float) for n in ('bg_layer_disp', 'max_disp', 'zbuf_scale')] +
-      [('reserved', ctypes.c_int32)])
-
-
-class LsiSsimDesc(ctypes.Structure):
-  _fields_ = (
-      [(n, ctypes.c_int32) for n in ('nl', 'B', 'Ht', 'Wt', 'H', 'W', 'x_min',
-                                     'y_min', 'win')] +
-      [(n, ctypes.c_float) for n in ('sigma', 'c1', 'c2')] +
-      [(n, ctypes.c_int64) for n in ('t_sb', 't_sy', 't_sx', 't_sc')])
-
-
-class LsiEdgeSmoothDesc(ctypes.Structure):
-  _fields_ = (
-      [(n, ctypes.c_int32) for n in ('L', 'B', 'H', 'W', 'order', 'normalise')] +
-      [(n, ctypes.c_int64) for n in ('d_sl', 'd_sb', 'd_sy', 'd_sx',
-                                     'g_sl', 'g_sb', 'g_sy', 'g_sx', 'g_sc')] +
-      [(n, ctypes.c_float) for n in ('alpha', 'eps')])
-
-
-class LsiDepthSupDesc(ctypes.Structure):
-  _fields_ = (
-      [(n, ctypes.c_int32) for n in ('P', 'H', 'W', 'mode')] +
-      [(n, ctypes.c_int64) for n in ('p_sp', 'p_sy', 'p_sx', 'g_sp', 'g_sy', 'g_sx')] +
-      [(n, ctypes.c_float) for n in ('valid_above', 'g_min', 'g_max', 'eps', 'lam')] +
-      [('reserved', ctypes.c_int32)])
-
-
-class LsiGeoConsDesc(ctypes.Structure):
-  _fields_ = (
-      [(n, ctypes.c_int32) for n in ('P', 'H', 'W', 'mode')] +
-      [(n, ctypes.c_int64) for n in ('d_sp', 'd_sy', 'd_sx', 'e_sp', 'e_sy', 'e_sx')] +
-      [('shift', ctypes.c_int32), ('occl_thresh', ctypes.c_float)])
-
-
-class LsiConvDesc(ctypes.Structure):
-  _fields_ = [(n, ctypes.c_int32) for n in (
-      'N', 'H', 'W', 'Cin', 'OH', 'OW', 'Cout', 'KH', 'KW', 'stride', 'pad_t', 'pad_l')]
-
-
-class LsiSceneDesc(ctypes.Structure):
-  _fields_ = ([(n, ctypes.c_int32) for n in ('B', 'V', 'P', 'Hs', 'Ws', 'H', 'W',
-                                             'n_box', 'soft')] +
-              [('min_disp', ctypes.c_float), ('temp', ctypes.c_float),
-               ('outputs', ctypes.c_uint32)])
-
-
-class LsiFcDesc(ctypes.Structure):
-  _fields_ = ([(n, ctypes.c_int32) for n in ('M', 'K', 'N', 'groups', 'taps')] +
-              [('flags', ctypes.c_uint32), ('w_sn', ctypes.c_int64),
-               ('w_sk', ctypes.c_int64), ('tap_off', ctypes.c_int64 * 4),
-               ('eps', ctypes.c_float), ('reserved', ctypes.c_int32)])
-
-
-class LsiPackJob(ctypes.Structure):
-  _fields_ = ([('w', ctypes.c_void_p), ('dst', ctypes.c_void_p)] +
-              [(n, ctypes.c_int32) for n in ('D0', 'D1', 'khw', 'tr', 'ntaps', 'block0')] +
-              [('tap', ctypes.c_int8 * 56)])
-
-
-class LsiConvIO(ctypes.Structure):
-  _fields_ = ([(n, ctypes.c_void_p) for n in ('x', 'x2', 'packed', 'out', 'out2',
-                                              'bn_workspace', 'workspace')] +
-              [('workspace_bytes', ctypes.c_size_t), ('c1', ctypes.c_int32),
-               ('groups', ctypes.c_int32)])
-
-
-class LsiImageDesc(ctypes.Structure):
-  _fields_ = ([('offset', ctypes.c_int64)] +
-              [(n, ctypes.c_int32) for n in ('H', 'W', 'C', 'reserved')])
-
-
-class LsiAugmentDesc(ctypes.Structure):
-  _fields_ = ([('offset', ctypes.c_int64)] +
-              [(n, ctypes.c_int32) for n in ('H', 'W', 'C')] +
-              [('flags', ctypes.c_uint32)] +
-              [(n, ctypes.c_int32) for n in ('y0', 'x0', 'ch', 'cw', 'table',
-                                             'reserved')] +
-              [('gain', ctypes.c_float * 3), ('reserved2', ctypes.c_int32)])
-
-
-class LsiVisSheet(ctypes.Structure):
-  _fields_ = ([(n, ctypes.c_int32) for n in ('rows', 'cols', 'cell_h', 'cell_w',
-                                             'gutter', 'n_items')] +
-              [('bg', ctypes.c_uint8 * 3), ('nan', ctypes.c_uint8 * 3),
-               ('reserved', ctypes.c_uint8 * 2)])
-
-
-class LsiScanDesc(ctypes.Structure):
-  _fields_ = [('first', ctypes.c_int64), ('n', ctypes.c_int32),
-              ('reserved', ctypes.c_int32)]
-
-
-class LsiVisItem(ctypes.Structure):
-  _fields_ = ([('src', ctypes.c_void_p), ('ref', ctypes.c_void_p)] +
-              [(n, ctypes.c_int64) for n in ('s_y', 's_x', 's_c', 'r_y', 'r_x', 'r_c')] +
-              [(n, ctypes.c_int32) for n in ('kind', 'H', 'W', 'C', 'zoom', 'reserved')] +
-              [('lo', ctypes.c_float), ('inv', ctypes.c_float)])
-
-
-# name -> (restype, argtypes); every symbol include/lsi_hip.h declares.
-_I32, _I64, _VP, _SZ = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
-_DP = ctypes.POINTER(LsiSplatDesc)
-_LP = ctypes.POINTER(LsiLossDesc)
-_CP = ctypes.POINTER(LsiConvDesc)
-_F32 = ctypes.c_float
-SIGNATURES = {
-    'lsi_version': (ctypes.c_int, []),
-    'lsi_strerror': (ctypes.c_char_p, [ctypes.c_int]),
-    'lsi_bg_weight': (ctypes.c_float, [ctypes.c_double] * 3),
-    'lsi_rowband_ok': (ctypes.c_int, [_DP, _VP]),
-    'lsi_stream_ok': (ctypes.c_int, [_DP, _VP]),
-    'lsi_splat_workspace_bytes': (_SZ, [_DP]),
-    'lsi_stream_adapt_state': (ctypes.c_int, [ctypes.POINTER(LsiStreamAdapt)]),
-    'lsi_splat_fwd': (ctypes.c_int, [_DP] + [_VP] * 8 + [_SZ, _VP]),
-    'lsi_splat_bwd_workspace_bytes': (_SZ, [_DP]),
-    'lsi_splat_bwd': (ctypes.c_int, [_DP] + [_VP] * 12 + [_SZ, _VP]),
-    'lsi_splat_bwd_m': (ctypes.c_int, [_DP] + [_VP] * 13 + [_SZ, _VP]),
-    'lsi_splat_bwd_disp_workspace_bytes': (_SZ, [_DP]),
-    'lsi_splat_bwd_disp': (ctypes.c_int, [_DP] + [_VP] * 15 + [_SZ, _VP]),
-    'lsi_splat_fwd_both': (ctypes.c_int, [_DP] + [_VP] * 9 + [_SZ, _VP]),
-    'lsi_splat_bwd_both': (ctypes.c_int, [_DP] + [_VP] * 16 + [_SZ, _VP]),
-    'lsi_splat_bwd_both_m': (ctypes.c_int, [_DP] + [_VP] * 17 + [_SZ, _VP]),
-    'lsi_project_indices': (ctypes.c_int, [_DP] + [_VP] * 6),
-    'lsi_splat_generic': (ctypes.c_int, [_I32] * 6 + [_VP] * 4),
-    'lsi_splat_generic_bwd': (ctypes.c_int, [_I32] * 6 + [_VP] * 6),
-    'lsi_scatter_add': (ctypes.c_int, [_I32, _I64, _I64] + [_VP] * 4),
-    'lsi_bilinear_fwd': (ctypes.c_int, [_I32] * 6 + [_VP] * 4),
-    'lsi_conv3x3_pred_bwd_workspace_bytes': (_SZ, [_I32] * 3),
-    'lsi_conv3x3_wgrad_workspace_bytes': (_SZ, [_I32] * 5),
-    'lsi_conv3x3_wgrad': (ctypes.c_int, [_I32] * 5 + [_VP] * 4 + [_SZ, _VP]),
-    'lsi_conv3x3_pred_bwd': (ctypes.c_int, [_I32] * 4 + [_VP] * 7 + [_SZ, _VP]),
-    'lsi_conv3x3_c32_fwd': (ctypes.c_int, [_I32] * 5 + [_VP] * 3 + [_F32, _VP, _VP]),
-    'lsi_projection_matrices': (ctypes.c_int, [_I32] + [_VP] * 4 + [_I32, _VP]),
-    'lsi_bilinear_taps': (ctypes.c_int, [_I32] * 6 + [_VP] * 5),
-    'lsi_bilinear_bwd': (ctypes.c_int, [_I32] * 6 + [_VP] * 6),
-    'lsi_bilinear_taps_bwd': (ctypes.c_int, [_I32] * 6 + [_VP] * 5 + [_VP]),
-    'lsi_loss_workspace_bytes': (_SZ, []),
-    'lsi_zbuf_comp_loss_fwd': (ctypes.c_int, [_LP] + [_VP] * 6 + [_SZ, _VP]),
-    'lsi_zbuf_comp_loss_bwd': (ctypes.c_int, [_LP] + [_VP] * 9),
-    'lsi_disp_reg_loss_fwd': (ctypes.c_int, [_I32] * 4 + [_I64] * 4 + [_VP] * 3 +
-                              [_SZ, _VP]),
-    'lsi_disp_reg_loss_bwd': (ctypes.c_int, [_I32] * 4 + [_I64] * 4 + [_VP] * 4),
-    'lsi_view_synth_loss_fwd': (ctypes.c_int, [_I32] * 8 + [_VP] * 2 + [_I64] * 4 +
-                                [_VP] * 2 + [_SZ, _VP]),
-    'lsi_view_synth_loss_bwd': (ctypes.c_int, [_I32] * 8 + [_VP] * 2 + [_I64] * 4 +
-                                [_VP] * 3),
-    'lsi_ssim_window': (ctypes.c_int, [_I32, _F32, _VP]),
-    'lsi_ssim_loss_fwd': (ctypes.c_int, [ctypes.POINTER(LsiSsimDesc)] + [_VP] * 4 +
-                          [_SZ, _VP]),
-    'lsi_ssim_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiSsimDesc)] + [_VP] * 5),
-    'lsi_eval_ssim': (ctypes.c_int, [ctypes.POINTER(LsiSsimDesc)] + [_VP] * 4 +
-                      [_SZ, _VP]),
-    'lsi_edge_smooth_workspace_bytes': (_SZ, [ctypes.POINTER(LsiEdgeSmoothDesc)]),
-    'lsi_edge_smooth_loss_fwd': (ctypes.c_int, [ctypes.POINTER(LsiEdgeSmoothDesc)] +
-                                 [_VP] * 5 + [_SZ, _VP]),
-    'lsi_edge_smooth_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiEdgeSmoothDesc)] +
-                                 [_VP] * 6),
-    'lsi_depth_sup_workspace_bytes': (_SZ, [ctypes.POINTER(LsiDepthSupDesc)]),
-    'lsi_depth_sup_loss_fwd': (ctypes.c_int, [ctypes.POINTER(LsiDepthSupDesc)] +
-                               [_VP] * 6 + [_SZ, _VP]),
-    'lsi_depth_sup_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiDepthSupDesc)] +
-                               [_VP] * 7),
-    'lsi_geo_cons_workspace_bytes': (_SZ, [ctypes.POINTER(LsiGeoConsDesc)]),
-    'lsi_geo_cons_loss_fwd': (ctypes.c_int, [ctypes.POINTER(LsiGeoConsDesc)] +
-                              [_VP] * 7 + [_SZ, _VP]),
-    'lsi_geo_cons_loss_bwd': (ctypes.c_int, [ctypes.POINTER(LsiGeoConsDesc)] +
-                              [_VP] * 8),
-    'lsi_compose_fwd': (ctypes.c_int, [_I32, _I64, _I32] + [_VP] * 3 +
-                        [_I32, _F32, _F32, _VP, _VP]),
-    'lsi_compose_depth_fwd': (ctypes.c_int, [_I32, _I64] + [_VP] * 2 +
-                              [_I32, _F32, _F32, _F32, _VP, _VP]),
-    'lsi_compose_bwd': (ctypes.c_int, [_I32, _I64, _I32] + [_VP] * 3 +
-                        [_I32, _F32, _F32] + [_VP] * 5),
-    'lsi_compose_depth_bwd': (ctypes.c_int, [_I32, _I64] + [_VP] * 2 +
-                              [_I32, _F32, _F32, _F32] + [_VP] * 3),
-    'lsi_eval_workspace_bytes': (_SZ, []),
-    'lsi_eval_view_metrics': (ctypes.c_int, [_I32] * 8 + [_VP] * 3 + [_I64] * 4 +
-                              [_VP] * 3 + [ctypes.c_uint32, _F32] + [_VP] * 2 +
-                              [_SZ, _VP]),
-    'lsi_eval_layer_metrics': (ctypes.c_int, ([_LP] + [_VP] * 6) * 2 + [_VP] * 2 +
-                               [_SZ, _VP]),
-    'lsi_eval_depth_workspace_bytes': (_SZ, [_I32] * 4),
-    'lsi_eval_depth_metrics': (ctypes.c_int, [_I32] * 3 + [_VP] * 4 + [_I32] * 4 +
-                               [_F32] * 3 + [ctypes.c_uint32] + [_VP] * 3 + [_SZ, _VP]),
-    'lsi_disocclusion_mask': (ctypes.c_int, [_I32] * 5 + [_VP] * 3 + [_F32, _VP, _VP]),
-    'lsi_render_planes': (ctypes.c_int, [ctypes.POINTER(LsiSceneDesc)] + [_VP] * 8),
-    'lsi_render_planes_bwd_workspace_bytes': (_SZ, [ctypes.POINTER(LsiSceneDesc)]),
-    'lsi_render_planes_bwd': (ctypes.c_int, [ctypes.POINTER(LsiSceneDesc)] +
-                              [_VP] * 9 + [_SZ, _VP]),
-    'lsi_conv2d_supported': (ctypes.c_int, [_CP]),
-    'lsi_conv2d_packed_bytes': (_SZ, [_CP]),
-    'lsi_conv2d_pack': (ctypes.c_int, [_CP, _I32, _VP, _VP, _SZ, _VP]),
-    'lsi_conv2d_pack_job': (ctypes.c_int, [_CP, _I32, _VP, _VP, _SZ,
-                                           ctypes.POINTER(LsiPackJob), _c_i]),
-    'lsi_conv2d_pack_many': (ctypes.c_int, [_VP, _I32, _I32, _VP]),
-    'lsi_conv2d_fwd': (ctypes.c_int, [_CP] + [_VP] * 4),
-    'lsi_conv2d_bwd_data': (ctypes.c_int, [_CP] + [_VP] * 4),
-    'lsi_conv2d_fwd_bnstats': (ctypes.c_int, [_CP] + [_VP] * 4 + [_I32, _VP]),
-    'lsi_conv2d_bwd_data_bnstats': (ctypes.c_int, [_CP] + [_VP] * 4 + [_I32, _VP]),
-    'lsi_conv2d_fwd_cat': (ctypes.c_int, [_CP, _VP, _VP, _I32, _VP, _VP, _VP, _I32, _VP]),
-    'lsi_conv2d_bwd_data_cat': (ctypes.c_int, [_CP, _VP, _VP, _VP, _VP, _I32, _VP]),
-    'lsi_conv2d_wgrad_cat': (ctypes.c_int, [_CP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _SZ, _VP]),
-    'lsi_conv2d_workspace_bytes': (_SZ, [_CP, _I32]),
-    'lsi_conv2d_run': (ctypes.c_int, [_CP, _I32, ctypes.POINTER(LsiConvIO), _VP]),
-    'lsi_conv2d_wgrad_workspace_bytes': (_SZ, [_CP]),
-    'lsi_conv2d_wgrad': (ctypes.c_int, [_CP] + [_VP] * 4 + [_SZ, _VP]),
-    'lsi_conv2d_first_supported': (ctypes.c_int, [_CP]),
-    'lsi_conv2d_first_fwd': (ctypes.c_int, [_CP, _VP, _I32, _VP, _I32, _VP, _VP, _I32, _VP]),
-    'lsi_conv2d_first_wgrad_workspace_bytes': (_SZ, [_CP]),
-    'lsi_conv2d_first_wgrad': (ctypes.c_int, [_CP, _VP, _I32, _VP, _VP, _I32, _VP, _SZ, _VP]),
-    'lsi_conv2d_f32_supported': (ctypes.c_int, [_CP]),
-    'lsi_conv2d_f32_packed_bytes': (_SZ, [_CP]),
-    'lsi_conv2d_f32_pack': (ctypes.c_int, [_CP, _I32, _VP, _VP, _SZ, _VP]),
-    'lsi_conv2d_f32_pack_job': (ctypes.c_int, [_CP, _I32, _VP, _VP, _SZ,
-                                               ctypes.POINTER(LsiPackJob), _c_i]),
-    'lsi_conv2d_f32_pack_many': (ctypes.c_int, [_VP, _I32, _I32, _VP]),
-    'lsi_conv2d_f32_workspace_bytes': (_SZ, [_CP, _I32]),
-    'lsi_conv2d_f32_run': (ctypes.c_int, [_CP, _I32, ctypes.POINTER(LsiConvIO), _VP]),
-    'lsi_conv2d_wgrad_f32_workspace_bytes': (_SZ, [_CP]),
-    'lsi_conv2d_wgrad_f32': (ctypes.c_int, [_CP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _SZ,
-                                            _VP]),
-    'lsi_bn_workspace_floats': (_SZ, [_I64, _I32, _I32, _I32]),
-    'lsi_bn_launch_workgroups': (_I32, [_I64, _I32, _I32, _I32]),
-    'lsi_bn_relu_fwd': (ctypes.c_int, [_VP] * 5 + [_I64, _I32, _I32, _I32, _F32, _I32, _VP]),
-    'lsi_bn_relu_bwd': (ctypes.c_int, [_VP] * 7 + [_I64, _I32, _I32, _I32, _I32, _VP]),
-    'lsi_bn_relu_norm': (ctypes.c_int, [_VP] * 5 + [_I64, _I32, _I32, _I32, _F32, _I32, _VP]),
-    'lsi_bn_stats_discard': (ctypes.c_int, [_VP, _I32, _VP]),
-    'lsi_fc_desc_bytes': (_SZ, []),
-    'lsi_fc_supported': (ctypes.c_int, [ctypes.POINTER(LsiFcDesc)]),
-    'lsi_fc_workspace_bytes': (_SZ, [ctypes.POINTER(LsiFcDesc)]),
-    'lsi_fc_fwd': (ctypes.c_int, [ctypes.POINTER(LsiFcDesc)] + [_VP] * 7 + [_SZ, _VP]),
-    'lsi_fc_bwd': (ctypes.c_int, [ctypes.POINTER(LsiFcDesc)] + [_VP] * 10 + [_SZ, _VP]),
-    'lsi_area_resize_u8': (ctypes.c_int, [_I32, _VP, _VP, _VP, _SZ] + [_I32] * 3 +
-                           [_VP, _VP]),
-    'lsi_augment_resize_u8': (ctypes.c_int, [_I32, _VP, _VP, _VP, _SZ, _I64, _I32] +
-                              [_I32] * 3 + [_VP, _VP]),
-    'lsi_augment_sample_u16': (ctypes.c_int, [_I32, _VP, _VP, _VP, _SZ, _I32, _I32,
-                                              _VP, _VP]),
-    'lsi_visual_sheet_size': (ctypes.c_int, [ctypes.POINTER(LsiVisSheet),
-                                             ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
-    'lsi_visual_pack_u8': (ctypes.c_int, [ctypes.POINTER(LsiVisSheet), _VP, _VP, _VP, _VP,
-                                          _I64, _VP]),
-    'lsi_sgm_workspace_bytes': (_SZ, [_I32] * 6),
-    'lsi_sgm_disparity_u8': (ctypes.c_int, [_I32] * 4 + [_VP] * 2 + [_I32] * 6 +
-                             [_VP] * 3 + [_SZ, _VP]),
-    'lsi_disparity_filter_workspace_bytes': (_SZ, [_I32] * 5),
-    'lsi_disparity_filter_u16': (ctypes.c_int, [_I32] * 3 + [_VP] * 2 + [_I32] * 3 +
-                                 [_VP, _SZ, _VP]),
-    'lsi_lidar_workspace_bytes': (_SZ, [_I32] * 6),
-    'lsi_lidar_rasterize': (ctypes.c_int, [_I32] * 4 + [_VP] * 3 + [_I64, _VP, _F32, _F32,
-                                                                  _I32, _I32, _F32,
-                                                                  ctypes.c_uint32] +
-                            [_VP, _VP, _SZ, _VP]),
-    'lsi_fill_holes_workspace_bytes': (_SZ, [_I32] * 4),
-    'lsi_fill_holes': (ctypes.c_int, [_I32] * 4 + [_VP, _VP, _I32, _F32, _F32, _F32,
-                                                   _VP, _VP, _SZ, _VP]),
+_SCALARS = {
+    'void': None, 'char': ctypes.c_char, 'int': ctypes.c_int, 'float': ctypes.c_float,
+    'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'int8_t': ctypes.c_int8,
+    'uint8_t': ctypes.c_uint8, 'uint16_t': ctypes.c_uint16, 'int32_t': ctypes.c_int32,
+    'uint32_t': ctypes.c_uint32, 'int64_t': ctypes.c_int64,
 }
+# [const|volatile] type [*] name [[N] | []]
+_DECL = re.compile(r'((?:(?:const|volatile) )*\w+) ?(\*?) ?(\w+) ?(?:\[(\d*)\])?$')
+
+
+def _declarator(text, structs, where):
+  """(name, ctype) of a struct field, a parameter or `restype function`."""
+  m = _DECL.match(text.strip())
+  if not m:
+    raise ValueError('lsi_hip.h: cannot read the declaration `%s`' % text)
+  base, star, name, dim = m.group(1).split()[-1], m.group(2), m.group(3), m.group(4)
+  if base == 'lsi_stream_t' and not star and dim is None and where == 'param':
+    return name, ctypes.c_void_p
+  if base not in _SCALARS and base not in structs:
+    raise ValueError('lsi_hip.h: unknown type `%s` in `%s`' % (base, text))
+  if dim is not None:
+    if not star and where == 'field' and dim and _SCALARS.get(base):
+      return name, _SCALARS[base] * int(dim)    # T x[N]: an array member
+    if not star and where == 'param' and not dim:
+      return name, ctypes.c_void_p              # T x[]: the address of an array
+    raise ValueError('lsi_hip.h: cannot map the array `%s`' % text)
+  if star:
+    if where == 'return':
+      if base != 'char':
+        raise ValueError('lsi_hip.h: cannot map the return type of `%s`' % text)
+      return name, ctypes.c_char_p
+    typed = where == 'param' and base in structs
+    return name, ctypes.POINTER(structs[base]) if typed else ctypes.c_void_p
+  if base in structs or base == 'char' or (base == 'void' and where != 'return'):
+    raise ValueError('lsi_hip.h: cannot map `%s`' % text)
+  return name, _SCALARS[base]
+
+
+def parse(text):
+  """(constants, structs, signatures) of a header written in lsi_hip.h's style;
+  raises ValueError on anything it cannot map.  A pure function of the text."""
+  constants, structs, signatures = {}, {}, {}
+  code, cplusplus = [], False
+  for line in re.sub(r'/\*.*?\*/', ' ', text, flags=re.S).splitlines():
+    line = line.strip()
+    if cplusplus:           # what only a C++ compiler sees is no part of the C ABI
+      cplusplus = line != '#endif'
+    elif line == '#ifdef __cplusplus':
+      cplusplus = True
+    elif line.startswith('#define'):
+      words = line.split(None, 2)
+      if len(words) == 3:   # (a define without a value is the include guard)
+        if not re.match(r'-?\d+u?$', words[2]):
+          raise ValueError('lsi_hip.h: `%s` is no integer constant' % line)
+        constants[words[1]] = int(words[2].rstrip('u'))
+    elif line.startswith('#'):
+      if not re.match(r'#(include|ifndef|endif)\b', line):
+        raise ValueError('lsi_hip.h: cannot read `%s`' % line)
+    else:
+      code.append(line)
+  code = ' '.join(' '.join(code).split())
+
+  def struct(m):
+    fields = []
+    for stmt in filter(None, (s.strip() for s in m.group(2).split(';'))):
+      # `type a, b[N], c`: one type, then the names that share it
+      d = re.match(r'(.*?[ *])(\w+(?:\[\d*\])?(?: ?, ?\w+(?:\[\d*\])?)*)$', stmt)
+      if not d or ('*' in d.group(1) and ',' in d.group(2)):
+        raise ValueError('lsi_hip.h: cannot read the member `%s`' % stmt)
+      fields += [_declarator(d.group(1) + n.strip(), structs, 'field')
+                 for n in d.group(2).split(',')]
+    structs[m.group(1)] = type(m.group(1), (ctypes.Structure,), {'_fields_': fields})
+    return ''
+
+  code = re.sub(r'typedef struct (\w+) \{(.*?)\} ?\1 ?;', struct, code)
+  *stmts, rest = code.split(';')
+  if rest.strip():
+    raise ValueError('lsi_hip.h: `%s` does not end in `;`' % rest)
+  for stmt in stmts:
+    stmt = stmt.strip()
+    if stmt in ('', 'typedef void* lsi_stream_t'):  # (mapped by name in _declarator)
+      continue
+    m = re.match(r'([^(){}]+)\(([^(){}]*)\)$', stmt)
+    if not m:
+      raise ValueError('lsi_hip.h: cannot read the declaration `%s`' % stmt)
+    name, res = _declarator(m.group(1), structs, 'return')
+    params = [] if m.group(2).strip() == 'void' else m.group(2).split(',')
+    signatures[name] = (res, [_declarator(p, structs, 'param')[1] for p in params])
+  return constants, structs, signatures
+
+
+if not os.path.exists(HEADER_PATH):
+  raise RuntimeError('include/lsi_hip.h is missing (%s): the binding of '
+                     'liblsi_hip.so is derived from it' % HEADER_PATH)
+with open(HEADER_PATH) as _f:
+  # LSI_* -> int; Lsi* -> Structure; name -> (restype, argtypes) of every symbol
+  CONSTANTS, STRUCTS, SIGNATURES = parse(_f.read())
+globals().update(CONSTANTS)
+globals().update(STRUCTS)
+_DP = ctypes.POINTER(STRUCTS['LsiSplatDesc'])
+PATH_NAMES = {v: k[len('LSI_PATH_'):].lower() for k, v in CONSTANTS.items()
+              if k.startswith('LSI_PATH_') and v != CONSTANTS['LSI_PATH_AUTO']}
 
 _lib = None
 
@@ -352,7 +146,7 @@ def lib():
 
 
 def check(rc, what):
-  if rc != LSI_OK:
+  if rc != LSI_OK:  # pylint: disable=undefined-variable  (from the header)
     msg = lib().lsi_strerror(rc).decode()
     raise RuntimeError('%s failed: %s (code %d)' % (what, msg, rc))
 

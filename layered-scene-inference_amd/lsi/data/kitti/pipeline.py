@@ -53,18 +53,14 @@ from concurrent import futures
 
 import numpy as np
 
+from lsi import _C
 from lsi.data.kitti import data as kitti_data
 
 MAX_THREADS = 16
-DESC_DTYPE = np.dtype([('offset', '<i8'), ('H', '<i4'), ('W', '<i4'),
-                       ('C', '<i4'), ('reserved', '<i4')])  # _C.LsiImageDesc
-AUG_DESC_DTYPE = np.dtype([('offset', '<i8'), ('H', '<i4'), ('W', '<i4'),
-                           ('C', '<i4'), ('flags', '<u4'), ('y0', '<i4'),
-                           ('x0', '<i4'), ('ch', '<i4'), ('cw', '<i4'),
-                           ('table', '<i4'), ('reserved', '<i4'),
-                           ('gain', '<f4', (3,)),
-                           ('reserved2', '<i4')])  # _C.LsiAugmentDesc
-AUG_FLIP = 1
+# the records of include/lsi_hip.h, as the binding lays them out
+DESC_DTYPE = np.dtype(_C.LsiImageDesc)
+AUG_DESC_DTYPE = np.dtype(_C.LsiAugmentDesc)
+AUG_FLIP = _C.LSI_AUG_FLIP
 TABLE_BYTES = 3 * 256
 
 
@@ -101,7 +97,6 @@ def area_resize_u8(packed, desc_host, desc_dev, n, h, w, nc, out=None):
   records, desc_dev the address of their device copy.  Returns float32
   [n, h, w, nc] on packed's device."""
   import torch  # pylint: disable=g-import-not-at-top
-  from lsi import _C  # pylint: disable=g-import-not-at-top
   if not packed.is_cuda:
     raise RuntimeError('the device AREA resize needs a ROCm GPU (got device %s); '
                        'there is no CPU fallback' % packed.device)
@@ -142,7 +137,6 @@ def augment_resize_u8(packed, desc_host, desc_dev, n, h, w, nc, tables_offset=0,
   AUG_DESC_DTYPE records; the n_tables tone tables (uint8[nc][256] each) lie
   in `packed` from byte tables_offset.  Returns float32 [n, h, w, nc]."""
   import torch  # pylint: disable=g-import-not-at-top
-  from lsi import _C  # pylint: disable=g-import-not-at-top
   if not packed.is_cuda:
     raise RuntimeError('the device AREA resize needs a ROCm GPU (got device %s); '
                        'there is no CPU fallback' % packed.device)
@@ -166,7 +160,6 @@ def augment_sample_u16(packed, desc_host, desc_dev, n, h, w, out=None):
   their AUG_DESC_DTYPE records (C = 1, table -1), in pixels of the h x w image
   (augment.sample_disparity_px's bits).  Returns float32 [n, h, w, 1]."""
   import torch  # pylint: disable=g-import-not-at-top
-  from lsi import _C  # pylint: disable=g-import-not-at-top
   if not packed.is_cuda:
     raise RuntimeError('the device disparity sampling needs a ROCm GPU (got device '
                        '%s); there is no CPU fallback' % packed.device)
@@ -256,7 +249,7 @@ def _device_task(stop, path, nc, staging, slot):
     raise RuntimeError('the loader was closed')
   arr = decode_u8(path, nc)
   h, w = arr.shape[:2]
-  if h * w > 16843009:
+  if h * w > _C.LSI_IMAGE_MAX_PIXELS:
     raise ValueError('%s: %d x %d pixels exceed the resize kernel\'s bound' %
                      (path, h, w))
   off = staging.alloc(arr.size)

@@ -11,18 +11,18 @@ import torch
 
 from lsi import _C
 
+
+def _slots(prefix, names):
+  return {n: getattr(_C, prefix + n) for n in names.split()}
+
+
 # the header's LSI_EVAL_* slots of the accumulator
-SLOTS = {
-    'COMPOSE_SUM': 0, 'COMPOSE_NORM': 1,
-    'COMPOSE_DISOCC_SUM': 2, 'COMPOSE_DISOCC_NORM': 3,
-    'DEPTH_SUM': 4, 'DEPTH_NORM': 5,
-    'DEPTH_DISOCC_SUM': 6, 'DEPTH_DISOCC_NORM': 7,
-    'PSNR_SUM': 8, 'PSNR_COUNT': 9,
-    'FG_TEX_SUM': 10, 'FG_DISP_SUM': 11, 'FG_NORM': 12,
-    'BG_TEX_SUM': 13, 'BG_DISP_SUM': 14, 'BG_NORM': 15,
-}
-SLOT_COUNT = 16
-LSI_EVAL_DISOCC_U8, LSI_EVAL_VALID_GT = 1, 2
+SLOTS = _slots('LSI_EVAL_', 'COMPOSE_SUM COMPOSE_NORM COMPOSE_DISOCC_SUM '
+               'COMPOSE_DISOCC_NORM DEPTH_SUM DEPTH_NORM DEPTH_DISOCC_SUM '
+               'DEPTH_DISOCC_NORM PSNR_SUM PSNR_COUNT FG_TEX_SUM FG_DISP_SUM FG_NORM '
+               'BG_TEX_SUM BG_DISP_SUM BG_NORM')
+SLOT_COUNT = _C.LSI_EVAL_SLOTS
+LSI_EVAL_DISOCC_U8, LSI_EVAL_VALID_GT = _C.LSI_EVAL_DISOCC_U8, _C.LSI_EVAL_VALID_GT
 
 # metric name (the keys of eval_metrics.aggregate) -> (sum slot, normaliser slot)
 METRICS = {
@@ -136,10 +136,9 @@ def ssim_metric(acc2, recons, target, x_min, y_min, win, sigma):
 
 
 # the header's LSI_DEPTH_* slots of the depth accumulator (lsi_eval_depth_metrics)
-DEPTH_SLOTS = {'ABS_REL': 0, 'SQ_REL': 1, 'RMSE': 2, 'RMSE_LOG': 3, 'A1': 4, 'A2': 5,
-               'A3': 6, 'SCALE': 7, 'IMAGES': 8}
-DEPTH_SLOT_COUNT, DEPTH_PER_IMAGE = 9, 10
-LSI_DEPTH_MASK_U8, LSI_DEPTH_MEDIAN = 1, 2
+DEPTH_SLOTS = _slots('LSI_DEPTH_', 'ABS_REL SQ_REL RMSE RMSE_LOG A1 A2 A3 SCALE IMAGES')
+DEPTH_SLOT_COUNT, DEPTH_PER_IMAGE = _C.LSI_DEPTH_SLOTS, _C.LSI_DEPTH_PER_IMAGE
+LSI_DEPTH_MASK_U8, LSI_DEPTH_MEDIAN = _C.LSI_DEPTH_MASK_U8, _C.LSI_DEPTH_MEDIAN
 # metric name -> sum slot; the normaliser of every one is the IMAGES slot
 DEPTH_METRICS = {
     'depth_abs_rel': 'ABS_REL', 'depth_sq_rel': 'SQ_REL', 'depth_rmse': 'RMSE',

@@ -47,6 +47,117 @@ def test_desc_struct_matches_header_layout(built_lib):
   assert _C.LsiSplatDesc.flags.offset == 144
 
 
+def test_layouts_and_constants_match_the_compiler(tmp_path):
+  """Everything lsi._C derives from include/lsi_hip.h, held to what the C
+  compiler of the ROCm toolchain makes of the same header: the size of every
+  struct, the offset and size of every field and the value of every constant,
+  as _Static_asserts in one C11 file.  Syntax check only: no GPU, no link, no
+  run."""
+  import subprocess
+  import build as lsi_build  # layered-scene-inference_amd/build.py
+  from lsi import _C
+  bin_dir = os.path.dirname(os.path.realpath(lsi_build.hipcc()))
+  found = [p for p in (os.path.join(bin_dir, 'amdclang'),
+                       os.path.join(bin_dir, '..', 'lib', 'llvm', 'bin', 'clang'),
+                       os.path.join(bin_dir, '..', 'llvm', 'bin', 'clang'))
+           if os.path.exists(p)]
+  assert found, 'no clang beside %s' % lsi_build.hipcc()
+  lines = ['#include <stddef.h>', '#include "lsi_hip.h"']
+  check = lambda cond: lines.append('_Static_assert(%s, "%s");' % (cond, cond))
+  n_fields = 0
+  for name, cls in _C.STRUCTS.items():
+    assert getattr(_C, name) is cls
+    check('sizeof(%s) == %d' % (name, ctypes.sizeof(cls)))
+    for field, _ in cls._fields_:
+      at = getattr(cls, field)
+      check('offsetof(%s, %s) == %d' % (name, field, at.offset))
+      check('sizeof(((%s*)0)->%s) == %d' % (name, field, at.size))
+      n_fields += 1
+  for name, value in _C.CONSTANTS.items():
+    assert getattr(_C, name) == value
+    check('%s == %d' % (name, value))
+  assert len(_C.STRUCTS) >= 17 and n_fields >= 222 and len(_C.CONSTANTS) >= 78
+  src = tmp_path / 'layouts.c'
+  src.write_text('\n'.join(lines) + '\n')
+  done = subprocess.run(
+      [found[0], '-x', 'c', '-std=c11', '-fsyntax-only', '-Wall', '-Werror',
+       '-I', os.path.join(ROOT, 'include'), str(src)],
+      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+  assert done.returncode == 0, done.stdout
+
+
+SNIPPET = '''
+/* a comment may hold anything:
+#define LSI_NOT 1
+int lsi_not(void); */
+#ifndef LSI_SNIPPET_H_
+#define LSI_SNIPPET_H_
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define LSI_FLAG 4u   /* a flag */
+#define LSI_ECODE -3
+typedef void* lsi_stream_t; /* hipStream_t */
+typedef struct LsiRec {
+  int64_t first;           /* bytes */
+  int32_t n, tap[3];
+  const float* src;        /* device */
+  uint8_t bg[2];
+} LsiRec;
+int lsi_run(const LsiRec* one, const LsiRec many[], const float* data,
+            size_t nbytes, lsi_stream_t stream);
+const char* lsi_name(int code);
+size_t lsi_bytes(void);
+#ifdef __cplusplus
+}
+#endif
+#endif /* LSI_SNIPPET_H_ */
+'''
+
+
+def test_header_parser_maps_the_style_and_refuses_the_rest():
+  """lsi._C.parse on literal snippets in the header's style: exactly the
+  expected ctypes; a declaration it cannot map raises, none is skipped."""
+  from lsi import _C
+  constants, structs, signatures = _C.parse(SNIPPET)
+  assert constants == {'LSI_FLAG': 4, 'LSI_ECODE': -3}
+  assert list(structs) == ['LsiRec']
+  rec = structs['LsiRec']
+  assert issubclass(rec, ctypes.Structure) and rec.__name__ == 'LsiRec'
+  assert rec._fields_ == [
+      ('first', ctypes.c_int64), ('n', ctypes.c_int32), ('tap', ctypes.c_int32 * 3),
+      ('src', ctypes.c_void_p), ('bg', ctypes.c_uint8 * 2)]
+  assert ctypes.sizeof(rec) == 40 and rec.src.offset == 24 and rec.bg.offset == 32
+  assert signatures == {
+      'lsi_run': (ctypes.c_int, [ctypes.POINTER(rec), ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_size_t, ctypes.c_void_p]),
+      'lsi_name': (ctypes.c_char_p, [ctypes.c_int]),
+      'lsi_bytes': (ctypes.c_size_t, []),
+  }
+  record = 'typedef struct LsiRec { int32_t n; } LsiRec;\n'
+  for bad in ('int lsi_f(long n);',                      # unknown type
+              'typedef struct LsiBad { wchar_t c; } LsiBad;',
+              'unsigned lsi_f(void);',
+              '#define LSI_HALF 0.5',                    # non-integer defines
+              '#define LSI_SHIFT (1 << 4)',
+              '#define LSI_TEXT "text"',
+              'int lsi_f(int (*callback)(int));',        # prototypes it cannot split
+              'int lsi_f(int32_t a, b);',
+              'int lsi_f(int32_t a)',
+              'int lsi_f(int32_t a) { return a; }',
+              record + 'int lsi_f(LsiRec by_value);',
+              record + 'LsiRec* lsi_f(void);',
+              'int lsi_f(const float* rows[]);',
+              'typedef struct LsiBad { int32_t* a, b; } LsiBad;',
+              'typedef struct LsiBad { int32_t n; } LsiOther;',
+              'typedef int lsi_int;',
+              '#if LSI_FLAG\n#endif',
+              'static const int lsi_k = 1;'):
+    with pytest.raises(ValueError):
+      _C.parse(bad)
+
+
 def test_bg_weight_matches_reference_known_answers(built_lib):
   from lsi import _C
   g = golden('known_answers.npz')

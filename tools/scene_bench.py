@@ -82,7 +82,10 @@ def main():
   dmat = dmat.reshape(args.bs, 2, npl, 3).contiguous()
   result = {'loaders_s': med, 'spread_s': spread, 'bs': args.bs, 'hw': args.hw,
             'gt': bool(args.gt), 'launch': {}}
-  for label, bits in (('img', 1), ('img+disp', 3), ('all four', 15)):
+  out_bits = (_C.LSI_SCENE_IMG, _C.LSI_SCENE_DISP, _C.LSI_SCENE_IMG_ROOM,
+              _C.LSI_SCENE_DISP_ROOM)
+  for label, bits in (('img', out_bits[0]), ('img+disp', sum(out_bits[:2])),
+                      ('all four', sum(out_bits))):
     d = _C.LsiSceneDesc()
     d.B, d.V, d.P, d.Hs, d.Ws, d.H, d.W = args.bs, 2, npl, h, w, h, w
     d.n_box, d.soft, d.min_disp, d.temp, d.outputs = 5, 0, sp.MIN_DISP, sp.SOFTMAX_TEMP, bits
@@ -110,7 +113,7 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3 / args.replays
-    nbytes = tex.numel() * 4 + sum(o.numel() * 4 for o, bit in zip(outs, (1, 2, 4, 8))
+    nbytes = tex.numel() * 4 + sum(o.numel() * 4 for o, bit in zip(outs, out_bits)
                                    if bits & bit)
     frac = nbytes / (us * 1e-6) / 8e12
     print('lsi_render_planes %-9s %8.1f us per launch, %6.1f MB to move, %4.1f %% of 8 TB/s'

@@ -755,6 +755,85 @@ int lsi_geo_cons_loss_bwd(const LsiGeoConsDesc* desc, const float* disp,
                           float* g_disp, float* g_partner, lsi_stream_t stream);
 
 /*
+ * Backward-warp photometric loss over the layers of an LDI
+ * (csrc/lsi_photo_reproj.hip; no reference counterpart, the definition is
+ * DESIGN.md section 4.23; Garg et al. 2016, Godard et al. 2017, Zhou et al. 2017).
+ * tex [P,H,W,C] with C in 1 .. 4 and disp [P,H,W]; img [Q,H,W,C] with the element
+ * strides i_s*, the images that are sampled; M [Q,4,4] contiguous; partner
+ * [Q,H,W] with e_s* or NULL, the inverse depths of the sampled views' visible
+ * surface.  Q divides P: plane p = l Q + q is layer l of view q = p mod Q, it
+ * uses the matrix M[q] and the image and partner plane r = (q + shift) mod Q,
+ * so L x B layers of B views are P = L B planes over Q = B images; a buffer of
+ * 2 B views pairs each half with the other by shift = B.  Plane p of tex begins
+ * at element l t_sl + q t_sq, of disp at l d_sl + q d_sq (a contiguous [P,...]
+ * has t_sl = Q t_sq): the network's [L,Q,H,W,4] views of one [Q,H,W,L,4] buffer
+ * are read in place.  Pixel (x, y) of plane p with
+ * d = disp[p,y,x] is projected to (u, v, dd) by M[q] exactly as
+ * lsi_geo_cons_loss_fwd projects it (q_j, n, n' above);
+ *   s_c = the bilinear sample of img[r,:,:,c] at (u, v), taps, weights and order
+ *         of lsi_bilinear_fwd.
+ * The pixel is scored when d, u, v, dd are finite, n > 0, dd > 0,
+ * 0.5 <= u <= W - 0.5, 0.5 <= v <= H - 0.5, every tex[p,y,x,c] and every s_c is
+ * finite and, with occl_thresh > 0, the bilinear sample sd of partner[r] at
+ * (u, v) is > 0 and not sd - dd > occl_thresh (sd + dd).  With tex_c and s_c
+ * widened to fp64 and summed over c in order:
+ *   LSI_PHOTO_L1      e = (1 / C) sum_c |tex_c - s_c|
+ *   LSI_PHOTO_CHARB   e = (1 / C) sum_c sqrt((tex_c - s_c)^2 + eps^2)
+ *   loss = 1 / S sum_{N_p > 0} (sum e over plane p) / N_p, N_p = scored pixels
+ *   of plane p, S = planes with N_p > 0; 0 when S = 0.
+ * Gradient w.r.t. tex and disp only; the scored set, M, img and partner are
+ * constants, dd enters only the rule.  In fp32, x_c = tex_c - s_c, psi'(x) =
+ * sign(x) (sign(0) = 0) or x / sqrt(x^2 + eps^2), g = g_loss / (S N_p):
+ *   g_tex[p,y,x,c] = (g / C) psi'(x_c)
+ *   g_disp[p,y,x]  = -(g / C) ((sum_c psi'(x_c) ds_c/du) du/dd +
+ *                               (sum_c psi'(x_c) ds_c/dv) dv/dd)
+ * with du/dd, dv/dd, ds/du, ds/dv the expressions of lsi_geo_cons_loss_bwd; 0
+ * where the pixel is not scored.  Every cell of a requested gradient is stored
+ * exactly once, by the thread of its pixel: no zero-fill, no atomics.
+ * LSI_EINVAL for an unknown mode, non-positive dimensions, C outside 1 .. 4,
+ * P > 65535, Q not a divisor of P, H W >= 2^24, P H W > INT32_MAX, shift
+ * outside [0, Q), occl_thresh outside [0, 1) or eps not finite and > 0; then
+ * LSI_ENULL (partner may be NULL only with occl_thresh == 0; it is not read
+ * then); then LSI_EWORKSPACE -- all before any launch.  No host
+ * synchronisation, no allocation: both directions can be captured in a HIP
+ * graph, and in both the same inputs give the same bits.
+ */
+#define LSI_PHOTO_L1 0
+#define LSI_PHOTO_CHARB 1
+typedef struct LsiPhotoReprojDesc {
+  int32_t P, Q, H, W, C, mode;
+  int64_t t_sl, t_sq, t_sy, t_sx, t_sc;
+  int64_t d_sl, d_sq, d_sy, d_sx;
+  int64_t i_sq, i_sy, i_sx, i_sc;
+  int64_t e_sq, e_sy, e_sx;
+  int32_t shift;
+  float occl_thresh, eps;
+  int32_t reserved;
+} LsiPhotoReprojDesc;
+
+/* (3 P bpp + P) doubles: a block covers r = max(ceil(1024 / W), ceil(H / 256))
+ * rows of a plane, bpp = ceil(H / r) blocks per plane; 0 for a descriptor the
+ * entries below refuse. */
+size_t lsi_photo_reproj_workspace_bytes(const LsiPhotoReprojDesc* desc);
+/* 2 launches.  out_loss (one device float) = the loss; plane_sums (3 P device
+ * doubles, the caller's) = sum e, N_p, 0 at [3 p .. 3 p + 2]: written by the
+ * finishing kernel, read by the backward.  out_map [P,H,W] contiguous or NULL:
+ * the per-pixel e as fp32, -1 where the pixel is not scored.  The library keeps
+ * no state. */
+int lsi_photo_reproj_loss_fwd(const LsiPhotoReprojDesc* desc, const float* tex,
+                              const float* disp, const float* img, const float* M,
+                              const float* partner, float* out_loss,
+                              double* plane_sums, float* out_map, void* workspace,
+                              size_t workspace_bytes, lsi_stream_t stream);
+/* 1 launch.  g_tex [P,H,W,C] and g_disp [P,H,W] contiguous, scaled by the
+ * device scalar g_loss; either may be NULL (not both): its work is skipped. */
+int lsi_photo_reproj_loss_bwd(const LsiPhotoReprojDesc* desc, const float* tex,
+                              const float* disp, const float* img, const float* M,
+                              const float* partner, const double* plane_sums,
+                              const float* g_loss, float* g_tex, float* g_disp,
+                              lsi_stream_t stream);
+
+/*
  * layers.compose, lsi/geometry/layers.py:29-70 with helpers.soft_z_buffering
  * (lsi/nnutils/helpers.py:140-160): white background layer at min_disp,
  * per-pixel softmax of log(mask + 1e-8) - depth / temp over the L + 1 layers,

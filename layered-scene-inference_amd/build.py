@@ -22,7 +22,7 @@ SOURCES = ['lsi_splat.hip', 'lsi_splat_stream.hip', 'lsi_splat_stream2.hip',
            'lsi_conv_wgrad.hip', 'lsi_conv_igemm.hip', 'lsi_conv_wgrad_igemm.hip',
            'lsi_conv_first.hip', 'lsi_conv_f32.hip', 'lsi_scene.hip', 'lsi_fc.hip',
            'lsi_image.hip', 'lsi_ssim.hip', 'lsi_edge_smooth.hip', 'lsi_depth_sup.hip',
-           'lsi_geo_cons.hip',
+           'lsi_geo_cons.hip', 'lsi_photo_reproj.hip',
            'lsi_visual.hip',
            'lsi_depth_metrics.hip', 'lsi_sgm.hip', 'lsi_disp_filter.hip',
            'lsi_lidar.hip', 'lsi_fill.hip']

@@ -49,7 +49,8 @@ __device__ __forceinline__ void tap_weights(const Taps& t, float (&c)[4]) {
 
 // ... and the sample, summed in that order; 0 for a non-finite point.  at(i) is
 // the image's value at the flat tap index i = x + y*Ws.  (The one gather of
-// lsi_bilinear_fwd, lsi_disocclusion_mask and lsi_geo_cons_loss_*.)
+// lsi_bilinear_fwd, lsi_disocclusion_mask, lsi_geo_cons_loss_* and
+// lsi_photo_reproj_loss_*.)
 template <class At>
 __device__ __forceinline__ float bilinear_gather_at(const Taps& t, const float (&c)[4],
                                                     At at) {

@@ -9,9 +9,9 @@
 //                sums per plane (plane_store_partials), then ONE block
 //                (plane_finish_kernel) that writes the plane sums and the mean
 //                of the planes' terms: lsi_edge_smooth.hip, lsi_depth_sup.hip,
-//                lsi_geo_cons.hip.
+//                lsi_geo_cons.hip, lsi_photo_reproj.hip.
 //
-// rc_of_launch() is here for all seven, sgn() for lsi_loss.hip and the three
+// rc_of_launch() is here for all eight, sgn() for lsi_loss.hip and the four
 // per-plane losses.
 #pragma once
 #include <hip/hip_runtime.h>

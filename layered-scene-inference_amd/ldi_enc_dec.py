@@ -173,6 +173,24 @@ def build_parser():
   a('--geo_cons_occl', type=float, default=0.0,
     help='a pixel whose projection lies behind the other view\'s surface, s - dd > '
     'geo_cons_occl * (s + dd), is not scored; 0 = every pixel that lands is')
+  a('--photo_reproj_wt', type=float, default=0.0,
+    help='weight of the backward-warp photometric term (csrc/lsi_photo_reproj.hip, '
+    'DESIGN.md 4.23): every pixel\'s disparity is projected into the other view, '
+    'that view\'s input image is sampled bilinearly where the point lands and the '
+    'sample is compared with the colour the pixel should have there; '
+    'photo_reproj_wt * photo_reproj_loss is added to the total; 0 = no such term, '
+    'no extra launch')
+  a('--photo_reproj_mode', default='l1', choices=['l1', 'charb'],
+    help='|tex - s|, or the Charbonnier sqrt((tex - s)^2 + 1e-6), mean over the '
+    'channels')
+  a('--photo_reproj_occl', type=float, default=0.2,
+    help='a point that lies behind the other view\'s layer-0 surface, sd - dd > '
+    'photo_reproj_occl * (sd + dd), is not scored; 0 = every pixel that lands is')
+  a('--photo_reproj_what', default='texture', choices=['texture', 'image'],
+    help="'texture': every layer's predicted texture at that layer's disparity -- "
+    "hidden layers learn their colours where the other view sees them; 'image': "
+    "layer 0's disparity only, compared with the view's own input image (the "
+    'classic monocular-depth term; no texture gradient)')
   a('--zbuf_scale', type=float, default=50)
   a('--trg_splat_downsampling', type=float, default=0.5)
   a('--disp_smoothness_wt', type=float, default=0.1)
@@ -720,6 +738,32 @@ class Trainer(train_utils.Trainer):
             loss.geometric_consistency_loss(ldi_trg[2][0], mats['src'],
                                             partner_disps=ldi_src[2][0], **geo_kw))
 
+    # backward-warp photometric term (no reference counterpart)
+    photo_wt = getattr(opts, 'photo_reproj_wt', 0.0)
+    if photo_wt > 0:
+      photo_kw = dict(mode=opts.photo_reproj_mode, occl_thresh=opts.photo_reproj_occl)
+      by_texture = opts.photo_reproj_what == 'texture'
+
+      def photo_loss(l, own_imgs, other_imgs, mat, visible, shift):
+        # texture: all layers at their own disparities; image: layer 0's
+        # disparities under the view's own input image
+        tex, disps = (l[0], l[2]) if by_texture else (own_imgs, l[2][0])
+        return loss.photometric_reprojection_loss(
+            tex, disps, other_imgs, mat,
+            partner_disps=visible.detach(), shift=shift, **photo_kw)
+      if paired:
+        # one call on the 2 B views: a plane of view q samples the input image of
+        # view q +- B; the matrices are the paired splat's
+        if mat2 is None:
+          mat2 = torch.cat([mats['trg'], mats['src']], dim=0)
+        imgs2 = torch.cat([imgs_src, imgs_trg], dim=0)
+        photo_reproj_loss = 2.0 * photo_loss(pair, imgs2, imgs2, mat2, pair[2][0],
+                                             imgs_src.shape[0])
+      else:
+        photo_reproj_loss = (
+            photo_loss(ldi_src, imgs_src, imgs_trg, mats['trg'], ldi_trg[2][0], 0) +
+            photo_loss(ldi_trg, imgs_trg, imgs_src, mats['src'], ldi_src[2][0], 0))
+
     total = zero
     if opts.self_cons_wt > 0:
       total = total + opts.self_cons_wt * self_cons_loss
@@ -746,6 +790,8 @@ class Trainer(train_utils.Trainer):
       # the ratio is scale-free; l1 is linear in d
       total = total + (geo_wt / opts.max_disp if opts.geo_cons_mode == 'l1'
                        else geo_wt) * geo_cons_loss
+    if photo_wt > 0:
+      total = total + photo_wt * photo_reproj_loss
     scalars = {
         'self_cons_loss': self_cons_loss,
         'compose_splat_loss': compose_splat_loss,
@@ -763,6 +809,8 @@ class Trainer(train_utils.Trainer):
       scalars['depth_sup_loss'] = depth_sup_loss
     if geo_wt > 0:
       scalars['geo_cons_loss'] = geo_cons_loss
+    if photo_wt > 0:
+      scalars['photo_reproj_loss'] = photo_reproj_loss
     return total, scalars
 
 

@@ -548,6 +548,144 @@ def geometric_consistency_loss(disp, partner, mats, mode, occl_thresh,
   return res if len(res) > 1 else out
 
 
+# launches of the photometric-reprojection kernels through this binding
+CALLS.update({'photo_reproj_fwd': 0, 'photo_reproj_bwd': 0})
+PHOTO_MODES = {'l1': _C.LSI_PHOTO_L1, 'charb': _C.LSI_PHOTO_CHARB}
+
+
+def photo_reproj_desc(tex, disp, img, mats, partner, shift, mode, occl_thresh, eps,
+                      what):
+  """The LsiPhotoReprojDesc of tex L x Q x H x W x C and disp L x Q x H x W (plane
+  p = l Q + q) against img Q x H x W x C under mats Q x 4 x 4, partner Q x H x W
+  or None (any strides); RuntimeError for a wrong shape or dtype, ValueError for
+  what the kernels would refuse with LSI_EINVAL."""
+  for name, t in (('layer_imgs', tex), ('layer_disps', disp), ('other_imgs', img),
+                  ('mats', mats), ('partner_disps', partner)):
+    if t is not None and t.dtype != torch.float32:
+      raise RuntimeError('%s: %s is fp32 (got %s)' % (what, name, t.dtype))
+  if tex.dim() != 5 or disp.dim() != 4 or tuple(tex.shape[:4]) != tuple(disp.shape):
+    raise RuntimeError('%s: layer_imgs are L x Q x H x W x C and layer_disps L x Q x H x '
+                       'W, of one shape (got %s and %s)' %
+                       (what, tuple(tex.shape), tuple(disp.shape)))
+  nl, nq, h, w, c = tex.shape
+  p = nl * nq
+  if img.dim() != 4 or tuple(img.shape[1:]) != (h, w, c):
+    raise RuntimeError('%s: other_imgs are Q x H x W x C, %s (got %s)' %
+                       (what, ('Q', h, w, c), tuple(img.shape)))
+  q = img.shape[0]
+  if nq != q:
+    raise RuntimeError('%s: layer_imgs hold L layers of the Q = %d views of other_imgs '
+                       '(got %s)' % (what, q, tuple(tex.shape)))
+  if partner is not None and tuple(partner.shape) != (q, h, w):
+    raise RuntimeError('%s: partner_disps are Q x H x W, of one shape with other_imgs, '
+                       '%s (got %s)' % (what, (q, h, w), tuple(partner.shape)))
+  if tuple(mats.shape) != (q, 4, 4):
+    raise RuntimeError('%s: mats holds one 4 x 4 matrix per image, %s (got %s)' %
+                       (what, (q, 4, 4), tuple(mats.shape)))
+  if mode not in PHOTO_MODES:
+    raise ValueError("%s: the mode is 'l1' or 'charb' (got %r)" % (what, mode))
+  if min(p, q, h, w) < 1:
+    raise ValueError('%s: empty maps (%s over %d images)' % (what, (p, h, w), q))
+  if not 1 <= c <= 4:
+    raise ValueError('%s: 1 to 4 channels (got %d)' % (what, c))
+  if p > 65535 or h * w >= 1 << 24 or p * h * w > 2 ** 31 - 1:
+    raise ValueError('%s: at most 65535 planes of fewer than 2^24 pixels, 2^31 - 1 '
+                     'pixels in all (got %s)' % (what, (p, h, w)))
+  if isinstance(shift, bool) or int(shift) != shift or not 0 <= shift < q:
+    raise ValueError('%s: shift is an integer in [0, %d) (got %r)' % (what, q, shift))
+  occl_thresh, eps = float(occl_thresh), float(eps)
+  if not 0.0 <= occl_thresh < 1.0:
+    raise ValueError('%s: occl_thresh lies in [0, 1) (got %r)' % (what, occl_thresh))
+  if partner is None and occl_thresh > 0.0:
+    raise ValueError('%s: occl_thresh > 0 needs partner_disps (got %r without)' %
+                     (what, occl_thresh))
+  if not 0.0 < eps < float('inf'):
+    raise ValueError('%s: eps is finite and > 0 (got %r)' % (what, eps))
+  d = _C.LsiPhotoReprojDesc()
+  d.P, d.Q, d.H, d.W, d.C, d.mode = p, q, h, w, c, PHOTO_MODES[mode]
+  d.t_sl, d.t_sq, d.t_sy, d.t_sx, d.t_sc = tex.stride()
+  d.d_sl, d.d_sq, d.d_sy, d.d_sx = disp.stride()
+  d.i_sq, d.i_sy, d.i_sx, d.i_sc = img.stride()
+  if partner is not None:
+    d.e_sq, d.e_sy, d.e_sx = partner.stride()
+  d.shift, d.occl_thresh, d.eps = int(shift), occl_thresh, eps
+  return d
+
+
+class _PhotoReproj(torch.autograd.Function):
+  """lsi_photo_reproj_loss_fwd / _bwd."""
+
+  @staticmethod
+  def forward(ctx, tex, disp, img, mats, partner, shift, mode, occl_thresh, eps,
+              want_map):
+    d = photo_reproj_desc(tex, disp, img, mats, partner, shift, mode, occl_thresh, eps,
+                          'photometric_reprojection_loss')
+    dev = _C.require_device(tex, disp, img, mats, partner)
+    mats = mats.contiguous()
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    sums = torch.empty((3 * d.P,), dtype=torch.float64, device=dev)
+    emap = (torch.empty((d.P, d.H, d.W), dtype=torch.float32, device=dev)
+            if want_map else None)
+    n = int(_C.lib().lsi_photo_reproj_workspace_bytes(ctypes.byref(d)))
+    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+    CALLS['photo_reproj_fwd'] += 1
+    rc = _C.lib().lsi_photo_reproj_loss_fwd(
+        ctypes.byref(d), _C.ptr(tex), _C.ptr(disp), _C.ptr(img), _C.ptr(mats),
+        _C.ptr(partner), _C.ptr(out), _C.ptr(sums), _C.ptr(emap), _C.ptr(ws), n,
+        _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_photo_reproj_loss_fwd')
+    ctx.save_for_backward(tex, disp, img, mats, sums,
+                          partner if partner is not None else disp.new_empty(0))
+    ctx.has_partner = partner is not None
+    ctx.desc = d
+    if emap is None:
+      emap = disp.new_empty(0)
+    ctx.mark_non_differentiable(sums, emap)
+    return out, sums, emap
+
+  @staticmethod
+  def backward(ctx, g, _s, _m):
+    tex, disp, img, mats, sums, partner = ctx.saved_tensors
+    partner = partner if ctx.has_partner else None
+    dev = disp.device
+    d = ctx.desc
+    g = g.contiguous().float()
+    need_tex, need_disp = ctx.needs_input_grad[:2]
+    if not (need_tex or need_disp):
+      return (None,) * 10
+    g_tex = (torch.empty(tuple(tex.shape), dtype=torch.float32, device=dev)
+             if need_tex else None)
+    g_disp = (torch.empty(tuple(disp.shape), dtype=torch.float32, device=dev)
+              if need_disp else None)
+    CALLS['photo_reproj_bwd'] += 1
+    rc = _C.lib().lsi_photo_reproj_loss_bwd(
+        ctypes.byref(d), _C.ptr(tex), _C.ptr(disp), _C.ptr(img), _C.ptr(mats),
+        _C.ptr(partner), _C.ptr(sums), _C.ptr(g), _C.ptr(g_tex), _C.ptr(g_disp),
+        _C.stream_ptr(dev))
+    _C.check(rc, 'lsi_photo_reproj_loss_bwd')
+    return (g_tex, g_disp) + (None,) * 8
+
+
+def photometric_reprojection_loss(tex, disp, img, mats, partner, shift, mode,
+                                  occl_thresh, eps, return_map=False,
+                                  return_plane_sums=False):
+  """Backward-warp photometric loss of tex L x Q x H x W x C at disp L x Q x H x W
+  (any strides, never copied; plane p = l Q + q) against img Q x H x W x C sampled
+  under mats Q x 4 x 4, partner Q x H x W or None; the gradient is w.r.t. tex and
+  disp.  return_map:
+  also the per-pixel term, -1 where unscored; return_plane_sums: also the 3 P
+  doubles (sum e, N_p, 0) the forward left for the backward."""
+  # the sampled views and the cameras are constants here
+  for name, t in (('other_imgs', img), ('mats', mats), ('partner_disps', partner)):
+    if torch.is_tensor(t) and t.requires_grad:
+      raise RuntimeError('photometric_reprojection_loss: %s is not differentiable on '
+                         'the HIP path (pass %s.detach())' % (name, name))
+  out, sums, emap = _PhotoReproj.apply(tex, disp, img, mats, partner, shift, mode,
+                                       occl_thresh, eps, bool(return_map))
+  res = (out,) + ((emap,) if return_map else ()) + ((sums,) if return_plane_sums else ())
+  return res if len(res) > 1 else out
+
+
 class _Compose(torch.autograd.Function):
   """lsi_compose_fwd / lsi_compose_bwd on imgs [L,N,C], masks [L,N], dmaps
   [L,N] (contiguous fp32)."""

@@ -175,3 +175,79 @@ def geometric_consistency_loss(disps, mats, partner_disps=None, mode='ratio',
   e = None if partner_disps is None else _planes(partner_disps, 'partner_disps', what)
   return _hip.geometric_consistency_loss(d, e, mats, mode, occl_thresh,
                                          return_map=return_map)
+
+
+def _image_planes(t, name, what):
+  """[..., H, W, C] as a P x H x W x C view (never a copy)."""
+  if t.dim() < 3:
+    raise RuntimeError('%s: %s is [..., H, W, C] (got %s)' % (what, name, tuple(t.shape)))
+  h, w, c = t.shape[-3:]
+  try:
+    return t.view(-1, h, w, c)
+  except RuntimeError:
+    raise RuntimeError('%s: the leading dimensions of %s (%s, '
+                       'strides %s) do not flatten without a copy' %
+                       (what, name, tuple(t.shape), t.stride())) from None
+
+
+def _layers_of_views(t, q, tail, name, what):
+  """[..., *tail dimensions] as an L x Q x tail view (never a copy): the leading
+  dimensions flatten to L Q planes, plane p = l Q + q.  The planes need not lie
+  at one stride -- the layers of the network's buffer do not -- as long as the
+  split into layers and views is a view."""
+  if t.dim() < tail:
+    raise RuntimeError('%s: %s is [..., %s] (got %s)' %
+                       (what, name, 'H, W, C' if tail == 3 else 'H, W', tuple(t.shape)))
+  lead = 1
+  for n in t.shape[:t.dim() - tail]:
+    lead *= n
+  if q < 1 or lead % q:
+    raise ValueError('%s: the number of sampled images divides the number of planes '
+                     '(got %d planes of %s over %d images)' % (what, lead, name, q))
+  try:
+    return t.view((lead // q, q) + tuple(t.shape[t.dim() - tail:]))
+  except RuntimeError:
+    raise RuntimeError('%s: the leading dimensions of %s (%s, '
+                       'strides %s) do not flatten without a copy' %
+                       (what, name, tuple(t.shape), t.stride())) from None
+
+
+def photometric_reprojection_loss(layer_imgs, layer_disps, other_imgs, mats,
+                                  partner_disps=None, shift=0, mode='l1',
+                                  occl_thresh=0., eps=1e-3, return_map=False):
+  """Backward-warp photometric loss over the layers of an LDI (the
+  reference has none; Garg et al. 2016, Godard et al. 2017, Zhou et al. 2017).
+  layer_imgs is [..., H, W, C] with 1 <= C <= 4, layer_disps [..., H, W, 1] or
+  [..., H, W] with the same leading dimensions (flattened to P planes as views);
+  other_imgs [..., H, W, C] are the Q images that are sampled, mats Q x 4 x 4 on
+  the device, partner_disps [..., H, W, 1] or [..., H, W] (Q planes) or None the
+  inverse depths of the sampled views' visible surface (for both, a last
+  dimension of 1 is the channel from four dimensions on, as in `_planes`: a
+  map of width 1 needs its channel dimension).  Q divides P: plane p is
+  a layer of view q = p mod Q, mats[q] takes its pixels (x + .5, y + .5, 1, d)
+  to the frame of image r = (q + shift) mod Q -- L x B layers over B images with
+  shift 0, the trainer's buffer of 2 B views against its own input images with
+  shift B.  Each pixel's d is projected to (u, v, dd) in fp32 as the renderer
+  does, image r is sampled bilinearly at (u, v), and the sample is compared with
+  the pixel's own texture: mode 'l1' the mean over the channels of |tex - s|,
+  'charb' of sqrt((tex - s)^2 + eps^2).  The pixel is scored when everything is
+  finite, the point lies in front of that camera (n > 0, dd > 0) and inside the
+  hull of its pixel centres and -- with occl_thresh > 0, which needs
+  partner_disps -- it is visible there: the sample sd of partner r is > 0 and
+  not sd - dd > occl_thresh (sd + dd).  Per plane the mean over its scored
+  pixels; the loss is the mean over the planes that hold one, 0 if none does.
+  One fused HIP launch each way plus a one-block finish
+  (lsi_photo_reproj_loss_fwd / _bwd), no atomics: both directions give the same
+  bits on the same inputs.  The gradient is w.r.t. layer_imgs and layer_disps;
+  the scored set, the sampled images, mats and partner_disps are constants.
+  return_map: also the detached per-pixel term, P x H x W, -1 where unscored."""
+  from lsi.loss import _hip  # pylint: disable=g-import-not-at-top
+  what = 'photometric_reprojection_loss'
+  img = _image_planes(other_imgs, 'other_imgs', what)
+  e = None if partner_disps is None else _planes(partner_disps, 'partner_disps', what)
+  tex = _layers_of_views(layer_imgs, img.shape[0], 3, 'layer_imgs', what)
+  if layer_disps.dim() >= 4 and layer_disps.shape[-1] == 1:
+    layer_disps = layer_disps[..., 0]
+  disp = _layers_of_views(layer_disps, img.shape[0], 2, 'layer_disps', what)
+  return _hip.photometric_reprojection_loss(tex, disp, img, mats, e, shift, mode,
+                                            occl_thresh, eps, return_map=return_map)

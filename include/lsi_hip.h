@@ -1918,6 +1918,76 @@ int lsi_fill_holes(int32_t N, int32_t H, int32_t W, int32_t C, const float* img,
                    float conf_min, float* out, void* workspace, size_t workspace_bytes,
                    lsi_stream_t stream);
 
+/*
+ * A layered depth image as a textured triangle mesh: the packed vertex and face
+ * records of a binary little-endian PLY file (csrc/lsi_ldi_mesh.hip; DESIGN.md
+ * 4.24).  Forward only.  Per batch item b:
+ *   tex  [l,b,y,x,c] c in 0..2, disp [l,b,y,x], mask [l,b,y,x] (may be NULL):
+ *        float, device, read in place through the descriptor's ELEMENT strides
+ *        (RGBD-packed and planar buffers alike)
+ *   kinv_dev  B x 9 float, device: the inverse of the source intrinsics
+ *   in range  disp finite and disp >= disp_min (a NaN fails)
+ *   vertex (l, y, x) exists iff it is in range, mask is NULL or mask > mask_min
+ *        (a NaN fails), and it is not merged; it is merged iff merge_ratio > 0,
+ *        l > 0, layer l - 1 is in range at (y, x) and
+ *        disp_l >= merge_ratio * disp_{l-1}
+ *   position  u = x + 0.5, v = y + 0.5, z = 1 / disp,
+ *        P_r = ((kinv[3r] u + kinv[3r+1] v) + kinv[3r+2]) z for r = 0, 1, 2;
+ *        LSI_MESH_FLIP_YZ negates P_1 and P_2 (y up, looking down -z)
+ *   colour    per channel t = min(max(v, 0), 1), (int)floorf(t * 255 + 0.5), a
+ *        NaN gives 0 (lsi_visual_pack_u8's rule with lo = 0, inv = 1); alpha 255
+ *   vertex record, LSI_MESH_VERTEX_BYTES: float x, y, z; uchar r, g, b, alpha
+ *   faces     per layer the quad a = (y, x), b = (y, x+1), c = (y+1, x),
+ *        d = (y+1, x+1), y < H - 1, x < W - 1, gives triangle 0 (a, c, b) and
+ *        triangle 1 (b, c, d), counter-clockwise seen from the source camera; a
+ *        triangle exists iff its three vertices exist and
+ *        min(d_i) >= edge_ratio * max(d_i) over their disparities
+ *   face record, LSI_MESH_FACE_BYTES: uchar 3; int32 i0, i1, i2
+ *   order     vertices are numbered from 0 within an item in order (l, y, x),
+ *        faces run in order (l, y, x, triangle) and hold their item's numbers
+ *   capacity  item b's records start at b * capacity * record bytes; records
+ *        numbered >= the capacity are not written, nor any byte beyond the
+ *        item's region; counts[b] = {vertices, faces} are always the true totals
+ * All fp32, every operation rounded on its own, divisions correctly rounded: the
+ * bytes are a function of the inputs alone.
+ * LSI_EINVAL for a NULL descriptor, L, H or W < 1, B outside [1, 65535],
+ * L H W > 2^28 (vertex and face numbers and a workgroup's dword index into an
+ * item's face bytes, < 2 L H W 13 / 4, then fit the kernels' int32), a negative
+ * stride, disp_min that is not positive and finite, a mask_min that is not
+ * finite, edge_ratio or merge_ratio outside [0, 1], unknown flag bits, a
+ * non-zero reserved word, a capacity outside [0, 2^29], or a misaligned buffer
+ * (vertices and workspace 16 bytes, everything else 4); then LSI_ENULL (mask may
+ * be NULL; vertices and faces only with a capacity of 0); then LSI_EWORKSPACE
+ * -- all before any launch.  Workspace: the index map (int32 per texel, -1
+ * where no vertex) and two int32 per LSI_MESH_CHUNK texels.  4 launches on
+ * `stream` whatever the data, 3 with a face capacity of 0: count per workgroup
+ * of LSI_MESH_CHUNK texels, exclusive scan of the workgroup totals per item in
+ * trips of LSI_MESH_SCAN_TRIP (writes counts), vertex records and index map,
+ * face records.  No atomics, no host synchronisation, no allocation, no state.
+ */
+#define LSI_MESH_FLIP_YZ 1u
+#define LSI_MESH_VERTEX_BYTES 16
+#define LSI_MESH_FACE_BYTES 13
+#define LSI_MESH_CHUNK 256
+#define LSI_MESH_SCAN_TRIP 256
+typedef struct LsiMeshDesc {
+  int32_t L, B, H, W;
+  int64_t tex_sl, tex_sb, tex_sy, tex_sx, tex_sc;
+  int64_t disp_sl, disp_sb, disp_sy, disp_sx;
+  int64_t mask_sl, mask_sb, mask_sy, mask_sx;
+  float disp_min, mask_min, edge_ratio, merge_ratio;
+  uint32_t flags;
+  int32_t reserved;       /* 0 */
+} LsiMeshDesc;
+/* Bytes of device scratch lsi_ldi_mesh needs; 0 for a descriptor the call
+ * refuses. */
+size_t lsi_ldi_mesh_workspace_bytes(const LsiMeshDesc* desc);
+int lsi_ldi_mesh(const LsiMeshDesc* desc, const float* tex, const float* mask,
+                 const float* disp, const float* kinv_dev, void* vertices,
+                 int64_t vertex_capacity, void* faces, int64_t face_capacity,
+                 int32_t* counts, void* workspace, size_t workspace_bytes,
+                 lsi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

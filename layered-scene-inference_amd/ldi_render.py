@@ -20,6 +20,15 @@ source and target images -- packed by one launch and written off-thread to
 per iteration and frame s, the hole fraction (the mean of 1 - c0 inside the
 `--splat_bdry_ignore` crop) and, at s = 0 and s = 1, the PSNR against the real
 image as rendered and as filled.
+
+With `--save_mesh true` the source LDI of batch element 0 -- the LDI the frames
+are splatted from -- is also written as a textured triangle mesh,
+`iter_%06d.ply` next to the sheet (lsi.geometry.mesh, DESIGN.md 4.24: one
+lsi_ldi_mesh call on the network's output in place; `--mesh_edge_ratio`,
+`--mesh_merge_ratio`, `--mesh_disp_min`, `--mesh_flip_yz`), listed with its
+vertex and face counts in `render.json` and `index.html`: a surface to orbit in
+MeshLab, Blender or Open3D, cut at depth discontinuities, with the hidden layers
+behind the foreground.  Without the flag nothing of this runs.
 """
 import json
 import os
@@ -34,7 +43,7 @@ if _HERE not in sys.path:
 
 import ldi_enc_dec as train_script  # noqa: E402
 import ldi_pred_eval as ev  # noqa: E402
-from lsi.geometry import fill, ldi as ldi_utils, trajectory  # noqa: E402
+from lsi.geometry import fill, ldi as ldi_utils, mesh as mesh_utils, trajectory  # noqa: E402
 from lsi.loss import loss as loss_utils  # noqa: E402
 from lsi.nnutils import eval_metrics  # noqa: E402
 
@@ -53,6 +62,19 @@ def build_parser():
   a('--fill_conf_min', type=float, default=1e-3,
     help='a pixel whose share from the layers is below this is a hole')
   a('--num_render_iter', type=int, default=4, help='pairs to render')
+  a('--save_mesh', type=train_script._bool, default=False,
+    help='write the source LDI of batch element 0 as a textured triangle mesh, '
+    'iter_%%06d.ply (lsi.geometry.mesh, lsi_ldi_mesh)')
+  a('--mesh_edge_ratio', type=float, default=mesh_utils.EDGE_RATIO,
+    help='a triangle whose smallest disparity is below this times its largest is '
+    'cut (a depth discontinuity); a starting value, not a tuned one')
+  a('--mesh_merge_ratio', type=float, default=0.,
+    help='> 0: a hidden-layer texel whose disparity is at least this times the '
+    'disparity of the layer in front is dropped')
+  a('--mesh_disp_min', type=float, default=1e-3,
+    help='texels with a smaller disparity are no surface')
+  a('--mesh_flip_yz', type=train_script._bool, default=True,
+    help='y up, looking down -z, as mesh viewers expect (false: camera axes)')
   return p
 
 
@@ -106,6 +128,10 @@ class Renderer(ev.Tester):
     dev = tr.device
     imgs_src, imgs_trg = imgs_src.to(dev), imgs_trg.to(dev)
     ldi_src, _ = tr.model(imgs_src, imgs_trg)
+    # the mesh of batch element 0: the network's output read in place (views,
+    # through their strides), before it is repeated over the cameras
+    mesh = self.mesh([None if x is None else ev._f32(x)[:, :1] for x in ldi_src],
+                     k_s[:1]) if o.save_mesh else None
     n = len(self.s)
     rep = lambda x: None if x is None else ev._f32(x)[:, :1].expand(
         -1, n, -1, -1, -1).contiguous()
@@ -129,8 +155,19 @@ class Renderer(ev.Tester):
           if img is not None:
             f[key] = self.psnr(img[:, i:i + 1], real, [x[i:i + 1] for x in cams])
       frames.append(f)
-    return {'s': list(self.s), 'cams': cams, 'ldi': ldi_k, 'raw': raw, 'wts': wts,
-            'conf': conf, 'filled': filled, 'imgs': (imgs_src, imgs_trg), 'frames': frames}
+    out = {'s': list(self.s), 'cams': cams, 'ldi': ldi_k, 'raw': raw, 'wts': wts,
+           'conf': conf, 'filled': filled, 'imgs': (imgs_src, imgs_trg), 'frames': frames}
+    if mesh is not None:
+      out['mesh'] = mesh           # (only with --save_mesh: an LdiMesh, not waited for)
+    return out
+
+  def mesh(self, ldi, k_s):
+    """The LdiMesh of an LDI under --mesh_*: one lsi_ldi_mesh call, no
+    synchronisation."""
+    o = self.opts
+    return mesh_utils.ldi_mesh(ldi, k_s.detach().cpu().float(), disp_min=o.mesh_disp_min,
+                               edge_ratio=o.mesh_edge_ratio, merge_ratio=o.mesh_merge_ratio,
+                               flip_yz=o.mesh_flip_yz)
 
   def psnr(self, frame, real, cams):
     """The evaluation's PSNR (eval_metrics.view_synthesis_metrics) of one frame
@@ -168,6 +205,11 @@ class Renderer(ev.Tester):
         writer.submit('iter_%06d' % it, sheet, sb.names, sb.meta())
         sb.clear()
         iters.append({'file': 'iter_%06d.png' % it, 'frames': r['frames']})
+        if 'mesh' in r:
+          # counts and used records to the host (the mesh's one wait); the file
+          # is written by the writer's thread
+          (vertices, faces), = r['mesh'].to_host()
+          iters[-1]['mesh'] = writer.submit_mesh('iter_%06d' % it, vertices, faces)
     finally:
       writer.close()
     with open(os.path.join(res_dir, 'render.json'), 'w') as f:

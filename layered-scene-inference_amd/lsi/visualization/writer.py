@@ -20,7 +20,9 @@ class VisualWriter(object):
   that.  `close()` joins the worker, writes `visuals.json` (per sheet: file,
   grid, cell size, names, value ranges) and a plain `index.html`, and re-raises
   the first exception the worker met.  Host uint8 arrays are accepted in place
-  of device sheets (no copy to pin, no event)."""
+  of device sheets (no copy to pin, no event).  `submit_mesh` hands the same
+  worker the host records of a mesh (lsi.geometry.mesh) to write as
+  `<directory>/<stem>.ply`; the page lists the meshes after the sheets."""
 
   def __init__(self, directory, max_pending=2):
     if max_pending < 1:
@@ -28,6 +30,7 @@ class VisualWriter(object):
     self.directory = directory
     os.makedirs(directory, exist_ok=True)
     self.sheets = []             # the legend entries, in submission order
+    self.meshes = []             # {file, vertices, faces} of the meshes, likewise
     self._slots = threading.Semaphore(max_pending)
     self._jobs = queue.Queue()
     self._pinned = {}            # bytes -> idle pinned buffers of that size
@@ -69,15 +72,30 @@ class VisualWriter(object):
     self.sheets.append(entry)
     self._jobs.put((entry['file'], host, event, (hs, ws, pitch)))
 
+  def submit_mesh(self, stem, vertices, faces):
+    """vertices, faces: host record arrays of one item (LdiMesh.to_host)."""
+    if self._thread is None:
+      raise RuntimeError('the writer is closed')
+    from lsi.geometry import mesh  # pylint: disable=g-import-not-at-top
+    self._slots.acquire()
+    entry = {'file': stem + '.ply', 'vertices': len(vertices), 'faces': len(faces)}
+    self.meshes.append(entry)
+    path = os.path.join(self.directory, entry['file'])
+    self._jobs.put((entry['file'], lambda: mesh.write_ply(path, vertices, faces), None, None))
+    return entry
+
   def _work(self):
     from PIL import Image  # pylint: disable=g-import-not-at-top
     while True:
       job = self._jobs.get()
       if job is None:
         return
-      name, host, event, (hs, ws, pitch) = job
+      name, host, event, size = job
       try:
-        if self._error is None:
+        if self._error is None and size is None:
+          host()                   # a mesh: its file
+        elif self._error is None:
+          hs, ws, pitch = size
           if event is not None:
             event.synchronize()
             rows = np.lib.stride_tricks.as_strided(host.numpy(), (hs, ws, 3),
@@ -128,5 +146,9 @@ class VisualWriter(object):
                                           ' [%g, %g]' % tuple(rng) if rng else ''))
         out.append('<tr>%s</tr>' % ''.join(cells))
       out.append('</table>')
+    for m in self.meshes:
+      out.append('<p><a href="%s">%s</a>: %d vertices, %d faces</p>' %
+                 (html.escape(m['file'], quote=True), html.escape(m['file']),
+                  m['vertices'], m['faces']))
     out.append('</body></html>')
     return '\n'.join(out) + '\n'

@@ -17,6 +17,7 @@ the view-synthesis loss has something consistent to explain); the SUN / PASCAL
 textures of the synthetic scenes are procedural as well.
 """
 import argparse
+import contextlib
 import math
 import os
 import sys
@@ -29,7 +30,7 @@ if _HERE not in sys.path:
 
 from lsi.geometry import ldi as ldi_utils  # noqa: E402
 from lsi.geometry import projection  # noqa: E402
-from lsi.loss import loss  # noqa: E402
+from lsi.loss import objective  # noqa: E402
 from lsi.nnutils import helpers as nn_helpers  # noqa: E402
 from lsi.nnutils import nets  # noqa: E402
 from lsi.nnutils import train_utils  # noqa: E402
@@ -559,9 +560,8 @@ class Trainer(train_utils.Trainer):
       raise RuntimeError('the renderer and the six loss terms are HIP kernels: '
                          'training needs a ROCm device')
     imgs_src, imgs_trg, mat_trg, mat_src = staged[:4]
-    mats = {'trg': mat_trg, 'src': mat_src}
     amp = (torch.autocast('cuda', dtype=torch.bfloat16) if opts.bf16
-           else _NullCtx())
+           else contextlib.nullcontext())
     if hasattr(self, 'model'):
       self.model.pair_ldi = None
     with amp:
@@ -571,256 +571,24 @@ class Trainer(train_utils.Trainer):
       ldi_src[2] = 0 * ldi_src[2] + staged[4]
       ldi_trg[2] = 0 * ldi_trg[2] + staged[5]
 
-    def ones_like_mask(l):
-      return l[1] if l[1] is not None else torch.ones_like(l[2])
-
-    # The network's output is one buffer of 2 B LDIs (source views, then target
-    # views) whose halves `ldi_src` / `ldi_trg` are views of it.  A loss taken on
-    # a half sends its gradient back through a slice: autograd fills a zero
-    # tensor of the whole buffer per half and adds them up (texture, masks,
-    # disparities: a dozen kernels over 25 - 100 MB each per step).  Every term
-    # below is a mean over the batch, so the term of the pair is twice the mean
-    # over the 2 B LDIs: one call per term on the whole buffer, no slices.
+    # The pair as one buffer of 2 B views where the network made one (and no
+    # ground-truth disparities were substituted into its halves), else one
+    # group of views per direction: lsi/loss/objective.py
     pair = getattr(getattr(self, 'model', None), 'pair_ldi', None)
-    paired = (pair is not None and getattr(opts, 'paired_splat', True) and
-              not (opts.debug_synth_texture and len(staged) >= 6))
-
-    # self-consistency (ldi_enc_dec.py:269-294)
-    if paired and not opts.l0_self_cons:
-      self_cons_loss = 2.0 * loss.zbuffer_composition_loss(
-          pair[0], ones_like_mask(pair), pair[2],
-          torch.cat([imgs_src, imgs_trg], dim=0),
-          zbuf_scale=opts.zbuf_scale, bg_layer_disp=opts.bg_layer_disp,
-          max_disp=opts.max_disp)
-    elif opts.l0_self_cons:
-      sc_src = torch.mean(torch.abs(imgs_src - ldi_src[0][0]))
-      sc_trg = torch.mean(torch.abs(imgs_trg - ldi_trg[0][0]))
-    else:
-      sc_src = loss.zbuffer_composition_loss(
-          ldi_src[0], ones_like_mask(ldi_src), ldi_src[2], imgs_src,
-          zbuf_scale=opts.zbuf_scale, bg_layer_disp=opts.bg_layer_disp,
-          max_disp=opts.max_disp)
-      sc_trg = loss.zbuffer_composition_loss(
-          ldi_trg[0], ones_like_mask(ldi_trg), ldi_trg[2], imgs_trg,
-          zbuf_scale=opts.zbuf_scale, bg_layer_disp=opts.bg_layer_disp,
-          max_disp=opts.max_disp)
-    if not (paired and not opts.l0_self_cons):
-      self_cons_loss = sc_src + sc_trg
-
-    # view synthesis via forward splatting (ldi_enc_dec.py:296-357)
-    zero = imgs_src.new_zeros(())
-    indep_splat_loss, compose_splat_loss = zero, zero
-    ssim_wt = getattr(opts, 'ssim_wt', 0.0)
-    indep_ssim_loss, compose_ssim_loss = zero, zero
-
-    def ssim_loss(img, target):
-      return loss.ssim_view_synthesis_loss(
-          img, target, opts.splat_bdry_ignore, win=opts.ssim_win,
-          sigma=opts.ssim_sigma)
-    # One sweep per direction renders the per-layer AND the composed view
-    # (the reference makes four forward_splat calls whose per-layer splats
-    # are identical pairwise).
-    mat2 = None
-    if paired and (opts.indep_splat_wt > 0 or opts.compose_splat_wt > 0):
-      # Both directions of the pair from ONE launch (and one in the backward):
-      # the network's output is one buffer of 2 B LDIs -- the B source views'
-      # then the B target views' -- so the src -> trg and the trg -> src
-      # renderings (reference ldi_enc_dec.py:302-334) are a batch of 2 B
-      # elements with their own matrices, compared with [imgs_trg; imgs_src].
-      # A rank with 4 samples then issues 8-view launches instead of twice 4.
-      # Each loss term is a mean over the batch: the mean over 2 B samples is
-      # half the sum of the two directions' means.
-      mat2 = torch.cat([mats['trg'], mats['src']], dim=0)
-      host2 = torch.cat([self.host_mats['trg'], self.host_mats['src']], dim=0)
-      target2 = torch.cat([imgs_trg, imgs_src], dim=0)
-      img_i, _, img_c, _ = ldi_utils.forward_splat_both(
-          pair, mat2, trg_downsampling=opts.trg_splat_downsampling,
-          zbuf_scale=opts.zbuf_scale, bg_layer_disp=opts.bg_layer_disp,
-          max_disp=opts.max_disp, mat_host=host2)
-      if opts.indep_splat_wt > 0:
-        indep_splat_loss = 2.0 * loss.view_synthesis_loss(
-            img_i, target2, opts.splat_bdry_ignore)
-        if ssim_wt > 0:
-          indep_ssim_loss = 2.0 * ssim_loss(img_i, target2)
-      if opts.compose_splat_wt > 0:
-        compose_splat_loss = 2.0 * loss.view_synthesis_loss(
-            img_c, target2, opts.splat_bdry_ignore)
-        if ssim_wt > 0:
-          compose_ssim_loss = 2.0 * ssim_loss(img_c, target2)
-    elif opts.indep_splat_wt > 0 or opts.compose_splat_wt > 0:
-      for which in ('trg', 'src'):
-        if which == 'trg':
-          target, l = imgs_trg, ldi_src
-        else:
-          target, l = imgs_src, ldi_trg
-        img_i, _, img_c, _ = ldi_utils.forward_splat_both(
-            l, mats[which], trg_downsampling=opts.trg_splat_downsampling,
-            zbuf_scale=opts.zbuf_scale, bg_layer_disp=opts.bg_layer_disp,
-            max_disp=opts.max_disp, mat_host=self.host_mats[which])
-        if opts.indep_splat_wt > 0:
-          indep_splat_loss = indep_splat_loss + loss.view_synthesis_loss(
-              img_i, target, opts.splat_bdry_ignore)
-          if ssim_wt > 0:
-            indep_ssim_loss = indep_ssim_loss + ssim_loss(img_i, target)
-        if opts.compose_splat_wt > 0:
-          compose_splat_loss = compose_splat_loss + loss.view_synthesis_loss(
-              img_c, target, opts.splat_bdry_ignore)
-          if ssim_wt > 0:
-            compose_ssim_loss = compose_ssim_loss + ssim_loss(img_c, target)
-
-    # regularisers (ldi_enc_dec.py:388-396): both from one read of each
-    # disparity tensor (fused HIP kernel lsi_disp_reg_loss_fwd)
-    from lsi.loss import _hip as loss_hip  # pylint: disable=g-import-not-at-top
-    if paired:
-      sm_p, dc_p = loss_hip.disp_regularisers(pair[2])
-      disp_smoothness_loss = 2.0 * sm_p
-      incr_depth_loss = 2.0 * dc_p if opts.n_layers > 1 else zero
-    else:
-      sm_s, dc_s = loss_hip.disp_regularisers(ldi_src[2])
-      sm_t, dc_t = loss_hip.disp_regularisers(ldi_trg[2])
-      disp_smoothness_loss = sm_s + sm_t
-      incr_depth_loss = (dc_s + dc_t) if opts.n_layers > 1 else zero
-
-    # edge-aware smoothness (no reference counterpart)
-    edge_wt = getattr(opts, 'edge_smooth_wt', 0.0)
-    if edge_wt > 0:
-      by_texture = opts.edge_smooth_guide == 'texture'
-
-      def edge_loss(l, imgs):
-        return loss.edge_aware_smoothness_loss(
-            l[2], l[0].detach() if by_texture else imgs,
-            alpha=opts.edge_smooth_alpha, order=opts.edge_smooth_order,
-            normalise=opts.edge_smooth_norm)
-      if paired:
-        edge_smooth_loss = 2.0 * edge_loss(
-            pair, None if by_texture else torch.cat([imgs_src, imgs_trg], dim=0))
-      else:
-        edge_smooth_loss = (edge_loss(ldi_src, imgs_src) +
-                            edge_loss(ldi_trg, imgs_trg))
-
-    # depth supervision of layer 0 (no reference counterpart)
-    dsup_wt = getattr(opts, 'depth_sup_wt', 0.0)
-    if dsup_wt > 0:
-      source = getattr(self, 'depth_sup_source', None)
+    if not getattr(opts, 'paired_splat', True) or (
+        opts.debug_synth_texture and len(staged) >= 6):
+      pair = None
+    coef = objective.loss_coefficients(opts)
+    source, gt = getattr(self, 'depth_sup_source', None), (None, None)
+    if 'depth_sup' in coef:
       if source is None:
         raise ValueError('--depth_sup_wt > 0 needs ground-truth depth from: ' +
                          DEPTH_SUP_SOURCES)
-      gt2, scale2 = (staged[-2:] if source == 'px' else (staged[-1], None))
-
-      def depth_loss(disps, gt, scale):
-        return loss.depth_supervision_loss(
-            disps[0], gt, scale, mode=opts.depth_sup_mode, lam=opts.depth_sup_lambda,
-            valid_above=opts.bg_layer_disp if source == 'planes' else 0.,
-            depth_min=opts.depth_sup_min, depth_max=opts.depth_sup_max)
-      if paired:
-        depth_sup_loss = 2.0 * depth_loss(pair[2], gt2, scale2)
-      else:
-        b = imgs_src.shape[0]
-        half = lambda t, k: None if t is None else t[k * b:(k + 1) * b]
-        depth_sup_loss = (depth_loss(ldi_src[2], half(gt2, 0), half(scale2, 0)) +
-                          depth_loss(ldi_trg[2], half(gt2, 1), half(scale2, 1)))
-
-    # geometric consistency of the two views' layer 0 (no
-    # reference counterpart)
-    geo_wt = getattr(opts, 'geo_cons_wt', 0.0)
-    if geo_wt > 0:
-      geo_kw = dict(mode=opts.geo_cons_mode, occl_thresh=opts.geo_cons_occl)
-      if paired:
-        # one call on the 2 B views: plane b's partner is plane b +- B; the
-        # matrices are the paired splat's, built here when its weights are 0
-        if mat2 is None:
-          mat2 = torch.cat([mats['trg'], mats['src']], dim=0)
-        geo_cons_loss = 2.0 * loss.geometric_consistency_loss(pair[2][0], mat2, **geo_kw)
-      else:
-        geo_cons_loss = (
-            loss.geometric_consistency_loss(ldi_src[2][0], mats['trg'],
-                                            partner_disps=ldi_trg[2][0], **geo_kw) +
-            loss.geometric_consistency_loss(ldi_trg[2][0], mats['src'],
-                                            partner_disps=ldi_src[2][0], **geo_kw))
-
-    # backward-warp photometric term (no reference counterpart)
-    photo_wt = getattr(opts, 'photo_reproj_wt', 0.0)
-    if photo_wt > 0:
-      photo_kw = dict(mode=opts.photo_reproj_mode, occl_thresh=opts.photo_reproj_occl)
-      by_texture = opts.photo_reproj_what == 'texture'
-
-      def photo_loss(l, own_imgs, other_imgs, mat, visible, shift):
-        # texture: all layers at their own disparities; image: layer 0's
-        # disparities under the view's own input image
-        tex, disps = (l[0], l[2]) if by_texture else (own_imgs, l[2][0])
-        return loss.photometric_reprojection_loss(
-            tex, disps, other_imgs, mat,
-            partner_disps=visible.detach(), shift=shift, **photo_kw)
-      if paired:
-        # one call on the 2 B views: a plane of view q samples the input image of
-        # view q +- B; the matrices are the paired splat's
-        if mat2 is None:
-          mat2 = torch.cat([mats['trg'], mats['src']], dim=0)
-        imgs2 = torch.cat([imgs_src, imgs_trg], dim=0)
-        photo_reproj_loss = 2.0 * photo_loss(pair, imgs2, imgs2, mat2, pair[2][0],
-                                             imgs_src.shape[0])
-      else:
-        photo_reproj_loss = (
-            photo_loss(ldi_src, imgs_src, imgs_trg, mats['trg'], ldi_trg[2][0], 0) +
-            photo_loss(ldi_trg, imgs_trg, imgs_src, mats['src'], ldi_src[2][0], 0))
-
-    total = zero
-    if opts.self_cons_wt > 0:
-      total = total + opts.self_cons_wt * self_cons_loss
-    if opts.compose_splat_wt > 0:
-      total = total + opts.compose_splat_wt * compose_splat_loss
-    if opts.indep_splat_wt > 0:
-      total = total + opts.indep_splat_wt * indep_splat_loss
-    if ssim_wt > 0:
-      # the structural terms ride on the L1 terms' weights
-      total = total + ssim_wt * (opts.compose_splat_wt * compose_ssim_loss +
-                                 opts.indep_splat_wt * indep_ssim_loss)
-    if opts.incr_depth_wt > 0:
-      total = total + (opts.incr_depth_wt / opts.max_disp) * incr_depth_loss
-    if opts.disp_smoothness_wt > 0:
-      total = total + (opts.disp_smoothness_wt /
-                       (opts.max_disp * opts.max_disp)) * disp_smoothness_loss
-    if edge_wt > 0:
-      # normalised, the term is scale-free; else both orders are linear in d
-      total = total + (edge_wt if opts.edge_smooth_norm
-                       else edge_wt / opts.max_disp) * edge_smooth_loss
-    if dsup_wt > 0:
-      total = total + dsup_wt * depth_sup_loss
-    if geo_wt > 0:
-      # the ratio is scale-free; l1 is linear in d
-      total = total + (geo_wt / opts.max_disp if opts.geo_cons_mode == 'l1'
-                       else geo_wt) * geo_cons_loss
-    if photo_wt > 0:
-      total = total + photo_wt * photo_reproj_loss
-    scalars = {
-        'self_cons_loss': self_cons_loss,
-        'compose_splat_loss': compose_splat_loss,
-        'indep_splat_loss': indep_splat_loss,
-        'incr_depth_loss': incr_depth_loss,
-        'disp_smoothness_loss': disp_smoothness_loss,
-        'total_loss': total,
-    }
-    if ssim_wt > 0:
-      scalars['compose_ssim_loss'] = compose_ssim_loss
-      scalars['indep_ssim_loss'] = indep_ssim_loss
-    if edge_wt > 0:
-      scalars['edge_smooth_loss'] = edge_smooth_loss
-    if dsup_wt > 0:
-      scalars['depth_sup_loss'] = depth_sup_loss
-    if geo_wt > 0:
-      scalars['geo_cons_loss'] = geo_cons_loss
-    if photo_wt > 0:
-      scalars['photo_reproj_loss'] = photo_reproj_loss
-    return total, scalars
-
-
-class _NullCtx(object):
-
-  def __enter__(self):
-    return self
-
-  def __exit__(self, *a):
-    return False
+      gt = staged[-2:] if source == 'px' else (staged[-1], None)
+    groups, halves = objective.view_groups(
+        ldi_src, ldi_trg, pair, (imgs_src, imgs_trg), (mat_trg, mat_src),
+        (self.host_mats['trg'], self.host_mats['src']), gt)
+    return objective.objective(groups, halves, opts, coef, source)
 
 
 def main(argv=None):

@@ -1988,6 +1988,93 @@ int lsi_ldi_mesh(const LsiMeshDesc* desc, const float* tex, const float* mask,
                  int32_t* counts, void* workspace, size_t workspace_bytes,
                  lsi_stream_t stream);
 
+/*
+ * The surface of lsi_ldi_mesh rasterised into V target views per item with a
+ * z-buffer (csrc/lsi_ldi_raster.hip).  Forward only.
+ *   tex, disp, mask  as lsi_ldi_mesh reads them, through the ELEMENT strides
+ *   M        [B,V,4,4] float, device, contiguous: source pixel (u, v, 1, disp)
+ *            to target frame (projection.forward_projection_matrix)
+ *   img      [B,V,Ht,Wt,3] float, cov [B,V,Ht,Wt] float (1: a triangle won the
+ *            pixel, 0: a hole), out_disp [B,V,Ht,Wt] float or NULL (the
+ *            winner's target disparity, 0 at holes): device, written fully
+ *   vertex   texel (l, y, x) of item b is a vertex iff lsi_ldi_mesh's rule holds
+ *            (in range, mask, not merged).  Under view (b, v), with d its
+ *            disparity, px = x + .5, py = y + .5 (the renderer's contract):
+ *              q_j = ((px M[j][0] + py M[j][1]) + M[j][2]) + d M[j][3]
+ *              n = q_2, u = q_0 / n, v = q_1 / n, dd = q_3 / n
+ *            usable iff u, v, dd are finite, n > 0, dd > 0, |u| <= 16384 and
+ *            |v| <= 16384 (LSI_RASTER_GUARD); snapped to LSI_RASTER_SUBPIXEL_BITS
+ *            bits: X = (int)rintf(u * 256), Y = (int)rintf(v * 256), to nearest
+ *            even
+ *   triangle the export's (a, c, b) and (b, c, d) of the quad a = (y, x); it
+ *            exists iff its vertices exist and are usable and
+ *            min(d_i) >= edge_ratio * max(d_i).  No near-plane clipping.
+ *            id = ((l H + y) W + x) 2 + t.  In int64
+ *              A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0)
+ *            A == 0 drops it.  The export's order gives A < 0 where the view
+ *            keeps the source's orientation: vertices 1 and 2 are swapped
+ *            (then A is -A > 0).  A > 0 before any swap: the view sees the
+ *            back of the surface; LSI_RASTER_CULL_BACK drops the triangle,
+ *            without the flag it is kept as it is (a two-sided surface).
+ *            Pixel (i, j) has its centre at (256 i + 128, 256 j + 128).  The box
+ *            i0 = (min X + 127) >> 8 .. i1 = (max X - 128) >> 8 (j likewise), the
+ *            centres within the triangle's extent, is clipped to the frame; an
+ *            empty box, or a clipped box wider or taller than max_extent
+ *            pixels, drops the triangle.
+ *   coverage for the edges k = 0, 1, 2 from vertex a to vertex b, (a, b) =
+ *            (1, 2), (2, 0), (0, 1), with dx = Xb - Xa, dy = Yb - Ya, in int64
+ *              E_k = dx (py - Ya) - dy (px - Xa)
+ *            inside iff for every k: E_k > 0, or E_k == 0 and the edge is top-left
+ *            (dy < 0, or dy == 0 and dx > 0): a shared edge has one owner.
+ *   depth    b1 = (float)E_1 / (float)A, b2 = (float)E_2 / (float)A,
+ *            b0 = (1 - b1) - b2, z = (b0 dd_0 + b1 dd_1) + b2 dd_2; a z that is
+ *            not finite or not positive is no hit.
+ *   z-test   key = bits(z) << 32 | (0xFFFFFFFF - id), combined per pixel by an
+ *            unsigned 64-bit atomic maximum: the nearest wins, ties go to the
+ *            lowest id, whatever the order of arrival.
+ *   resolve  key 0: img = bg_value, cov = 0, out_disp = 0.  Otherwise the
+ *            winner's vertices, E_k and b_k are formed again and per channel
+ *            c = (b0 c_0 + b1 c_1) + b2 c_2 from tex; cov = 1, out_disp = z.
+ * All fp32, every operation rounded on its own, divisions correctly rounded, the
+ * int64 -> float conversions to nearest even: the outputs are a function of the
+ * inputs alone, bit for bit.
+ * LSI_EINVAL for what lsi_ldi_mesh refuses on the shared fields, V outside
+ * [1, 1024], B V > 65535, Ht or Wt outside [1, 8192], max_extent outside
+ * [1, 256], a bg_value that is not finite, unknown flag bits, a non-zero
+ * reserved word or a misaligned buffer (workspace 16 bytes, everything else 4);
+ * then LSI_ENULL (mask and out_disp may be NULL); then LSI_EWORKSPACE -- all
+ * before any launch.  Workspace: the keys, 8 bytes per target pixel, then 16
+ * bytes {X, Y, dd, d} per (b, v, l, y, x) (dd = 0: no usable vertex).  4
+ * launches on `stream` whatever the data: clear the keys, project, rasterise
+ * (a thread per texel and view: the corner a of its quad), resolve.  No host synchronisation, no
+ * allocation, no state, plain vector stores and atomics only.
+ */
+#define LSI_RASTER_CULL_BACK 1u
+#define LSI_RASTER_SUBPIXEL_BITS 8
+#define LSI_RASTER_GUARD 16384
+#define LSI_RASTER_MAX_VIEWS 1024
+#define LSI_RASTER_MAX_SIZE 8192
+#define LSI_RASTER_MAX_EXTENT 256
+typedef struct LsiRasterDesc {
+  int32_t L, B, H, W;
+  int64_t tex_sl, tex_sb, tex_sy, tex_sx, tex_sc;
+  int64_t disp_sl, disp_sb, disp_sy, disp_sx;
+  int64_t mask_sl, mask_sb, mask_sy, mask_sx;
+  int32_t V, Ht, Wt;
+  int32_t max_extent;
+  float disp_min, mask_min, edge_ratio, merge_ratio;
+  float bg_value;
+  uint32_t flags;
+  int32_t reserved;       /* 0 */
+} LsiRasterDesc;
+/* Bytes of device scratch lsi_ldi_raster needs; 0 for a descriptor the call
+ * refuses. */
+size_t lsi_ldi_raster_workspace_bytes(const LsiRasterDesc* desc);
+int lsi_ldi_raster(const LsiRasterDesc* desc, const float* tex, const float* mask,
+                   const float* disp, const float* M, float* img, float* cov,
+                   float* out_disp, void* workspace, size_t workspace_bytes,
+                   lsi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

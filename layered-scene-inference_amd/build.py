@@ -25,7 +25,7 @@ SOURCES = ['lsi_splat.hip', 'lsi_splat_stream.hip', 'lsi_splat_stream2.hip',
            'lsi_geo_cons.hip', 'lsi_photo_reproj.hip',
            'lsi_visual.hip',
            'lsi_depth_metrics.hip', 'lsi_sgm.hip', 'lsi_disp_filter.hip',
-           'lsi_lidar.hip', 'lsi_fill.hip', 'lsi_ldi_mesh.hip']
+           'lsi_lidar.hip', 'lsi_fill.hip', 'lsi_ldi_mesh.hip', 'lsi_ldi_raster.hip']
 HEADERS = [os.path.join(CSRC, 'lsi_common.h'),
            os.path.join(CSRC, 'lsi_layers.h'),
            os.path.join(CSRC, 'lsi_reduce.h'),

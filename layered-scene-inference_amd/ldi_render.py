@@ -29,6 +29,21 @@ lsi_ldi_mesh call on the network's output in place; `--mesh_edge_ratio`,
 vertex and face counts in `render.json` and `index.html`: a surface to orbit in
 MeshLab, Blender or Open3D, cut at depth discontinuities, with the hidden layers
 behind the foreground.  Without the flag nothing of this runs.
+
+With `--render_mesh true` the same K cameras also render that surface with the
+z-buffered triangle rasteriser (lsi.geometry.raster, DESIGN.md 4.25: one
+lsi_ldi_raster call on the network's output in place, not repeated over the
+cameras; the `--mesh_*` options above and `--mesh_max_extent`) and its holes are
+filled by `fill.fill_holes`.  The sheet gains a `mesh` and a `mesh_filled` row
+above the real images, every frame of `render.json` gains `hole_fraction_mesh`
+(the mean of 1 - cov inside the same crop) and, at s = 0 and s = 1, `psnr_mesh`
+and `psnr_mesh_filled`.  A mesh has no cracks between magnified texels, but a
+triangle that `--mesh_edge_ratio` cuts or `--mesh_max_extent` drops is a hole of
+the mesh too: `hole_fraction` - `hole_fraction_mesh` is the cracks' share of
+the splat rendering's holes only where no triangle is cut (a smooth surface, or
+`--mesh_edge_ratio 0`); on noisy disparities, an untrained network's for one,
+the default ratio cuts most of the surface and the difference is negative.
+Without the flag nothing of this runs.
 """
 import json
 import os
@@ -43,7 +58,8 @@ if _HERE not in sys.path:
 
 import ldi_enc_dec as train_script  # noqa: E402
 import ldi_pred_eval as ev  # noqa: E402
-from lsi.geometry import fill, ldi as ldi_utils, mesh as mesh_utils, trajectory  # noqa: E402
+from lsi.geometry import (fill, ldi as ldi_utils, mesh as mesh_utils, raster,  # noqa: E402
+                          trajectory)
 from lsi.loss import loss as loss_utils  # noqa: E402
 from lsi.nnutils import eval_metrics  # noqa: E402
 
@@ -75,6 +91,12 @@ def build_parser():
     help='texels with a smaller disparity are no surface')
   a('--mesh_flip_yz', type=train_script._bool, default=True,
     help='y up, looking down -z, as mesh viewers expect (false: camera axes)')
+  a('--render_mesh', type=train_script._bool, default=False,
+    help='also render the frames by rasterising the LDI\'s triangle mesh '
+    '(lsi.geometry.raster, lsi_ldi_raster) under the --mesh_* options')
+  a('--mesh_max_extent', type=int, default=32,
+    help='a triangle stretched over more target pixels than this, in x or y, is '
+    'no surface and is not drawn (1 .. 256)')
   return p
 
 
@@ -146,12 +168,22 @@ class Renderer(ev.Tester):
     x0 = loss_utils._py2_round(wt * o.splat_bdry_ignore)
     y0 = loss_utils._py2_round(ht * o.splat_bdry_ignore)
     holes = (1.0 - conf[:, y0:ht - y0, x0:wt - x0]).mean(dim=(1, 2)).cpu()
+    scored = [('psnr_raw', raw), ('psnr_filled', filled)]
+    if o.render_mesh:
+      # the K frames of the mesh: the network's output read in place, one item
+      # under K cameras
+      m_img, m_cov, m_filled = self.rasterize(
+          [None if x is None else ev._f32(x)[:, :1] for x in ldi_src], cams)
+      m_holes = (1.0 - m_cov[0, :, y0:ht - y0, x0:wt - x0]).mean(dim=(1, 2)).cpu()
+      scored += [('psnr_mesh', m_img), ('psnr_mesh_filled', m_filled)]
     frames = []
     for i, s in enumerate(self.s):
       f = {'s': s, 'hole_fraction': float(holes[i])}
+      if o.render_mesh:
+        f['hole_fraction_mesh'] = float(m_holes[i])
       if s in (0.0, 1.0):
         real = ev._f32(imgs_src if s == 0.0 else imgs_trg)[:1]
-        for key, img in (('psnr_raw', raw), ('psnr_filled', filled)):
+        for key, img in scored:
           if img is not None:
             f[key] = self.psnr(img[:, i:i + 1], real, [x[i:i + 1] for x in cams])
       frames.append(f)
@@ -159,7 +191,23 @@ class Renderer(ev.Tester):
            'conf': conf, 'filled': filled, 'imgs': (imgs_src, imgs_trg), 'frames': frames}
     if mesh is not None:
       out['mesh'] = mesh           # (only with --save_mesh: an LdiMesh, not waited for)
+    if o.render_mesh:              # (only with --render_mesh: 1 x K x Ht x Wt [x 3])
+      out['mesh_raw'], out['mesh_cov'], out['mesh_filled'] = m_img, m_cov, m_filled
     return out
+
+  def rasterize(self, ldi, cams):
+    """The K frames of the mesh of a one-item LDI under --mesh_*: (img 1 x K x Ht
+    x Wt x 3, cov 1 x K x Ht x Wt, img with its holes filled) of one
+    lsi_ldi_raster and one lsi_fill_holes call.  The K matrices are built on the
+    host; their copy to the device blocks the host, nothing else does."""
+    o = self.opts
+    ht, wt = int(o.img_height * o.render_downsampling), int(o.img_width * o.render_downsampling)
+    img, cov, _ = raster.render_views(
+        ldi, *cams, trg_downsampling=o.render_downsampling, trg_size=(ht, wt),
+        disp_min=o.mesh_disp_min, edge_ratio=o.mesh_edge_ratio, merge_ratio=o.mesh_merge_ratio,
+        max_extent=o.mesh_max_extent)
+    filled = fill.fill_holes(img[0], cov[0], conf_min=o.fill_conf_min).unsqueeze(0)
+    return img, cov, filled
 
   def mesh(self, ldi, k_s):
     """The LdiMesh of an LDI under --mesh_*: one lsi_ldi_mesh call, no
@@ -195,7 +243,10 @@ class Renderer(ev.Tester):
       for it in range(o.num_render_iter):
         r = self.render_batch(batches[it] if batches else None)
         sb.clear()
-        for key, img in (('raw', r['raw']), ('filled', r['filled'])):
+        rows = [('raw', r['raw']), ('filled', r['filled'])]
+        if o.render_mesh:
+          rows += [('mesh', r['mesh_raw']), ('mesh_filled', r['mesh_filled'])]
+        for key, img in rows:
           if img is not None:
             for i, s in enumerate(r['s']):
               sb.add_rgb('%s_s_%+.3f' % (key, s), img[0, i])
